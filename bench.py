@@ -18,16 +18,24 @@ rank scans its shard, candidate blocks are all-gathered over RCCL, each rank
 merges its slice of the queries (tsh_search_sharded, include/tostore_hip.h).
 
 Timing: W warm-up steps, then a timed region of EXACTLY K steps between a
-barrier + device synchronise on both sides, MAX over ranks.  That region is
-repeated (--repeats, default: enough regions for about 2000 timed steps, at
-most 25) and the MEDIAN region is the one reported: a 20-step region lasts
-9 ms, one region alone is noise.  Every region's time is in the line.
+barrier + device synchronise on both sides, MAX over ranks.  A plain run times
+that one region: --steps is the number of timed steps.  --repeats R times R
+such regions and reports the MEDIAN one; --full does so by default (enough
+regions for about 2000 timed steps, at most 25: a 20-step region lasts 9 ms).
+Every region's time is in the line.
 
-Prints ONE JSON line on rank 0.  Besides the headline it carries
-`roofline`, `cpu_baseline` and a `side` object with the other BASELINE.json
-configurations measured in the same process (C1 latency, C3 1024-query
-batches, C5 masked scans); a side leg that fails reports its error text and
-never takes the headline down.
+Prints ONE JSON line on rank 0: the headline, its `roofline` (from the HIP
+events of the timed scans) and the library's counters.  --dump-outputs DIR
+also writes the answer of the last timed step (ids, distances, count) as
+DIR/<name>.npy, float64.
+
+--full adds everything else, each in runs of its own after the headline:
+recall@k and `cpu_baseline` against the CPU oracle, the one-at-a-time latency
+leg, the scan kernel timed back to back, and a `side` object with the other
+BASELINE.json configurations measured in the same process (C1 latency, C3
+1024-query batches, C5 masked scans, one rank's share at N = 8; N > 1: C4's
+per-rank shape); a side leg that fails reports its error text and never takes
+the headline down.
 
 N > 1 lines carry `exchange_timeline` (where every rank's tsh_search_sharded time
 went, phase by phase, against ms_per_step), `host_cpu` per rank, and a `side.C4_per_rank`
@@ -82,7 +90,13 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed regions of --steps steps each; the median one is reported (0 = auto)")
+                    help="timed regions of --steps steps each; the median one is reported (0 = one region, or with "
+                         "--full enough regions for about 2000 timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: recall and CPU baselines against the oracle, the latency leg, the scan "
+                         "kernel timed alone, and the side legs (other configurations); off: the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the answer of the last timed step (ids, distances, count) as DIR/<name>.npy, float64")
     ap.add_argument("--config", default="c2", choices=["c2", "c4"],
                     help="BASELINE.json configuration: c2 = 1M x 768 L2 k=100 (the headline), c4 = 10M x 1536 inner "
                          "product k=100 (row-sharded over --gpus ranks); --rows / --dim / --k / --metric override")
@@ -179,6 +193,14 @@ def auto_repeats(steps, repeats=0):
     return int(max(3, min(25, math.ceil(2000 / max(steps, 1)))))
 
 
+def timed_repeats(steps, repeats=0, full=False):
+    """Timed regions of a run: --repeats when given, else one region (a plain run times exactly --steps steps) or,
+    with --full, auto_repeats()."""
+    if repeats > 0:
+        return repeats
+    return auto_repeats(steps) if full else 1
+
+
 def query_pool_size(steps, warmup, recall_queries, batch=0):
     """Distinct queries generated up front.  Every later index into the pool is taken modulo its
     length, and the pool is never smaller than what the baseline / recall legs read."""
@@ -233,6 +255,24 @@ def clean_json(o):
 
 def dumps(o):
     return json.dumps(clean_json(o), allow_nan=False)
+
+
+def last_answer(res):
+    """What a caller received for the LAST query of one call -> (ids, distances, count) of that query."""
+    if len(res) == 2:  # submit / wait: one query's ids and distances, already cut to its count
+        ids, dist = (np.asarray(x).reshape(-1) for x in res)
+        return ids, dist, len(ids)
+    ids, dist, cnt = res
+    c = int(np.asarray(cnt).reshape(-1)[-1])
+    return np.asarray(ids)[-1, :c], np.asarray(dist)[-1, :c], c
+
+
+def dump_outputs(path, ids, dist, cnt):
+    """--dump-outputs: the answer of the last timed step as <path>/{ids,distances,count}.npy, float64 (row ids are
+    below 2**53: exact)."""
+    os.makedirs(path, exist_ok=True)
+    for name, x in (("ids", ids), ("distances", dist), ("count", np.reshape(cnt, -1))):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(x, dtype=np.float64))
 
 
 def make_queries(nq, d, metric, seed=20260613):
@@ -549,8 +589,9 @@ def two_callers_batch(env, idx, qs, nq, k, steps):
             "timing": "wall clock over all calls of both threads"}
 
 
-def measure_batch(env, idx, host_rows, metric, n, d, k, nq, steps, warm, kernel, check_queries):
-    """One step = one call with nq queries through the matrix-core path."""
+def measure_batch(env, idx, host_rows, metric, n, d, k, nq, steps, warm, kernel, check_queries, last=None):
+    """One step = one call with nq queries through the matrix-core path.  `last` (a list): the last step's answer is
+    appended to it."""
     steps, warm = max(1, steps), max(1, warm)
     qs = make_queries(nq * 2, d, metric, seed=20260615)
     idx.set_batch_min_nq(1)
@@ -567,6 +608,8 @@ def measure_batch(env, idx, host_rows, metric, n, d, k, nq, steps, warm, kernel,
             per_step.append(time.perf_counter() - t1)
         env.fence()
         mean_step = (time.perf_counter() - t0) / steps
+        if last is not None:
+            last.append((ids, dist, cnt))
         gemm_us, flops = idx.bench_batch(qs[:nq], k, iters=3)
         two = two_callers_batch(env, idx, qs, nq, k, steps)
     # the container's CPU quota freezes the process for milliseconds now and then (tools/attic/throttle_probe.py): the
@@ -603,7 +646,11 @@ def bench_batch(a, env, idx, host_rows, metric):
         idx.set_batch_hub(True)
     if a.plane_in_row_order and hasattr(idx, "set_batch_group"):
         idx.set_batch_group(False)
-    r = measure_batch(env, idx, host_rows, metric, n, d, k, nq, min(a.steps, 20), min(a.warmup, 3), a.batch_kernel, 128)
+    last = []
+    r = measure_batch(env, idx, host_rows, metric, n, d, k, nq, min(a.steps, 20), min(a.warmup, 3), a.batch_kernel, 128,
+                      last)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, *last[0])  # a step here is one call: all its nq queries' answers
     out = {"metric": "kNN queries/sec, %dx%d f32 %s k=%d, %d-query batch (matrix-core path)" % (n, d, a.metric, k, nq),
            "value": r["value"], "unit": "queries/s", "n_gpus": 1, "steps": r["steps"], "warmup": r["warmup"],
            "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -883,10 +930,11 @@ def exchange_timeline(per_rank, steps_total, ms_per_step):
 def measure_single(env, a, idx, searcher, queries, k, row_mask, steps, warmup, repeats):
     """The headline measurement: W warm-up steps, then `repeats` timed regions of exactly `steps` single-query
     searches each, every region between a barrier + device synchronise on both sides, MAX over ranks.
-    -> dict(regions, scan_us, scan samples, per-rank records on rank 0, cgroup stats)."""
+    -> dict(regions, scan_us, scan samples, per-rank records on rank 0, cgroup stats, the last call's answer)."""
     nqp = len(queries)
     py_groups = getattr(searcher, "python_groups", True)  # False: the library forms the groups (tsh_search_sharded)
     batches = {}
+    last = [None]  # what the last call returned: its last query is the last step
 
     def one(i):
         q = queries[i % nqp]
@@ -902,18 +950,19 @@ def measure_single(env, a, idx, searcher, queries, k, row_mask, steps, warmup, r
             return
         if a.inflight <= 1:
             for i in range(count):
-                one(first + i)
+                last[0] = one(first + i)
         elif searcher is not None:
             # N > 1: groups of queries share one all-gather + one merge call, and the next group's
             # shard scans run while this group is exchanged and merged
             qb = batches.get((first, count))
             if qb is None:
                 qb = queries[[(first + j) % nqp for j in range(count)]]
-            searcher.search_many(qb, k, None, row_mask, group=sharded_group(a.group, count) if py_groups else 0)
+            last[0] = searcher.search_many(qb, k, None, row_mask,
+                                           group=sharded_group(a.group, count) if py_groups else 0)
         elif a.group > 0:
             for g0 in range(0, count, a.group):
                 sel = [(first + g0 + j) % nqp for j in range(min(a.group, count - g0))]
-                idx.search(queries[sel], k, None, row_mask)
+                last[0] = idx.search(queries[sel], k, None, row_mask)
         else:
             from collections import deque
             pend = deque()
@@ -922,7 +971,7 @@ def measure_single(env, a, idx, searcher, queries, k, row_mask, steps, warmup, r
                     idx.wait(pend.popleft())
                 pend.append(idx.submit(queries[(first + i) % nqp], k, row_mask))
             while pend:
-                idx.wait(pend.popleft())
+                last[0] = idx.wait(pend.popleft())
 
     run(0, warmup)
     regions = []
@@ -971,7 +1020,7 @@ def measure_single(env, a, idx, searcher, queries, k, row_mask, steps, warmup, r
                                      cg0.get("throttled_usec", cg0.get("throttled_time", 0))) / 1e3,
                     "wall_s": t_cg1 - t_cg0}
     return {"regions": regions, "scan_us": scan_us, "scan_samples": int(ns), "per_rank": per_rank, "host_cpu": host_cpu,
-            "one": one, "py_groups": py_groups}
+            "one": one, "py_groups": py_groups, "last": last[0]}
 
 
 def side_c4_per_rank(env, a):
@@ -1199,6 +1248,7 @@ def run_bench(a, env=None):
     metric = METRICS[a.metric]
     world, rank = env.world, env.rank
     n, d, k = a.rows, a.dim, a.k
+    full = a.full  # everything besides the headline
 
     # ---- resident corpus: this rank generates and holds its own row range only -------
     per = (n + world - 1) // world
@@ -1206,7 +1256,7 @@ def run_bench(a, env=None):
     # a host copy for the CPU baseline / recall check, unless the corpus is too big for one (C4: 61 GB): then the
     # oracle sees it chunk by chunk, as in a sharded run
     big = float(n) * d * 4 > 16e9
-    want_host = rank == 0 and world == 1 and not a.no_cpu_baseline and not big
+    want_host = full and rank == 0 and world == 1 and not a.no_cpu_baseline and not big
     # --in-process: this one process holds all --gpus devices' shards in one handle (no ranks, no collective)
     n_dev = a.gpus if getattr(a, "in_process", False) and a.gpus > 1 else 1
     if n_dev > 1:
@@ -1237,10 +1287,12 @@ def run_bench(a, env=None):
     gc.collect()
     gc_was = gc.isenabled()
     gc.disable()
-    repeats = auto_repeats(a.steps, a.repeats)
+    repeats = timed_repeats(a.steps, a.repeats, full)
     m = measure_single(env, a, idx, searcher, queries, k, row_mask, a.steps, a.warmup, repeats)
     regions, one, py_groups = m["regions"], m["one"], m["py_groups"]
     elapsed = float(np.median(regions))
+    if a.dump_outputs and rank == 0 and m["last"] is not None:
+        dump_outputs(a.dump_outputs, *last_answer(m["last"]))
 
     # single-query latency, one at a time (not the headline value).  Round 2's line carried p99 = 42.8 ms: one
     # call in a few hundred coincided with a full (generation 2) collection of THIS harness's Python heap
@@ -1256,7 +1308,7 @@ def run_bench(a, env=None):
     gc.callbacks.append(_gc_cb)
     try:
         with timed_region():
-            for i in range(a.lat_queries if world == 1 else min(a.lat_queries, 200)):
+            for i in range((a.lat_queries if world == 1 else min(a.lat_queries, 200)) if full else 0):
                 t1 = time.perf_counter()
                 one(i)
                 lat.append(time.perf_counter() - t1)
@@ -1271,7 +1323,8 @@ def run_bench(a, env=None):
     # around real scan launches on its pipeline stream, during the timed regions above
     ns, scan_us = m["scan_samples"], m["scan_us"]
     with timed_region():  # (the hook measures ONE shard's kernel: a single-device handle)
-        scan_alone_us = idx.bench_scan(queries[0], iters=50, row_mask=row_mask) if hi > lo and n_dev == 1 else float("nan")
+        scan_alone_us = idx.bench_scan(queries[0], iters=50, row_mask=row_mask) if full and hi > lo and n_dev == 1 \
+            else float("nan")
     if not math.isfinite(scan_us):
         scan_us = scan_alone_us
     shard_bytes = float(min(per_dev, hi - lo)) * d * 4  # algorithmic: every stored f32 read once (per device: its shard)
@@ -1287,7 +1340,7 @@ def run_bench(a, env=None):
 
         ref, cpu_elapsed = bench_check.cpu_baseline_single(host_rows, queries, metric, k, row_mask, a.cpu_seconds)
         n_cpu = len(ref)
-    elif rank == 0 and not a.no_cpu_baseline:
+    elif full and rank == 0 and not a.no_cpu_baseline:
         # sharded run (or a corpus too big for a host copy): no process holds the corpus.  Rank 0 regenerates it
         # chunk by chunk (counter-based generator) and runs the exhaustive oracle on a few sampled queries -- a
         # parity check; cpu_baseline is reported at N = 1 only
@@ -1302,7 +1355,7 @@ def run_bench(a, env=None):
         if world == 1:  # big corpus on one GPU: the single-thread baseline on a bounded sample of its rows
             big_cpu = bench_check.cpu_baseline_sample_of_rows(env.oracle_chunks(n, d, metric), n, queries, metric, k,
                                                               row_mask, a.cpu_seconds)
-    n_cpu = env.bcast_int(n_cpu)
+    n_cpu = env.bcast_int(n_cpu) if full else 0
     got = [one(i) for i in range(n_cpu)]
 
     out = None
@@ -1357,7 +1410,7 @@ def run_bench(a, env=None):
                          "kernel_us_back_to_back_alone": scan_alone_us,
                          "algorithmic_bytes_per_launch": shard_bytes},
         }
-        if (min(per_dev, hi - lo) + 63) // 64 < 6144 and a.inflight > 1 and n_dev == 1:
+        if full and (min(per_dev, hi - lo) + 63) // 64 < 6144 and a.inflight > 1 and n_dev == 1:
             # shards below 6144 tiles alternate their scans between two streams: two scans
             # run side by side, so one launch's own duration is about twice its share of the HBM time
             out["roofline"]["scans_side_by_side"] = 2
@@ -1396,10 +1449,11 @@ def run_bench(a, env=None):
                                                                          max(2, min(n_cpu, 8)))
                 except Exception:  # noqa: BLE001
                     pass
-        out["latency_ms_one_at_a_time"] = {"p50": float(lat[len(lat) // 2]), "p99": float(lat[int(len(lat) * 0.99)]),
-                                           "max": float(lat[-1]), "argmax": int(np.argmax(lat_raw)),
-                                           "mean": float(lat.mean()), "queries": int(len(lat)),
-                                           "harness_gc_collections_inside": len(gc_ms)}
+        if full:
+            out["latency_ms_one_at_a_time"] = {"p50": float(lat[len(lat) // 2]), "p99": float(lat[int(len(lat) * 0.99)]),
+                                               "max": float(lat[-1]), "argmax": int(np.argmax(lat_raw)),
+                                               "mean": float(lat.mean()), "queries": int(len(lat)),
+                                               "harness_gc_collections_inside": len(gc_ms)}
         c = idx.counters()
         if m["host_cpu"]:
             out["host_cpu"] = m["host_cpu"]
@@ -1409,7 +1463,7 @@ def run_bench(a, env=None):
                            "candidates_per_query": c["candidates_total"] / max(c["searches"], 1)}
 
     # ---- C4 on ONE GPU (--config c4 --gpus 1): the 1024-query batched figure of SURVEY section 8d beside the headline
-    if world == 1 and rank == 0 and a.config == "c4" and a.mask_keep == 0 and not a.no_side:
+    if full and world == 1 and rank == 0 and a.config == "c4" and a.mask_keep == 0 and not a.no_side:
         try:
             r = measure_batch(env, idx, None, metric, n, d, k, 1024, 3, 1, 3, 0)
             out["batch_1024"] = {key: r[key] for key in ("value", "unit", "ms_per_step", "ms_per_step_max", "batch_kernel",
@@ -1427,7 +1481,8 @@ def run_bench(a, env=None):
             out["batch_1024"] = {"error": repr(e)}
 
     # ---- side legs: the other BASELINE.json configurations, same process, after the headline ----
-    if world == 1 and rank == 0 and not a.no_side and a.mask_keep == 0 and searcher is None and a.config == "c2" and n_dev == 1:
+    if full and world == 1 and rank == 0 and not a.no_side and a.mask_keep == 0 and searcher is None and a.config == "c2" \
+            and n_dev == 1:
         side = {}
         legs = [s.strip() for s in a.side.split(",") if s.strip()]
         t_side = time.perf_counter()
@@ -1463,7 +1518,7 @@ def run_bench(a, env=None):
         side["seconds"] = time.perf_counter() - t_side
         out["side"] = side
     # ---- N > 1: the weak-scaling point (C4's per-rank shape), every rank takes part ----
-    if world > 1 and searcher is not None and not a.no_side and a.c4_rows_per_rank > 0 and a.mask_keep == 0 \
+    if full and world > 1 and searcher is not None and not a.no_side and a.c4_rows_per_rank > 0 and a.mask_keep == 0 \
             and a.config == "c2":
         if hasattr(searcher, "close"):
             searcher.close()

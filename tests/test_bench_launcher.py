@@ -22,7 +22,7 @@ def _run(extra_env, *args, timeout=300):
 
 
 def test_plain_command_starts_its_own_ranks():
-    p = _run({}, "--gpus", "2")
+    p = _run({}, "--gpus", "2", "--full")
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout

@@ -16,16 +16,17 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
+import bench_check  # noqa: E402
 
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from fake_bench_env import FakeEnv  # noqa: E402
 
 
-def _args(*extra):
+def _args(*extra, full=True):
     return bench.parse(["--rows", "3000", "--dim", "32", "--k", "10", "--cpu-seconds", "0.2",
                         "--recall-queries", "150", "--recall-seconds", "5", "--c4-rows-per-rank", "300",
-                        "--c3-check", "200", "--c5-check", "40"] + list(extra))
+                        "--c3-check", "200", "--c5-check", "40"] + (["--full"] if full else []) + list(extra))
 
 
 DRIVER_ARGS = [(1, 0), (5, 0), (20, 5), (1000, 50)]
@@ -228,3 +229,59 @@ def test_in_process_multi_gpu_line(oracle_mod, n_dev):
     assert out["recall_at_k"] == 1.0 and out["ids_and_distances_bit_exact"] is True and out["cpu_baseline"]["cores"] == 1
     assert "exchange_timeline" not in out
     assert all(i.closed for i in env.made)
+
+
+@pytest.mark.parametrize("steps,warmup", DRIVER_ARGS)
+def test_plain_line_is_the_headline_alone(oracle_mod, steps, warmup):
+    """Without --full the run is set-up, W warm-up steps, ONE timed region of exactly --steps steps and the line: no
+    other search reaches the index, no oracle, no side leg; the headline's keys mean what they mean with --full."""
+    a = _args("--steps", str(steps), "--warmup", str(warmup), full=False)
+    env = FakeEnv(oracle_mod)
+    out = json.loads(bench.run_bench(a, env))
+    assert out["steps"] == steps and out["warmup"] == warmup and out["n_gpus"] == 1
+    assert out["value"] > 0 and abs(out["ms_per_step"] - 1e3 / out["value"]) < 1e-9 * out["ms_per_step"]
+    assert out["unit"] == "queries/s" and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert out["metric"] == "kNN queries/sec + recall@k, 1Mx768 f32 brute-force"
+    assert out["timed_regions"]["count"] == len(out["timed_regions"]["seconds"]) == 1
+    assert abs(out["timed_regions"]["seconds"][0] * 1e3 / steps - out["ms_per_step"]) < 1e-9 * out["ms_per_step"]
+    for key in ("side", "cpu_baseline", "recall_at_k", "latency_ms_one_at_a_time"):
+        assert key not in out, key
+    assert out["roofline"]["bound"] == "hbm" and out["roofline"]["kernel_us"] > 0
+    [idx] = env.made
+    assert idx.closed and idx.counters()["searches"] == warmup + steps
+    # --repeats still asks for several regions of --steps steps, the median one reported
+    out = json.loads(bench.run_bench(_args("--steps", str(steps), "--warmup", str(warmup), "--repeats", "3", full=False),
+                                     FakeEnv(oracle_mod)))
+    assert out["timed_regions"]["count"] == 3 and "side" not in out
+
+
+@pytest.mark.parametrize("extra", [[], ["--full", "--no-side"], ["--group", "0", "--inflight", "3"], ["--inflight", "1"],
+                                   ["--batch", "64", "--metric", "cosine"]])
+def test_dump_outputs_hold_the_last_timed_step(oracle_mod, tmp_path, extra):
+    """--dump-outputs DIR: the answer the timed path gave in its last step, float64, the same from run to run."""
+    steps, warmup = 7, 2
+    dumps = []
+    for rep in range(2):
+        d = tmp_path / str(rep)
+        a = _args("--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d), *extra, full=False)
+        out = json.loads(bench.run_bench(a, FakeEnv(oracle_mod)))
+        got = {n: np.load(d / (n + ".npy")) for n in ("ids", "distances", "count")}
+        assert all(x.dtype == np.float64 for x in got.values())
+        dumps.append(got)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    a = _args("--steps", str(steps), *extra, full=False)
+    metric = bench.METRICS[a.metric]
+    rows = FakeEnv(oracle_mod).corpus(a.rows, a.dim, metric)
+    if a.batch:  # one step = one call of --batch queries: its whole answer
+        nq = a.batch
+        first = ((out["steps"] - 1) % 2) * nq
+        qs = bench.make_queries(nq * 2, a.dim, metric, seed=20260615)[first:first + nq]
+    else:  # one step = one query: the last timed query's answer
+        pool = bench.make_queries(bench.query_pool_size(steps, warmup, a.recall_queries), a.dim, metric)
+        last = (warmup + out["timed_regions"]["count"] * steps - 1) % len(pool)
+        qs = pool[last:last + 1]
+    ids, dist, cnt = bench_check.oracle_answers(rows, qs, metric, a.k)
+    assert np.array_equal(dumps[0]["count"], cnt.astype(np.float64))
+    assert np.array_equal(dumps[0]["ids"], ids[:, :a.k].astype(np.float64).reshape(dumps[0]["ids"].shape))
+    assert np.array_equal(dumps[0]["distances"], dist[:, :a.k].reshape(dumps[0]["distances"].shape))

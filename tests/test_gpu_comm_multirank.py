@@ -39,7 +39,7 @@ def test_bench_gpus_2_plain_command(hip_lib):
     """Exactly what a driver without a launcher runs: two ranks share this box's GPU."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ranks-share-gpu", "--backend",
-                        "gloo", "--steps", "20", "--warmup", "5", "--rows", "200000", "--cpu-seconds", "3"],
+                        "gloo", "--steps", "20", "--warmup", "5", "--rows", "200000", "--cpu-seconds", "3", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -56,7 +56,8 @@ def test_bench_in_process_multi_gpu(hip_lib):
     --shards-share-gpu), host threads + copies + host merge, no ranks and no collective -- the same one-line contract."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--in-process", "--shards-share-gpu",
-                        "--steps", "20", "--warmup", "5", "--rows", "200000", "--cpu-seconds", "3", "--recall-queries", "100"],
+                        "--steps", "20", "--warmup", "5", "--rows", "200000", "--cpu-seconds", "3", "--recall-queries", "100",
+                        "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -77,7 +78,7 @@ def test_bench_under_torch_distributed_run(hip_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--fake-rccl", "--rows", "200000", "--c4-rows-per-rank", "50000", "--cpu-seconds", "3"]
+           "--fake-rccl", "--rows", "200000", "--c4-rows-per-rank", "50000", "--cpu-seconds", "3", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
