@@ -315,7 +315,11 @@ int32_t tsh_search(tsh_index *idx, const float *queries, int32_t nq, int32_t k,
  *   rows tombstoned later are dropped as always (the kernels check the live bitmap), deleted rows never come back
  * A handle belongs to the index it was made for (any handle kind: whole index, several devices, a shard) and must be
  * destroyed before it; destroy it only after every ticket submitted with it has been waited for.  Thread-safe: any
- * number of searches may share one handle.  Results are identical to the pointer form's. */
+ * number of searches may share one handle.  Results are identical to the pointer form's.
+ * A handle that outlives its index is ORPHANED, not dangling: tsh_index_destroy frees the device parts of every handle
+ * still made for it and detaches them; tsh_mask_kept then answers TSH_E_BAD_ARG, a search with it TSH_E_BAD_ARG (it
+ * belongs to no index), and tsh_mask_destroy only frees the handle itself.  The two destroys may come in either order,
+ * from any threads. */
 typedef struct tsh_mask tsh_mask;
 int32_t tsh_mask_create(tsh_index *idx, const uint8_t *bits, int64_t n_bytes, tsh_mask **out);
 int32_t tsh_mask_destroy(tsh_mask *mask);

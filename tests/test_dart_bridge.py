@@ -316,3 +316,15 @@ def test_hook_call_sites_name_real_reference_lines():
         assert cite in hook, cite
     assert "void clearCacheForTable" in span(1192, 1192) and "void clearCacheForIndex" in span(1198, 1198)
     assert "Future<void> dispose()" in span(1205, 1205)
+
+
+def test_bridge_refuses_a_disposed_mask():
+    """HipRowMask.dispose() leaves a NULL handle, which the library reads as "no filter": search and searchAsync must
+    return null (with the bridge's usual warning) before either passes mask._mask on."""
+    text = _strip_comments(open(BRIDGE).read())
+    for head, call in (("List<NghSearchResult>? search(", "_searchMasked("), ("searchAsync(", "_submitMasked(")):
+        start = text.index(head)
+        body = text[start:text.index(call, start)]
+        guard = re.search(r"if\s*\(\s*mask\s*!=\s*null\s*&&\s*mask\._mask\s*==\s*nullptr\s*\)\s*\{(.*?)\}", body, flags=re.S)
+        assert guard, "%s passes a disposed mask on" % head
+        assert "Logger.warn(" in guard.group(1) and re.search(r"return\s+null\s*;", guard.group(1)), head

@@ -228,3 +228,64 @@ def test_many_threads_share_one_handle(hip_lib, oracle_mod):
             assert not errs, errs
             for t in range(4):
                 assert _same(out[t], tuple(x[t * 6:(t + 1) * 6] for x in want))
+
+
+def test_a_closed_mask_is_refused_not_taken_for_no_filter(hip_lib):
+    """A closed handle is NULL to the library, which reads NULL as "no filter": search / submit refuse it (ValueError)
+    before any call reaches the library, and `kept` does not call into it."""
+    from tostore_amd import HipVectorIndex
+
+    rng = np.random.default_rng(21)
+    n, d, k = 5000, 32, 10
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    with HipVectorIndex(d, L2) as idx:
+        idx.append(0, rows)
+        m = idx.make_mask(_bits(rng.random(n) < 0.1))
+        m.close()
+        s0 = idx.counters()["searches"]
+        with pytest.raises(ValueError):
+            idx.search(rows[:2], k, None, m)
+        with pytest.raises(ValueError):
+            idx.submit(rows[0], k, m)
+        with pytest.raises(ValueError):
+            m.kept
+        assert idx.counters()["searches"] == s0
+        m.close()  # (twice: harmless)
+
+
+def test_a_mask_that_outlives_its_index(hip_lib):
+    """The index closed first: it closes its masks (Python), and the library orphans any handle still made for it --
+    tsh_mask_kept answers TSH_E_BAD_ARG instead of reading the freed index, tsh_mask_destroy frees the handle only."""
+    import ctypes
+
+    from tostore_amd import HipVectorIndex, _ffi
+
+    rng = np.random.default_rng(22)
+    n, d = 5000, 32
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    keep = rng.random(n) < 0.1
+    idx = HipVectorIndex(d, L2)
+    idx.append(0, rows)
+    m = idx.make_mask(_bits(keep))
+    assert m.kept == int(keep.sum())
+    idx.close()
+    with pytest.raises(ValueError):
+        m.kept
+    m.close()
+    # the same through the C ABI, for a caller that bypasses HipVectorIndex / HipMask
+    L = _ffi.lib()
+    h, mh = ctypes.c_void_p(), ctypes.c_void_p()
+    _ffi.check(L.tsh_index_create(d, L2, 0, 1, ctypes.byref(h)))
+    _ffi.check(L.tsh_index_append(h, 0, n, rows.ctypes.data_as(_ffi.p_f32)))
+    bits = _bits(keep)
+    _ffi.check(L.tsh_mask_create(h, bits.ctypes.data_as(_ffi.p_u8), bits.shape[0], ctypes.byref(mh)))
+    assert L.tsh_mask_kept(mh) == int(keep.sum())
+    assert L.tsh_index_destroy(h) == _ffi.TSH_OK
+    assert L.tsh_mask_kept(mh) == _ffi.TSH_E_BAD_ARG
+    assert L.tsh_mask_destroy(mh) == _ffi.TSH_OK
+    # ... and in the usual order nothing changed: the mask first, then its index
+    _ffi.check(L.tsh_index_create(d, L2, 0, 1, ctypes.byref(h)))
+    _ffi.check(L.tsh_index_append(h, 0, n, rows.ctypes.data_as(_ffi.p_f32)))
+    _ffi.check(L.tsh_mask_create(h, bits.ctypes.data_as(_ffi.p_u8), bits.shape[0], ctypes.byref(mh)))
+    assert L.tsh_mask_destroy(mh) == _ffi.TSH_OK
+    assert L.tsh_index_destroy(h) == _ffi.TSH_OK

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import weakref
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -39,7 +40,8 @@ class HipMask:
     ones that serve many queries in the reference: a WHERE's primary keys mapped through the pk -> nodeId tree
     (/root/reference/lib/src/core/vector_index_manager.dart:1223-1378) and the complement of the tombstones
     (/root/reference/lib/src/core/ngh_page.dart:105-108).  Rows appended after the mask was made are not kept; rows
-    deleted later are dropped as always.  Destroy before the index (close / context manager)."""
+    deleted later are dropped as always.  Destroy before the index (close / context manager); an index that is closed
+    first closes its masks, and a closed mask is refused by every search (ValueError), never taken for "no filter"."""
 
     def __init__(self, index: "HipVectorIndex", bits):
         bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
@@ -47,10 +49,17 @@ class HipMask:
         self.index = index
         _ffi.check(_ffi.lib().tsh_mask_create(index._h, bits.ctypes.data_as(_ffi.p_u8), bits.shape[0],
                                               ctypes.byref(self._h)))
+        index._live_masks().add(self)
+
+    def handle(self):
+        """The `tsh_mask*` to pass to the library; ValueError once the mask (or its index) was closed."""
+        if not self._h:
+            raise ValueError("the mask is closed (or its index was)")
+        return self._h
 
     @property
     def kept(self) -> int:
-        n = _ffi.lib().tsh_mask_kept(self._h)
+        n = _ffi.lib().tsh_mask_kept(self.handle())
         if n < 0:
             _ffi.check(int(n))
         return int(n)
@@ -116,8 +125,17 @@ class HipVectorIndex:
         """A device-resident row set for many searches (bit i of `bits`, LSB first, keeps GLOBAL row id i)."""
         return HipMask(self, bits)
 
+    def _live_masks(self) -> "weakref.WeakSet":
+        """The masks made for this index and not yet closed: close() closes them before it destroys the index."""
+        s = self.__dict__.get("_masks")
+        if s is None:
+            s = self._masks = weakref.WeakSet()
+        return s
+
     # -- lifetime -----------------------------------------------------------
     def close(self) -> None:
+        for m in list(self.__dict__.get("_masks", ())):
+            m.close()
         if self._h:
             _ffi.lib().tsh_index_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -225,7 +243,7 @@ class HipVectorIndex:
         cnt = np.zeros(nq, dtype=np.int32)
         thr = math.nan if distance_threshold is None else float(distance_threshold)
         if isinstance(row_mask, HipMask):  # a mask handle: resident on the device, nothing to prepare
-            _ffi.check(_ffi.lib().tsh_search_masked(self._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, row_mask._h,
+            _ffi.check(_ffi.lib().tsh_search_masked(self._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, row_mask.handle(),
                                                     ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
                                                     cnt.ctypes.data_as(_ffi.p_i32)))
             return ids[:, :kk], dist[:, :kk], cnt
@@ -242,7 +260,7 @@ class HipVectorIndex:
             raise ValueError(f"query must have {self.dim} elements")
         t = ctypes.c_int32(-1)
         if isinstance(row_mask, HipMask):
-            _ffi.check(_ffi.lib().tsh_search_submit_masked(self._h, q.ctypes.data_as(_ffi.p_f32), int(k), row_mask._h,
+            _ffi.check(_ffi.lib().tsh_search_submit_masked(self._h, q.ctypes.data_as(_ffi.p_f32), int(k), row_mask.handle(),
                                                            ctypes.byref(t)))
             return (t.value, int(k))
         row_mask, mp = self.mask_arg(row_mask)

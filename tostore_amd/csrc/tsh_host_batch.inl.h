@@ -433,8 +433,7 @@ int shard_search_batch(Shard *s, BatchCtx *b, const float *queries, int32_t nq, 
   if (mask.part) {
     kept = mask.part->kept;
   } else if (mask.bytes) {
-    slice_mask(s, mask.bytes, b->h_mask, n_tiles_all);
-    if (rows & 63) b->h_mask[n_tiles_all - 1] &= (1ull << (rows & 63)) - 1ull;  // (bits past the last row keep nothing)
+    slice_mask(s, mask.bytes, b->h_mask, n_tiles_all);  // (bits past the last row keep nothing: slice_mask clears them)
     kept = popcount_words(b->h_mask, (size_t)n_tiles_all);
   }
   // LISTED mode (round 6): a mask that keeps at most LISTED_MAX rows, a small part of the shard.  Scoring all rows and
@@ -1176,21 +1175,8 @@ int shard_search_batch(Shard *s, BatchCtx *b, const float *queries, int32_t nq, 
   return TSH_OK;
 }
 
-// rows a caller's mask keeps on this shard (the pointer form, counted for the cost model below: 125 KB at 1 M rows, ~5 us)
-int64_t mask_kept_rows(const Shard *s, const uint8_t *bytes) {
-  const int64_t lo = s->row_base, hi = s->row_base + s->rows;
-  if (hi <= lo) return 0;
-  int64_t n = 0, i = lo;
-  for (; i < hi && (i & 7); ++i) n += (bytes[i >> 3] >> (i & 7)) & 1;
-  const int64_t whole = (hi - i) / 64;
-  for (int64_t w = 0; w < whole; ++w) {
-    uint64_t v;
-    memcpy(&v, bytes + (i >> 3) + 8 * w, 8);
-    n += __builtin_popcountll(v);
-  }
-  for (i += 64 * whole; i < hi; ++i) n += (bytes[i >> 3] >> (i & 7)) & 1;
-  return n;
-}
+// rows a caller's mask keeps on this shard (the pointer form, counted for the cost model below: tsh_host_sync.h)
+int64_t mask_kept_rows(const Shard *s, const uint8_t *bytes) { return tsh::mask_kept_rows(s->row_base, s->rows, bytes); }
 
 // does a call of nq queries on this shard go to the matrix cores?  kept: rows a mask of the call keeps (-1: none / unknown)
 bool shard_takes_batch(const Shard *s, int32_t batch_min_nq, int32_t nq, int32_t k, int64_t kept = -1) {

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -382,6 +383,50 @@ class ShardWorkers {
   std::mutex owner_;
   std::vector<std::unique_ptr<Slot>> slots_;
 };
+
+// ---- a caller's row mask, one shard's part of it (tsh_lib.hip, tsh_host_batch.inl.h) ---------------------------
+// The caller's GLOBAL keep bitmap (bit i, LSB first, keeps row id i) sliced to the shard of `rows` rows that starts at
+// row id `row_base`: word t bit r of out_words (n_words >= ceil(rows / 64) of them) is local row 64 t + r.  Bits at or
+// past `rows` are cleared -- a bitmap sized for capacity, or the global one every rank is handed, has them set -- so the
+// words' popcount is the mask's kept rows on the shard and their list names rows of the shard only.  Reads the bytes
+// [row_base / 8, (row_base + rows - 1) / 8] of `mask` and nothing else.
+inline void slice_mask(int64_t row_base, int64_t rows, const uint8_t *mask, uint64_t *out_words, int64_t n_words) {
+  memset(out_words, 0, (size_t)n_words * 8);
+  if (rows <= 0) return;
+  uint8_t *ob = reinterpret_cast<uint8_t *>(out_words);
+  const int64_t nbytes = (rows + 7) / 8;
+  if ((row_base & 7) == 0) {
+    memcpy(ob, mask + row_base / 8, (size_t)nbytes);
+  } else {
+    const int sh = (int)(row_base & 7);
+    const uint8_t *src = mask + row_base / 8;
+    const int64_t src_last = (row_base + rows - 1) / 8 - row_base / 8;  // last valid src byte index
+    for (int64_t i = 0; i < nbytes; ++i) {
+      const unsigned lo = src[i] >> sh;
+      const unsigned hi = (i + 1 <= src_last) ? (unsigned)(src[i + 1] << (8 - sh)) : 0u;
+      ob[i] = (uint8_t)(lo | hi);
+    }
+  }
+  // (the whole bytes above carry the bits of the rows past the shard's last one: its neighbours', or the capacity's)
+  if (rows & 63) out_words[(rows - 1) / 64] &= (1ull << (rows & 63)) - 1ull;
+}
+
+// rows a caller's mask keeps on the shard [row_base, row_base + rows) -- the pointer form, counted for the cost model
+// without a slice (tsh_host_batch.inl.h shard_search_any: 125 KB at 1 M rows, ~5 us)
+inline int64_t mask_kept_rows(int64_t row_base, int64_t rows, const uint8_t *bytes) {
+  const int64_t lo = row_base, hi = row_base + rows;
+  if (hi <= lo) return 0;
+  int64_t n = 0, i = lo;
+  for (; i < hi && (i & 7); ++i) n += (bytes[i >> 3] >> (i & 7)) & 1;
+  const int64_t whole = (hi - i) / 64;
+  for (int64_t w = 0; w < whole; ++w) {
+    uint64_t v;
+    memcpy(&v, bytes + (i >> 3) + 8 * w, 8);
+    n += __builtin_popcountll(v);
+  }
+  for (i += 64 * whole; i < hi; ++i) n += (bytes[i >> 3] >> (i & 7)) & 1;
+  return n;
+}
 
 // ---- a row mask as a list of row ids (tsh_lib.hip build_row_list) ----------------------------------------------
 // The set bits of a mask as ascending positions -> out (room for their count + 4), their number.  A lone masked query

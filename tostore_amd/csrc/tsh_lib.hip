@@ -903,24 +903,9 @@ void fill_scan_args(const Shard *s, const Ctx *c, bool masked, bool user_mask, S
   a->list = nullptr;
 }
 
-// slice the caller's GLOBAL keep mask into this shard's tile words
-void slice_mask(const Shard *s, const uint8_t *mask, uint64_t *out_words, int64_t n_words) {
-  int64_t rows = s->rows;
-  memset(out_words, 0, (size_t)n_words * 8);
-  uint8_t *ob = reinterpret_cast<uint8_t *>(out_words);
-  int64_t nbytes = (rows + 7) / 8;
-  if ((s->row_base & 7) == 0) {
-    memcpy(ob, mask + s->row_base / 8, (size_t)nbytes);
-  } else {
-    int sh = (int)(s->row_base & 7);
-    const uint8_t *src = mask + s->row_base / 8;
-    int64_t src_last = (s->row_base + rows - 1) / 8 - s->row_base / 8;  // last valid src byte index
-    for (int64_t i = 0; i < nbytes; ++i) {
-      unsigned lo = src[i] >> sh;
-      unsigned hi = (i + 1 <= src_last) ? (unsigned)(src[i + 1] << (8 - sh)) : 0u;
-      ob[i] = (uint8_t)(lo | hi);
-    }
-  }
+// slice the caller's GLOBAL keep mask into this shard's tile words (tsh_host_sync.h: no bit past the last row is kept)
+inline void slice_mask(const Shard *s, const uint8_t *mask, uint64_t *out_words, int64_t n_words) {
+  tsh::slice_mask(s->row_base, s->rows, mask, out_words, n_words);
 }
 
 // One query in flight on one context.  Its three kernels (scan, select,
@@ -1069,7 +1054,8 @@ bool row_list_pays(const Shard *s, int64_t rows_kept, int32_t k, int32_t entries
 bool build_row_list(const Shard *s, const uint64_t *mask_words, int32_t n_tiles, int64_t rows_kept, int32_t k, int32_t entries,
                     std::vector<uint32_t> *ids) {
   if (!mask_words || !row_list_pays(s, rows_kept, k, entries)) return false;
-  // (bits past the shard's last row cannot be set: slice_mask clears them; rows_kept is their exact count)
+  // (mask_words come from slice_mask, which clears every bit at or past the shard's last row: the list names rows of
+  // the shard only, and rows_kept -- their popcount -- is its exact length)
   ids->resize((size_t)round_up(rows_kept, 64) + 8);
   const size_t got = list_mask_bits(mask_words, n_tiles, rows_kept, ids->data());
   if (got == 0) return false;
@@ -1788,6 +1774,7 @@ struct tsh_index {
   std::vector<std::unique_ptr<Ticket>> tickets;
   std::atomic<int> tickets_open{0};  // submitted, not yet waited for: each holds one context per shard
   std::atomic<int32_t> batch_min_nq{1};  // 0 never, 1 by estimated cost, n >= 2: from n queries per call on
+  std::vector<tsh_mask *> masks;  // live mask handles made for this index (guarded by g_mask_mu): orphaned by destroy
   std::unique_ptr<ShardWorkers> workers;  // multi-device handles: one persistent host thread per further shard
   // result-block buffers of multi-query calls, kept between calls: a fresh 6 MB allocation per call spends
   // ~0.3 ms in page faults when it is first written
@@ -1921,13 +1908,18 @@ int index_append(tsh_index *idx, int64_t first, int64_t n, const float *rows, bo
 
 // ---- mask handles ---------------------------------------------------------------------------------------------
 struct tsh_mask {
-  tsh_index *idx = nullptr;
+  tsh_index *idx = nullptr;   // nullptr: orphaned -- its index was destroyed first (parts freed then)
   std::vector<uint8_t> bits;  // the caller's GLOBAL bitmap (its own copy; zero-extended as the index grows)
   std::mutex mu;              // builds / rebuilds of the parts
   std::vector<std::unique_ptr<MaskPart>> parts;  // one per shard of the index
 };
 
 namespace {
+
+// Settles a mask's destroy against its index's (either may come first, from any thread): index -> masks lists, every
+// mask's idx, and the parts' device buffers while an index frees them.  Held by tsh_mask_kept too, so an index cannot
+// be destroyed under a count.
+std::mutex g_mask_mu;
 
 void mask_part_free(MaskPart *p) {
   if (hipSetDevice(p->device) != hipSuccess) return;
@@ -2112,6 +2104,15 @@ int32_t tsh_index_create_shard(int32_t dim, int32_t metric, int64_t capacity_row
 
 int32_t tsh_index_destroy(tsh_index *idx) {
   if (!idx) return TSH_OK;
+  {
+    // mask handles still alive are orphaned: their device parts go now, the structs stay for tsh_mask_destroy
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    for (tsh_mask *m : idx->masks) {
+      for (auto &p : m->parts) mask_part_free(p.get());
+      m->idx = nullptr;
+    }
+    idx->masks.clear();
+  }
   idx->workers.reset();  // joins the shard threads
   for (auto &s : idx->shards) {
     std::unique_lock<RwLock> xl(s->mu);
@@ -2366,20 +2367,32 @@ int32_t tsh_mask_create(tsh_index *idx, const uint8_t *bits, int64_t n_bytes, ts
     g_err = keep;
     return rc;
   }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->masks.push_back(m.get());
+  }
   *out = m.release();
   return TSH_OK;
 }
 
 int32_t tsh_mask_destroy(tsh_mask *mask) {
   if (!mask) return TSH_OK;
-  for (auto &p : mask->parts) mask_part_free(p.get());
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    if (tsh_index *idx = mask->idx) {  // (an orphan's parts went with its index)
+      idx->masks.erase(std::remove(idx->masks.begin(), idx->masks.end(), mask), idx->masks.end());
+      for (auto &p : mask->parts) mask_part_free(p.get());
+    }
+  }
   delete mask;
   return TSH_OK;
 }
 
 int64_t tsh_mask_kept(tsh_mask *mask) {
   if (!mask) return set_err(TSH_E_BAD_ARG, "mask is NULL");
+  std::lock_guard<std::mutex> lk(g_mask_mu);
   tsh_index *idx = mask->idx;
+  if (!idx) return set_err(TSH_E_BAD_ARG, "the mask's index was destroyed");
   int64_t kept = 0;
   for (size_t g = 0; g < idx->shards.size(); ++g) {
     Shard *s = idx->shards[g].get();

@@ -628,6 +628,11 @@ final class HipVectorBackend {
   /// the caller falls through to the original graph search.
   List<NghSearchResult>? search(Float32List query, int topK,
       {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) {
+    // a disposed mask is NULL to the library, which reads NULL as "no filter": refuse it instead
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('search with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
     if (topK <= 0 || size == 0) return const [];
     final q = calloc<Float>(dimensions);
     final ids = calloc<Int64>(topK);
@@ -695,6 +700,11 @@ final class HipVectorBackend {
   /// synchronous path or the Dart graph search).
   Future<List<NghSearchResult>?> searchAsync(Float32List query, int topK,
       {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) async {
+    // (as in [search]: a disposed mask must not become "no filter")
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchAsync with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
     if (topK <= 0 || size == 0) return const [];
     final q = calloc<Float>(dimensions);
     final ticket = calloc<Int32>();
@@ -1008,7 +1018,9 @@ final class HipShardComm {
 /// (vector_index_manager.dart:1223-1378) -- or the complement of a tombstone set (ngh_page.dart:105-108),
 /// kept for as many queries as it serves.  Rows appended after it was made are not kept; rows deleted
 /// later are dropped by the kernels as always.  Dispose it before its backend, and only after every
-/// [HipVectorBackend.searchAsync] that used it has completed.
+/// [HipVectorBackend.searchAsync] that used it has completed.  A disposed mask is refused by [HipVectorBackend.search]
+/// and [HipVectorBackend.searchAsync] (null, with a warning); one whose backend was disposed first is orphaned by the
+/// library ([kept] answers -1) and still safe to dispose.
 final class HipRowMask {
   Pointer<Void> _mask;
 
