@@ -45,7 +45,8 @@ extern "C" {
  * 5: mask handles (tsh_mask_create / _destroy / _kept, tsh_search_masked, tsh_search_submit_masked): a WHERE row set
  *    that lives on the device across queries; tsh_index_open_ngh_shard (a rank cold-starts its own row range);
  *    tsh_ngh_info grew (row_base, row_end); tsh_comm_timeline's sampled fields are scaled by exchanges / timed
- *    exchanges instead of a constant. */
+ *    exchanges instead of a constant.
+ *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys. */
 
 /* status codes */
 #define TSH_OK 0
@@ -521,6 +522,15 @@ int32_t tsh_probe_batch_keys(tsh_index *idx, const float *queries, int32_t nq, i
  * out_beta2[q] = 2 * 1.0001 * beta_q: 2 |key - exact| <= out_alpha2[q] |v| + out_beta2[q] for every row v.  Key kernels
  * and metrics with one band for all rows report alpha = 0 and out_beta2 = out_delta2. */
 int32_t tsh_probe_batch_row_band(tsh_index *idx, int32_t nq, float *out_alpha2, float *out_beta2);
+/* tsh_probe_scan_f16_keys: the fp16 scan's (TSH_OPT_SCAN_F16) stored key of every row -- the UPPER side key + w of the
+ * row's band -- and that band w: |out_keys[i] - out_w[i] - exact_i| <= out_w[i] with exact = |v|^2 - 2 q.v (L2: the
+ * common |q|^2 is left out), -q.v, -q.v / |v|.  An error when the index or the query is not eligible for that scan.
+ * tsh_probe_scan_keys keeps probing the f32 kernel. */
+int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_keys, float *out_w);
+/* The fp16 scan's own counters (tsh_counters keeps its layout), summed over the shards: out[0] = scans launched over
+ * the fp16 copy, out[1] = of those, queries whose candidate list overflowed and that were redone through the f32 scan,
+ * out[2] = rows converted into the copy so far, out[3] = bytes of the copy resident now (part of bytes_resident). */
+int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out);
 
 /* Tuning knobs (no reference counterpart).  TSH_OPT_BATCH_MIN_NQ: when tsh_search /
  * tsh_search_shard answer a multi-query call on the batched matrix-core path:
@@ -583,6 +593,16 @@ int32_t tsh_probe_batch_row_band(tsh_index *idx, int32_t nq, float *out_alpha2, 
  * them down); 0 = in row order.  Results are identical either way; the copy is rebuilt by the next batched search
  * after a change. */
 #define TSH_OPT_BATCH_GROUP 7
+/* TSH_OPT_SCAN_F16 (default 1): whether a dense single-query scan -- no caller mask, no tombstones -- reads an fp16
+ * copy of the rows instead of the rows themselves: half the HBM bytes per query.  0 = never; 1 = auto: shards whose row
+ * store is larger than the 256 MiB Infinity Cache (below that a scan is not bandwidth-bound); 2 = every eligible
+ * scan whatever the size (tests, A/B runs).  Eligible: rows of at least 256 elements, a multiple of 8, index and
+ * query inside the error model.  The copy (2 B per element, scaled by a power of two) is built by the first such
+ * search and kept current lazily: appended rows are converted in front of the next scan; an overwrite, a
+ * reallocation or a change of the scale rebuild it.  A device too full for it scans f32.  Keys carry a per-row band
+ * alpha |v| + beta; a query whose candidate list overflows on them is redone through the f32 scan, and two such queries
+ * in a row move the index's next 256 eligible scans to f32.  Results are identical either way. */
+#define TSH_OPT_SCAN_F16 8
 /* TSH_OPT_TEST_HOOKS (process-wide; idx is ignored and may be NULL): value TSH_TEST_HOOKS_MAGIC switches the
  * library's TEST hooks on, 0 off.  Only then does it read the environment variables that change what it loads or make
  * it fail on purpose -- TSH_RCCL_LIB (a stand-in for librccl: tests/fake_rccl), TSH_TEST_FAIL_ALLOC_OVER (device

@@ -290,6 +290,26 @@ class HipVectorIndex:
         queries per call on.  Results are identical."""
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_BATCH_MIN_NQ, int(nq)))
 
+    def set_scan_f16(self, mode: int) -> None:
+        """Dense single-query scans over the fp16 copy of the rows (half the HBM bytes): 0 never, 1 auto (default: shards
+        whose row store is larger than 256 MiB), 2 every eligible scan whatever the size.  Results are identical."""
+        _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_F16, int(mode)))
+
+    def scan_f16_stats(self) -> dict:
+        """The fp16 scan's counters: scans launched, queries redone through the f32 scan, rows converted, copy bytes."""
+        out = (ctypes.c_int64 * 4)()
+        _ffi.check(_ffi.lib().tsh_scan_f16_stats(self._h, out))
+        return {"scans": out[0], "redone": out[1], "rows_converted": out[2], "copy_bytes": out[3]}
+
+    def probe_scan_f16_keys(self, query):
+        """(stored upper-side key of every row from the fp16 scan kernel, every row's band w): tests of the error model."""
+        q = _f32c(query).reshape(-1)
+        keys = np.empty(self.size - self.row_base, dtype=np.float32)
+        w = np.empty(self.size - self.row_base, dtype=np.float32)
+        _ffi.check(_ffi.lib().tsh_probe_scan_f16_keys(self._h, q.ctypes.data_as(_ffi.p_f32), keys.ctypes.data_as(_ffi.p_f32),
+                                                      w.ctypes.data_as(_ffi.p_f32)))
+        return keys, w
+
     def set_exact_scan_rows(self, rows: int) -> None:
         """Single-query searches with at most `rows` rows to look at (a selective mask's kept rows, a small index) take
         the exact sums of all of them and select among the exact distances (two dispatches, no f32 pre-filter):

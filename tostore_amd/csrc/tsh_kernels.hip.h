@@ -124,6 +124,13 @@ struct ScanArgs {
   int32_t n_tiles;        // ceil(n/64); list scans: ceil(list entries / 64) -- keys / gmin are in LIST order then
   const uint32_t *list;   // list scans (scan_list_kernel): local row ids of the rows to scan, ascending, padded with
                           // 0xFFFFFFFF to a multiple of 64; NULL otherwise
+  // scan_f16_kernel only (zero otherwise): the fp16 copy of the rows (n x ld halves, row-major, elements scaled by
+  // 1 / inv_scale, a power of two), |row|^2 per row (L2 / inner product), and this query's per-row band
+  // w_i = w_alpha * |row_i| + w_beta (scan_f16_w): the kernel stores the UPPER side key + w_i
+  const void *rows16;
+  const float *sqnorm;
+  float inv_scale, w_alpha, w_beta;
+  int32_t pad_;
 };
 
 // Kernel parameter block: the scan arguments plus up to 960 query floats inline,
@@ -311,6 +318,157 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_kernel(ScanArgsQ aq) {
     uint32_t m = wave_min_u32(key);
     if (lane == 0) a.gmin[t] = m;
   }
+}
+
+// ---------------------------------------------------------------------------
+// K1 over the fp16 copy of the rows (dense, unmasked, all-live scans of big shards): half the HBM bytes per query.
+// scan_kernel's structure -- one wave per 64-row tile, two register buffers with the next group in flight, the
+// same fences and butterfly -- with 8-byte loads per lane: a lane holds the same four ELEMENTS of a chunk as in the
+// f32 kernel (chunk = 256 elements = 512 contiguous bytes per wave instruction), so NCH, FULL, the query registers
+// and the tail handling are the f32 kernel's.  The buffers hold the raw halves (two VGPRs per load); they are widened
+// where they are consumed, behind the fence, so a load never waits for its own conversion.
+// All metrics are dot products here: acc = sum q_j * float(h_ij), h = fp16(S * v), in f32 FMAs; then
+//   L2      key = |v_i|^2 - 2 acc / S     (the common |q|^2 is left out: it orders nothing)
+//   IP      key = -acc / S
+//   cosine  key = -(acc / S) / |v_i|
+// and what is STORED is the upper side key + w_i of the band |key - exact| <= w_i = w_alpha |v_i| + w_beta that the
+// host proved for this query (tsh_scan_f16_band.h).  select_body then runs on upper sides.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float scan_f16_w(float alpha, float beta, float sqnorm) {
+  return __builtin_fmaf(alpha, __builtin_sqrtf(sqnorm), beta);
+}
+
+template <int NCH, int METRIC, bool FULL, int R, int WAVES, int MINW>
+__global__ void __launch_bounds__(WAVES * 64, MINW) scan_f16_kernel(ScanArgsQ aq) {
+  static_assert(R == 2 || R == 4, "R must give an even number of groups per 8-row batch");
+  const ScanArgs &a = aq.a;
+  const float *qsrc = a.query;
+  if (!qsrc) {
+    typedef const char __attribute__((address_space(4))) * karg_ptr;
+    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
+  }
+  constexpr int G = 8 / R;
+  const _Float16 *rows16 = reinterpret_cast<const _Float16 *>(a.rows16);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wpb = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
+  const int stride = gridDim.x * wpb;
+  uint32_t vmask = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) vmask |= (FULL || c * 64 + lane < a.d4) ? (1u << c) : 0u;
+  auto has = [&](int c) { return FULL || ((vmask >> c) & 1u) != 0u; };
+  auto off = [&](int c) { return has(c) ? c * 256 : -4 * lane; };
+  uint32_t loff[NCH];  // !FULL: this lane's element offset into a row, per chunk (lanes past the row's end: its start)
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) loff[c] = has(c) ? (uint32_t)(4 * lane + c * 256) : 0u;
+
+  f32x4 q[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    q[c] = *reinterpret_cast<const f32x4 *>(qsrc + 4 * lane + off(c));
+    if (!has(c)) q[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (a.query_out && blockIdx.x == 0 && wave == 0) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (has(c))
+        *reinterpret_cast<f32x4 *>(a.query_out + 4 * lane + c * 256) = q[c];
+  }
+
+  for (int t = (int)blockIdx.x * wpb + wave; t < a.n_tiles; t += stride) {
+    const _Float16 *tbase = rows16 + (int64_t)t * 64 * a.ld + 4 * lane;
+    f16x4 v[2][R][NCH];
+    int next_dense = 0;
+    auto load_group = [&](int buf) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const int r = next_dense++;
+        if (FULL) {
+          const _Float16 *rp = tbase + (int64_t)r * a.ld;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4 *>(rp + off(c)));
+        } else {
+          // (a scalar row base + one 32-bit lane offset per chunk: see scan_kernel)
+          const uint64_t rbi = (uint64_t)(rows16 + ((int64_t)t * 64 + r) * a.ld);
+          const _Float16 *rb = reinterpret_cast<const _Float16 *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rbi >> 32)) << 32) |
+                                                                  (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rbi));
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4 *>(rb + loff[c]));
+        }
+      }
+    };
+
+    float val = 0.f;
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the previous tile's stores (see scan_kernel)
+    load_group(0);
+    auto batch = [&](int b, auto LAST) {
+      float acc[8];
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        if (!(decltype(LAST)::value && k == G - 1)) load_group((k + 1) & 1);
+        TSH_FENCE();
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          float s = 0.f;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+            if (has(c)) s = accum4<METRIC_IP>(s, q[c], __builtin_convertvector(v[k & 1][j][c], f32x4));
+          asm volatile("" : "+v"(s)::"memory");
+          acc[k * R + j] = s;
+        }
+        TSH_FENCE();
+      }
+      float o = treduce8<0>(acc, lane);
+      o += __shfl_xor(o, 8);
+      o += __shfl_xor(o, 16);
+      o += __shfl_xor(o, 32);
+      if ((lane >> 3) == b) val = o;
+    };
+#pragma nounroll
+    for (int b = 0; b < 7; ++b) batch(b, std::false_type{});
+    batch(7, std::true_type{});
+
+    const int64_t row = (int64_t)t * 64 + lane;
+    const bool alive = row < a.n;
+    const float dot = val * a.inv_scale;
+    float x, w;
+    if (METRIC == METRIC_COS) {
+      const float inv = alive ? a.inv_norm[row] : 0.f;
+      x = -(dot * inv);
+      w = a.w_beta;
+    } else {
+      const float sq = alive ? a.sqnorm[row] : 0.f;
+      x = METRIC == METRIC_L2 ? __builtin_fmaf(-2.f, dot, sq) : -dot;
+      w = scan_f16_w(a.w_alpha, a.w_beta, sq);
+    }
+    const uint32_t key = alive ? f2key(x + w) : KEY_DEAD;
+    a.keys[row] = key;
+    const uint32_t m = wave_min_u32(key);
+    if (lane == 0) a.gmin[t] = m;
+  }
+}
+
+// rows [r0, r1) of the f32 store -> the fp16 copy, scaled by `scale` (a power of two: exact), round to nearest even.
+// Elementwise over the padded rows (ld is a multiple of 4): one 16-byte load and one 8-byte store per thread and step.
+static __global__ void __launch_bounds__(256) rows16_convert_kernel(const float *rows, void *rows16, int64_t ld, int64_t r0,
+                                                                    int64_t r1, float scale) {
+  const int64_t e0 = r0 * ld / 4, e1 = r1 * ld / 4;  // in groups of four elements
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  f16x4 *dst = reinterpret_cast<f16x4 *>(rows16);
+  for (int64_t i = e0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e1; i += step) {
+    const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(rows) + i);
+    const f32x4 y = x * scale;
+    dst[i] = __builtin_convertvector(y, f16x4);
+  }
+}
+
+// every row's band (tsh_probe_scan_f16_keys): what scan_f16_kernel added to its key
+static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqnorm, int64_t n, float alpha, float beta, float *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = sqnorm ? scan_f16_w(alpha, beta, sqnorm[i]) : beta;
 }
 
 // K1 for SELECTIVE row masks (a WHERE clause that keeps a few percent of the rows; config C5): the host compacts the
@@ -549,6 +707,11 @@ struct SelectArgs {
   int64_t shard_rows;
   const uint32_t *list;  // list scans: keys / gmin are in list order; candidate rows = list[position]
   uint32_t tag;          // generation of the block (BlockHeader.pad[1]): 0, or what a sharded call's exchange expects
+  // fp16 scans of L2 / inner-product shards (NULL otherwise: nothing below is read): keys[] hold UPPER sides
+  // key_i + w_i of a per-row band w_i = w_alpha * sqrt(w_sq[i]) + w_beta.  The band above (delta_abs = 2 w_max) only
+  // picks the tiles; a row is emitted iff its LOWER side key_i - w_i = keys[i] - 2 w_i is at or below the bound
+  const float *w_sq;
+  float w_alpha, w_beta;
 };
 
 constexpr int SEL_THREADS = 1024;   // one whole CU; tile minima stay in registers
@@ -853,7 +1016,10 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
   const bool over = nt > SEL_LIST_CAP;
   constexpr int NW = SEL_THREADS / 64;
   // (e) four tiles per wave per round so their (L2-resident) key loads overlap
-  auto emit = [&](uint32_t bnd) {
+  // (tk: the bound the band was widened FROM -- the rows' own bands are applied against it)
+  auto emit = [&](uint32_t bnd, uint32_t tk) {
+    const bool per_row = a.w_sq != nullptr && bnd < KEY_NAN && tk < KEY_NAN;
+    const double tk_f = per_row ? (double)key2f(tk) : 0.0;
     for (uint32_t j0 = wave * 4; j0 < nt; j0 += NW * 4) {
       uint32_t tile[4], key[4];
 #pragma unroll
@@ -864,6 +1030,10 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         bool pass = key[u] <= bnd;
+        if (per_row && pass) {  // (no list on this path: the tile's rows are rows tile * 64 + lane)
+          const double w = (double)scan_f16_w(a.w_alpha, a.w_beta, a.w_sq[(int64_t)tile[u] * 64 + lane]) * (1.0 + 9.5367431640625e-07);
+          pass = (double)key2f(key[u]) - 2.0 * w <= tk_f;
+        }
         uint64_t bm = __ballot(pass);
         if (bm) {
           uint32_t base = 0;
@@ -877,7 +1047,7 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
       }
     }
   };
-  if (!over) emit(band);
+  if (!over) emit(band, tau);
   __syncthreads();
   uint32_t tau_out = tau, band_out = band;
   const uint32_t first_count = s_cand;
@@ -943,7 +1113,7 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
     }
     tau_out = X;
     band_out = band_of(X, a.eps_rel, a.delta_abs);
-    emit(band_out);
+    emit(band_out, X);
     __syncthreads();
   }
   if (tid == 0) {

@@ -39,6 +39,7 @@
 #include "tsh_launch.h"
 #include "tsh_mask.hip.h"
 #include "tsh_pq.hip.h"
+#include "tsh_scan_f16_band.h"
 
 using namespace tsh;
 
@@ -454,6 +455,21 @@ struct Shard {
   int hub_n = 0, hub_exp = 0, hub_chunks = 0;
   int64_t hub_bytes = 0;
 
+  // The fp16 copy of the rows that big shards' dense single-query scans read (scan_f16_kernel): row-major, ld halves per
+  // row, elements scaled by 2^rows16_exp.  Kept current LAZILY by rows16_ensure, where a scan is enqueued: rows
+  // [0, rows16_valid) are converted; appends past the watermark are converted in front of the next scan; an overwrite of
+  // a stored row, a reallocation of the row store or another scale reset it to 0.  Tombstones do not touch it (a
+  // tombstoned shard scans f32).  Guarded by rows16_mu under a shared s->mu; appends change it under the exclusive lock.
+  void *d_rows16 = nullptr;
+  int64_t rows16_cap = 0, rows16_valid = 0, rows16_bytes = 0;
+  int rows16_exp = 0;
+  bool rows16_denied = false;  // the copy did not fit on the device: f32 scans until the row store is reallocated
+  std::mutex rows16_mu;
+  int scan_f16 = 1;  // TSH_OPT_SCAN_F16: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible dense scan
+  std::atomic<int64_t> c_f16_scans{0}, c_f16_redone{0}, c_f16_converted{0};
+  std::atomic<int> scan_f16_strikes{0};  // fp16 scans in a row whose candidate list overflowed
+  std::atomic<int> scan_f16_denied{0};   // eligible scans left that go straight to f32 (two overflows in a row: 256)
+
   bool safe_mode() const {
     if (nonfinite_rows) return true;
     if (max_abs > BIG_ABS) return true;
@@ -633,6 +649,14 @@ int shard_reserve(Shard *s, int64_t want_rows) {
   if (s->d_inv_norm) hipFree(s->d_inv_norm);
   if (s->d_sqnorm) hipFree(s->d_sqnorm);
   if (s->d_live) hipFree(s->d_live);
+  if (s->d_rows16) {  // the copy follows the row store's capacity: built again by the next eligible scan
+    hipFree(s->d_rows16);
+    s->d_rows16 = nullptr;
+    s->bytes -= s->rows16_bytes;
+    s->rows16_bytes = 0;
+  }
+  s->rows16_cap = s->rows16_valid = 0;
+  s->rows16_denied = false;
   s->d_rows = nrows;
   s->d_inv_norm = ninv;
   s->d_sqnorm = nsq;
@@ -729,6 +753,7 @@ int shard_append(Shard *s, int64_t first, int64_t n, const float *src, bool src_
   if (first > s->rows) s->all_live = false;  // gap of absent rows
   if (first + n > s->rows) s->rows = first + n;
   s->split_valid = std::min(s->split_valid, first);  // overwritten / new rows need re-splitting
+  if (first < s->rows16_valid) s->rows16_valid = 0;  // a stored row overwritten: the fp16 copy is rebuilt
   if (first < s->hub_rows_built) s->hub_rows_built = -1;  // (an overwritten row may be a hub row: its copy is stale)
   return TSH_OK;
 }
@@ -901,6 +926,10 @@ void fill_scan_args(const Shard *s, const Ctx *c, bool masked, bool user_mask, S
   a->d4 = (int32_t)(s->ld / 4);
   a->n_tiles = (int32_t)((s->rows + 63) / 64);
   a->list = nullptr;
+  a->rows16 = nullptr;
+  a->sqnorm = nullptr;
+  a->inv_scale = a->w_alpha = a->w_beta = 0.f;
+  a->pad_ = 0;
 }
 
 // slice the caller's GLOBAL keep mask into this shard's tile words (tsh_host_sync.h: no bit past the last row is kept)
@@ -933,6 +962,9 @@ struct Job {
                                 // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
                                 // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
                                 // redoing the group with larger blocks, not ahead
+  bool f16 = false;        // scanned over the fp16 copy (scan_f16_kernel): a list overflow is redone through the f32 scan,
+  std::vector<float> q_f16;  // from this copy of the query, with this tag
+  uint32_t tag = 0;
   hipStream_t last_stream = nullptr;  // where the job's last kernel was enqueued (ev_done rides on it)
   uint64_t enq_seq = 0;               // ... and its place in the device's enqueue order (DeviceStreams::enq_counter)
   std::vector<uint32_t> quar_sel;  // entries of c->h_quar that belong to this query's candidates
@@ -1125,10 +1157,84 @@ void launch_exact_scan(const ExactArgsQ &xa, int metric, hipStream_t st, const L
 #undef TSH_EXACT_LAUNCH
 }
 
+// ---- the fp16 scan's route (TSH_OPT_SCAN_F16) ---------------------------------------------------------------------
+inline bool alloc_fault(int64_t bytes);      // tsh_host_batch.inl.h
+inline bool device_has_room(int64_t bytes);
+constexpr int64_t SCAN_F16_MIN_BYTES = 256ll << 20;  // the Infinity Cache: a row store below it is not HBM-bound
+constexpr int SCAN_F16_DENIED_SCANS = 256;
+
+// Could a dense, unmasked scan of this shard read the fp16 copy?  (the shard's side of the decision: caller holds s->mu)
+bool scan_f16_applies(const Shard *s, int *v_exp) {
+  if (s->scan_f16 == 0 || !s->all_live || s->rows16_denied || s->safe_mode()) return false;
+  if (!scan_f16_supported(s->nch, s->dim)) return false;
+  if (s->scan_f16 == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
+  if (s->metric == TSH_METRIC_COSINE && !(s->min_norm > 0.f)) return false;  // (a zero row: no uniform cosine band)
+  return scan_f16_exp(s->max_abs, v_exp);
+}
+
+// Brings the fp16 copy up to the shard's rows: allocation on first use, conversion of the rows past the watermark (all
+// of them after a reset) on `st`, waited for -- a scan on any stream may follow.  false: the copy does not fit on the
+// device; the shard scans f32 from now on (rows16_denied) instead of asking again with every query.
+bool rows16_ensure(Shard *s, hipStream_t st, int v_exp) {
+  std::lock_guard<std::mutex> lk(s->rows16_mu);
+  if (s->rows16_denied) return false;
+  if (s->d_rows16 && s->rows16_cap == s->cap && s->rows16_exp == v_exp && s->rows16_valid == s->rows) return true;
+  if (hipSetDevice(s->device) != hipSuccess) return false;
+  if (!s->d_rows16 || s->rows16_cap != s->cap) {
+    if (s->d_rows16) {
+      hipFree(s->d_rows16);
+      s->d_rows16 = nullptr;
+      s->bytes -= s->rows16_bytes;
+      s->rows16_bytes = 0;
+    }
+    s->rows16_cap = s->rows16_valid = 0;
+    const int64_t bytes = s->cap * s->ld * 2;
+    if (alloc_fault(bytes) || !device_has_room(bytes) || hipMalloc(&s->d_rows16, (size_t)bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      s->d_rows16 = nullptr;
+      s->rows16_denied = true;
+      return false;
+    }
+    s->rows16_cap = s->cap;
+    s->rows16_bytes = bytes;
+    s->bytes += bytes;
+  }
+  if (s->rows16_exp != v_exp) s->rows16_valid = 0;  // another scale: every row again
+  s->rows16_exp = v_exp;
+  // whole tiles: the scan reads the last tile's rows past the shard's end (zeros in the f32 store) and drops them
+  const int64_t r0 = s->rows16_valid, r1 = std::min(round_up(s->rows, 64), s->cap);
+  const int64_t groups = (r1 - r0) * s->ld / 4;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 8192));
+  rows16_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->d_rows16, s->ld, r0, r1, std::ldexp(1.0f, v_exp));
+  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
+    s->rows16_valid = 0;
+    return false;
+  }
+  s->c_f16_converted += s->rows - r0;
+  s->rows16_valid = s->rows;
+  return true;
+}
+
+// the fp16 scan's arguments on top of the f32 scan's (fill_scan_args) and the select's
+void fill_scan_f16_args(const Shard *s, const ScanF16Band &fb, ScanArgsQ *aq, SelectArgs *se) {
+  aq->a.rows16 = s->d_rows16;
+  aq->a.sqnorm = s->d_sqnorm;
+  aq->a.inv_scale = std::ldexp(1.0f, -s->rows16_exp);
+  aq->a.w_alpha = fb.alpha;
+  aq->a.w_beta = fb.beta;
+  if (se) {
+    se->eps_rel = 0.f;
+    se->delta_abs = 2.0f * fb.w_max * 1.0001f;
+    se->w_sq = s->metric == TSH_METRIC_COSINE ? nullptr : s->d_sqnorm;  // (cosine: the band is uniform)
+    se->w_alpha = fb.alpha;
+    se->w_beta = fb.beta;
+  }
+}
+
 int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries,
                 const uint64_t *mask_words, uint64_t epoch, uint8_t *dev_target, int64_t rows_est = 0,
                 const RowList *list = nullptr, bool more_coming = false, bool last_of_call = false, uint32_t tag = 0,
-                const MaskPart *mp = nullptr) {
+                const MaskPart *mp = nullptr, bool no_f16 = false) {
   // mp: the mask is a handle's part -- mask_words are its host words, its device words and (list->d_ids) its list
   // are read in place: nothing of the mask is copied or uploaded here
   Ctx *c = j->c;
@@ -1180,6 +1286,8 @@ int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries
   memcpy(qdst, query, (size_t)s->dim * sizeof(float));
   for (int64_t i = s->dim; i < s->ld; ++i) qdst[i] = 0.f;
   Band band;
+  ScanF16Band fb;
+  bool f16 = false;
   if (exact) {
     fill_exact_args(s, c, use_list, j->user_mask && !use_list, n_exam, qdst, &xa);
     xa.a.mask = (j->user_mask && !use_list) ? j->d_mask : nullptr;  // (the context's copy, or a handle's resident words)
@@ -1207,6 +1315,16 @@ int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries
     j->eps_rel = band.eps_rel;
     j->delta_abs = band.delta_abs;
     j->force_all = band.force_all != 0;
+    // the fp16 route: dense, unmasked, all-live scans of big shards, inside the error model on both sides
+    int v_exp = 0;
+    if (!no_f16 && !use_list && !j->masked && !band.force_all && scan_f16_applies(s, &v_exp)) {
+      if (s->scan_f16_denied.load() > 0) {
+        s->scan_f16_denied.fetch_sub(1);
+      } else {
+        fb = scan_f16_band(s->metric, s->dim, s->nch, qdst, s->max_norm, s->min_norm, v_exp);
+        f16 = fb.ok && rows16_ensure(s, s->scan_stream, v_exp);
+      }
+    }
     if (inline_q) {
       sa.a.query = nullptr;        // read q[] from the kernel-argument segment ...
       sa.a.query_out = c->d_query;  // ... and leave a device copy for the rerank kernel
@@ -1229,6 +1347,12 @@ int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries
   se.metric = s->metric;
   se.row_base = s->row_base;
   se.shard_rows = s->rows;
+  j->f16 = f16;
+  if (f16) {
+    fill_scan_f16_args(s, fb, &sa, &se);
+    j->q_f16.assign(query, query + s->dim);
+    j->tag = tag;
+  }
   RerankArgs ra{};
   ra.rows = s->d_rows;
   ra.query = c->d_query;
@@ -1296,6 +1420,7 @@ int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries
     }
     if (exact) launch_exact_scan(xa, s->metric, ps, ev);
     else if (use_list) launch_scan_list(sa, s->nch, s->metric, ps, ev);
+    else if (f16) launch_scan_f16(sa, s->nch, s->metric, ps, ev);
     else
       launch_scan(sa, s->nch, s->metric, j->masked, ps, ev,
                   j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows));
@@ -1413,6 +1538,7 @@ int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries
   s->c_scans++;
   if (use_list) s->c_list_scans++;
   if (exact) s->c_exact_scans++;
+  if (f16) s->c_f16_scans++;
   return TSH_OK;
 }
 
@@ -1544,6 +1670,32 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipEventSynchronize(c->ev_done));
   HIPCHK(hipGetLastError());
+  if (j->f16) {
+    // An fp16 scan whose candidate list overflowed (crowded neighbours: ties, near-duplicates) is NOT widened over its
+    // fp16 keys: the query is redone through the f32 scan, whose own overflow handling follows below as ever.  Two
+    // such queries in a row and the shard's next SCAN_F16_DENIED_SCANS eligible scans go straight to f32.
+    const BlockHeader *h16 = reinterpret_cast<const BlockHeader *>(c->h_block);
+    const bool over = (h16->flags & FLAG_LIST_OVERFLOW) != 0;
+    if (!over) {
+      s->scan_f16_strikes.store(0);
+    } else if (!(j->leave_overflow && j->dev_target)) {  // (left as it is: see Job::leave_overflow)
+      s->c_f16_redone++;
+      if (s->scan_f16_strikes.fetch_add(1) + 1 >= 2) {
+        s->scan_f16_strikes.store(0);
+        s->scan_f16_denied.store(SCAN_F16_DENIED_SCANS);
+      }
+      const std::vector<float> q(j->q_f16);
+      int rc = job_enqueue(s, j, q.data(), j->k, j->entries, nullptr, 0, j->dev_target, 0, nullptr, false, true, j->tag, nullptr,
+                           /*no_f16=*/true);
+      if (j->counted) {
+        s->inflight.fetch_sub(1);
+        j->counted = false;
+      }
+      if (rc) return rc;
+      HIPCHK(hipEventSynchronize(c->ev_done));
+      HIPCHK(hipGetLastError());
+    }
+  }
   if (j->timed) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) {
@@ -1843,6 +1995,7 @@ void shard_destroy(Shard *s) {
   hipFree(s->d_sqnorm);
   hipFree(s->d_live);
   hipFree(s->d_split);
+  hipFree(s->d_rows16);
   hipFree(s->d_perm);
   hipFree(s->d_psq);
   hipFree(s->d_hub);
@@ -3016,9 +3169,18 @@ int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const 
     if ((rc = ctx_reserve_exact(c, n_exam))) return rc;
     fill_exact_args(s, c, use_list, row_mask && !use_list, n_exam, c->h_query, &xa);
   }
+  // (... and a dense scan of a big shard reads the fp16 copy: the routing of job_enqueue, but for the denial counter)
+  bool f16 = false;
+  int v_exp = 0;
+  if (!exact && !use_list && !masked && scan_f16_applies(s, &v_exp) && !compute_band(s, c->h_query).force_all) {
+    const ScanF16Band fb = scan_f16_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, v_exp);
+    f16 = fb.ok && rows16_ensure(s, st, v_exp);
+    if (f16) fill_scan_f16_args(s, fb, &sa, nullptr);
+  }
   auto launch = [&]() {
     if (exact) launch_exact_scan(xa, s->metric, st, LaunchEv());
     else if (use_list) launch_scan_list(sa, s->nch, s->metric, st);
+    else if (f16) launch_scan_f16(sa, s->nch, s->metric, st);
     else launch_scan(sa, s->nch, s->metric, masked, st, LaunchEv(), ml);
   };
   launch();  // warm
@@ -3079,6 +3241,14 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
     for (auto &sh : idx->shards) {
       std::unique_lock<RwLock> xl(sh->mu);
       sh->exact_pick = value != 0;
+    }
+    return TSH_OK;
+  }
+  if (option == TSH_OPT_SCAN_F16) {
+    if (value < 0 || value > 2) return set_err(TSH_E_BAD_ARG, "scan f16 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible dense scan)");
+    for (auto &sh : idx->shards) {
+      std::unique_lock<RwLock> xl(sh->mu);
+      sh->scan_f16 = (int)value;
     }
     return TSH_OK;
   }
@@ -3156,6 +3326,62 @@ int32_t tsh_probe_scan_keys(tsh_index *idx, const float *query, float *out_keys,
   for (int64_t i = 0; i < s->rows; ++i) out_keys[i] = keys[(size_t)i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[(size_t)i]);
   *out_eps_rel = band.eps_rel;
   *out_delta_abs = band.delta_abs;
+  return TSH_OK;
+}
+
+int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  for (auto &sp : idx->shards) {
+    Shard *s = sp.get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    out[0] += s->c_f16_scans.load();
+    out[1] += s->c_f16_redone.load();
+    out[2] += s->c_f16_converted.load();
+    std::lock_guard<std::mutex> lk(s->rows16_mu);
+    out[3] += s->rows16_bytes;
+  }
+  return TSH_OK;
+}
+
+int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_keys, float *out_w) {
+  if (!idx || idx->shards.size() != 1 || !query || !out_keys || !out_w) return set_err(TSH_E_BAD_ARG, "bad arguments");
+  Shard *s = idx->shards[0].get();
+  std::shared_lock<RwLock> sl = share(idx, s);
+  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
+  Ctx *c = ctx_acquire(s, true);
+  struct Rel {
+    Shard *s;
+    Ctx *c;
+    ~Rel() { ctx_release(s, c); }
+  } rel{s, c};
+  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
+  if (rc) return rc;
+  hipStream_t st = s->aux_stream;
+  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
+  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
+  int v_exp = 0;
+  if (!scan_f16_applies(s, &v_exp) || compute_band(s, c->h_query).force_all)
+    return set_err(TSH_E_BAD_ARG, "no fp16 scan for this index / query (TSH_OPT_SCAN_F16, row width, tombstones, error model)");
+  const ScanF16Band fb = scan_f16_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, v_exp);
+  if (!fb.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the fp16 scan's error model");
+  if (!rows16_ensure(s, st, v_exp)) return set_err(TSH_E_OOM, "no room on the device for the fp16 copy of the rows");
+  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
+  static thread_local ScanArgsQ sa;
+  fill_scan_args(s, c, false, false, &sa);
+  fill_scan_f16_args(s, fb, &sa, nullptr);
+  launch_scan_f16(sa, s->nch, s->metric, st);
+  std::vector<uint32_t> keys((size_t)s->rows);
+  HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
+  // (the rows' bands, by the function the kernel adds them with -- into gmin's neighbour: the keys buffer is free again
+  // once copied, in stream order)
+  float *d_w = reinterpret_cast<float *>(c->d_keys);
+  scan_f16_w_kernel<<<(unsigned)((s->rows + 255) / 256), 256, 0, st>>>(s->metric == TSH_METRIC_COSINE ? nullptr : s->d_sqnorm, s->rows,
+                                                                      fb.alpha, fb.beta, d_w);
+  HIPCHK(hipMemcpyAsync(out_w, d_w, (size_t)s->rows * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  for (int64_t i = 0; i < s->rows; ++i) out_keys[i] = keys[(size_t)i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[(size_t)i]);
   return TSH_OK;
 }
 

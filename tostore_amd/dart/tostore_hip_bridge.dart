@@ -100,6 +100,10 @@ typedef _WaitD = int Function(
     Pointer<Void>, int, double, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _CountersC = Int32 Function(Pointer<Void>, Pointer<TshCounters>);
 typedef _CountersD = int Function(Pointer<Void>, Pointer<TshCounters>);
+typedef _ScanF16StatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _ScanF16StatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _ProbeScanF16C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _ProbeScanF16D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
 typedef _SetOptionD = int Function(Pointer<Void>, int, int);
 typedef _BlockBytesC = Int64 Function(Int32);
@@ -304,6 +308,8 @@ final class HipVectorBackend {
   static late final _WaitD _wait;
   static late final _CountersD _counters;
   static late final _SetOptionD _setOption;
+  static late final _ScanF16StatsD _scanF16Stats;
+  static late final _ProbeScanF16D _probeScanF16;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
   static late final _SearchShardD _searchShard;
@@ -358,6 +364,8 @@ final class HipVectorBackend {
       _wait = lib.lookupFunction<_WaitC, _WaitD>('tsh_search_wait');
       _counters = lib.lookupFunction<_CountersC, _CountersD>('tsh_get_counters');
       _setOption = lib.lookupFunction<_SetOptionC, _SetOptionD>('tsh_index_set_option');
+      _scanF16Stats = lib.lookupFunction<_ScanF16StatsC, _ScanF16StatsD>('tsh_scan_f16_stats');
+      _probeScanF16 = lib.lookupFunction<_ProbeScanF16C, _ProbeScanF16D>('tsh_probe_scan_f16_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
       _searchShard = lib.lookupFunction<_SearchShardC, _SearchShardD>('tsh_search_shard');
@@ -800,8 +808,26 @@ final class HipVectorBackend {
   }
 
   /// tsh_index_set_option: 1 = TSH_OPT_BATCH_MIN_NQ, 2 = TSH_OPT_BATCH_KERNEL, 4 = TSH_OPT_EXACT_SCAN_ROWS,
-  /// 5 = TSH_OPT_EXACT_SELECT, 6 = TSH_OPT_BATCH_HUB, 7 = TSH_OPT_BATCH_GROUP (tuning only: results never depend on them).
+  /// 5 = TSH_OPT_EXACT_SELECT, 6 = TSH_OPT_BATCH_HUB, 7 = TSH_OPT_BATCH_GROUP, 8 = TSH_OPT_SCAN_F16 (tuning only: results
+  /// never depend on them).
   bool setOption(int option, int value) => _setOption(_handle, option, value) == 0;
+
+  /// The fp16 scan's counters (TSH_OPT_SCAN_F16): scans over the fp16 copy of the rows, queries redone through the
+  /// f32 scan, rows converted, bytes of the copy resident.
+  Map<String, int>? scanF16Stats() {
+    final o = calloc<Int64>(4);
+    try {
+      if (_scanF16Stats(_handle, o) != 0) return null;
+      return {'scans': o[0], 'redone': o[1], 'rowsConverted': o[2], 'copyBytes': o[3]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
+  /// Diagnostics: the fp16 scan's stored key (upper side of its band) and band of every row for one query;
+  /// `keys` and `w` hold one float per row.
+  bool probeScanF16Keys(Pointer<Float> query, Pointer<Float> keys, Pointer<Float> w) =>
+      _probeScanF16(_handle, query, keys, w) == 0;
 
   int get nativeDimensions => _dim(_handle);
   int get nativeMetric => _metric(_handle);
