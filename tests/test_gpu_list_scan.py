@@ -14,6 +14,19 @@ def _check(idx, oracle_mod, rows, qs, metric, k, mask, thr=None, base=0):
         assert cnt[i] == len(e), (i, cnt[i], len(e))
         assert np.array_equal(ids[i, :cnt[i]], e + base), i
         assert np.array_equal(dist[i, :cnt[i]].view(np.uint64), ed.view(np.uint64)), i
+    return ids, dist, cnt
+
+
+def _tickets(idx, qs, k, mask):
+    """The queries as tickets (submit / wait), as many in flight as the handle takes -> [(ids, distances)]."""
+    from tostore_amd import _ffi
+
+    depth, out, flying = _ffi.lib().tsh_max_inflight(), [], []
+    for q in qs:
+        if len(flying) == depth:
+            out.append(idx.wait(flying.pop(0)))
+        flying.append(idx.submit(q, k, mask))
+    return out + [idx.wait(t) for t in flying]
 
 
 def _local(mask, base, n):
@@ -39,7 +52,8 @@ def test_selective_masks_every_width(hip_lib, oracle_mod, metric, d, scan_path):
         for keep in (0.004, 0.03):
             mask = np.packbits(rng.random(n) < keep, bitorder="little")
             c0 = idx.counters()
-            _check(idx, oracle_mod, rows, qs, metric, k, mask)      # a call of several queries (one list for all)
+            ids, dist, cnt = _check(idx, oracle_mod, rows, qs, metric, k, mask)  # a call of several queries (one list for all)
+            cm = idx.counters()
             _check(idx, oracle_mod, rows, qs[:1], metric, k, mask)  # a lone query
             c1 = idx.counters()
             assert c1["fallback_searches"] == c0["fallback_searches"]
@@ -47,6 +61,16 @@ def test_selective_masks_every_width(hip_lib, oracle_mod, metric, d, scan_path):
             assert c1["list_scans"] - c0["list_scans"] == c1["scan_launches"] - c0["scan_launches"] == len(qs) + 1
             # ... as f32 keys of the listed rows, or (the product's choice for so few rows) as their exact sums
             assert c1["exact_scans"] - c0["exact_scans"] == (len(qs) + 1 if scan_path != "prefilter" else 0)
+            if d == 100 and keep == 0.004:
+                # the ticket entry resolves the mask and routes like the synchronous call: the same answers by the same kernels
+                got = _tickets(idx, qs, k, mask)
+                c2 = idx.counters()
+                for i, (t_ids, t_dist) in enumerate(got):
+                    assert np.array_equal(t_ids, ids[i, :cnt[i]]), i
+                    assert np.array_equal(t_dist.view(np.uint64), dist[i, :cnt[i]].view(np.uint64)), i
+                for what in ("list_scans", "exact_scans", "scan_launches"):
+                    assert c2[what] - c1[what] == cm[what] - c0[what], (what, c0, cm, c1, c2)
+                assert c2["fallback_searches"] == c1["fallback_searches"]
         # a mild mask (one kept row in 10 > 1 in 24) walks the tiles: no list scan -- unless its 4000 kept rows are few
         # enough for the exact path, which reads nothing but its list at any selectivity
         mask = np.packbits(rng.random(n) < 0.1, bitorder="little")

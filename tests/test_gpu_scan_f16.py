@@ -62,6 +62,14 @@ def test_parity(hip_lib, oracle_mod, d, metric):
             _same(idx.search(qs, k), ref, "k=%d" % k)
             s1 = idx.scan_f16_stats()
             assert s1["scans"] - s0["scans"] == len(qs) and s1["redone"] == 0, (s0, s1)
+            if d == 768 and metric == L2 and k == 10:  # the ticket entry takes the same route
+                tickets = [idx.submit(q, k) for q in qs]
+                for i, t in enumerate(tickets):
+                    ids, dist = idx.wait(t)
+                    assert np.array_equal(ids, ref[0][i, :ref[2][i]]), i
+                    assert np.array_equal(dist.view(np.uint64), ref[1][i, :ref[2][i]].view(np.uint64)), i
+                s2 = idx.scan_f16_stats()
+                assert s2["scans"] - s1["scans"] == len(qs) and s2["redone"] == 0, (s1, s2)
         assert s1["rows_converted"] == N and s1["copy_bytes"] >= N * d * 2
 
 

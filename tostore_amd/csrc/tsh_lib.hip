@@ -911,21 +911,23 @@ Band compute_band(const Shard *s, const float *q) {
   return b;
 }
 
-void fill_scan_args(const Shard *s, const Ctx *c, bool masked, bool user_mask, ScanArgsQ *aq) {
+// d_mask: the caller's mask words on the device, or NULL; d_list: the rows to scan as a list of list_padded ids on the
+// device, or NULL (the shard's tiles)
+void fill_scan_args(const Shard *s, const Ctx *c, const uint64_t *d_mask, const uint32_t *d_list, int32_t list_padded, ScanArgsQ *aq) {
   ScanArgs *a = &aq->a;
   a->rows = s->d_rows;
   a->query = c->d_query;
   a->query_out = nullptr;
   a->inv_norm = s->d_inv_norm;
   a->live = s->d_live;
-  a->mask = (masked && user_mask) ? c->d_mask : nullptr;
+  a->mask = d_mask;
   a->keys = c->d_keys;
   a->gmin = c->d_gmin;
   a->ld = s->ld;
   a->n = s->rows;
   a->d4 = (int32_t)(s->ld / 4);
-  a->n_tiles = (int32_t)((s->rows + 63) / 64);
-  a->list = nullptr;
+  a->n_tiles = d_list ? list_padded / 64 : (int32_t)((s->rows + 63) / 64);
+  a->list = d_list;
   a->rows16 = nullptr;
   a->sqnorm = nullptr;
   a->inv_scale = a->w_alpha = a->w_beta = 0.f;
@@ -936,6 +938,18 @@ void fill_scan_args(const Shard *s, const Ctx *c, bool masked, bool user_mask, S
 inline void slice_mask(const Shard *s, const uint8_t *mask, uint64_t *out_words, int64_t n_words) {
   tsh::slice_mask(s->row_base, s->rows, mask, out_words, n_words);
 }
+
+// Which kernels answer one query on one shard (choose_route)
+struct Route {
+  bool use_list = false;  // the scan reads the mask's list of kept rows, not the shard's tiles
+  int64_t n_exam = 0;     // rows (list: entries, padding included) the scan looks at
+  bool exact = false;     // exact_scan_kernel + exact_select_kernel: the block is final, no f32 keys exist
+  bool picked = false;    // ... + exact_pick_kernel instead of exact_select_kernel
+  Band band;              // the f32 keys' error band (zero on the exact path)
+  bool f16_eligible = false;  // the fp16 scan may run (the caller still owes the denial counter and rows16_ensure) ...
+  int v_exp = 0;              // ... over a copy of this scale, its keys inside this band
+  ScanF16Band fb;
+};
 
 // One query in flight on one context.  Its three kernels (scan, select,
 // rerank) are enqueued back to back on the shard's single in-order pipeline
@@ -949,14 +963,13 @@ struct Job {
   uint8_t *dev_target = nullptr;  // shard mode: caller's device block (header + entries land there)
   bool timed = false;             // ev0/ev1 bracket this job's scan kernel
   bool counted = false;           // contributes to Shard::inflight
-  float eps_rel = 0.f, delta_abs = 0.f;  // this query's error band (for the fallback's own threshold)
-  bool force_all = false;
-  int32_t list_tiles = 0;  // > 0: a list scan -- the context's keys / gmin are in list order, that many tiles of them
+  Route route;  // the kernels it was enqueued with; its band is also the fallback's own threshold.  (A list scan leaves
+                // the context's keys / gmin in list order, route.n_exam of them)
+  bool up_mask = false, up_list = false;  // staged in the context's pinned buffers: copied to the device in front of the scan
   const uint64_t *d_mask = nullptr;  // the caller's mask words on the device: the context's copy, or a mask handle's
   const uint32_t *d_list = nullptr;  // the scanned list on the device: the context's copy, or a mask handle's
-  bool exact = false;      // answered by exact_scan_kernel + exact_select_kernel: the block is final, no f32 keys exist
-  bool picked = false;     // ... by exact_pick_kernel instead of exact_select_kernel: a cut bin too full for the block is
-  ExactSelArgs xsel{};     // finished by exact_select_kernel on the same keys (these arguments), job_finish
+  ExactSelArgs xsel{};     // the exact path: a pick whose cut bin was too full for the block is finished by
+                           // exact_select_kernel on the same keys (these arguments), job_finish
   bool leave_overflow = false;  // shard mode under TSH_OPT_EXCHANGE_AHEAD: an exchange enqueued behind this job's kernels
                                 // may be reading the device block when the host looks at it -- a block whose list
                                 // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
@@ -1009,6 +1022,15 @@ struct MaskSrc {
   explicit MaskSrc(const MaskPart *p) : part(p) {}
   explicit operator bool() const { return bytes != nullptr || part != nullptr; }
 };
+// ... and as one shard's scans read it: what resolve_mask makes of a MaskSrc, once per call
+struct ShardMask {
+  const uint64_t *words = nullptr;  // this shard's slice on the host (the caller's scratch, or a handle's part); NULL: no mask
+  uint64_t epoch = 0;               // names a sliced pointer mask, so that a context uploads it once per call
+  int64_t rows_est = 0;             // rows the scan will actually read (the mask's popcount, at least 1); 0: all of them
+  RowList list;                     // a selective mask's kept rows
+  const MaskPart *part = nullptr;   // a handle's: its device words and list are read in place, nothing is copied or uploaded
+  bool listed() const { return list.ids || list.d_ids; }
+};
 
 void launch_select(const SelectArgs &se, int32_t n_tiles, hipStream_t st) {
   // a few hundred tiles (an index of some ten thousand rows): four waves instead of sixteen synchronise
@@ -1026,6 +1048,21 @@ void launch_select(const SelectArgs &se, int32_t n_tiles, hipStream_t st) {
   else select_kernel<SEL_THREADS, false><<<1, SEL_THREADS, 0, st>>>(se);
 }
 
+// host mode: the quarantined rows' sums go to the context's pinned h_quar (the host picks the query's: Job::quar_sel)
+void launch_quarantine(Shard *s, Ctx *c, hipStream_t st) {
+  QuarArgs qa{};
+  qa.rows = s->d_rows;
+  qa.Q = c->d_query;
+  qa.list = s->d_quar;
+  qa.out = c->h_quar_dev;
+  qa.ld = s->ld;
+  qa.ldq = s->ld;
+  qa.row_base = s->row_base;
+  qa.dim = s->dim;
+  qa.cap = (int32_t)QUARANTINE_MAX;
+  qa.metric = s->metric;
+  quarantine_kernel<<<dim3((unsigned)((s->quar_ids.size() + 63) / 64), 1), 64, 0, st>>>(qa);
+}
 // shard mode: the quarantined rows go into the job's device block
 void launch_quarantine_append(Shard *s, Ctx *c, Job *j, hipStream_t st) {
   QuarAppendArgs qa{};
@@ -1044,9 +1081,6 @@ void launch_quarantine_append(Shard *s, Ctx *c, Job *j, hipStream_t st) {
   quarantine_append_kernel<<<dim3((unsigned)((s->quar_ids.size() + 63) / 64), 1), 64, 0, st>>>(qa);
 }
 
-// mask_words: this shard's slice of the caller mask (host), or NULL; epoch
-// identifies it so a context uploads it once per call
-// rows_est: rows the scan will actually read (popcount of the caller's mask; <= 0: all of them)
 int ctx_reserve_list(Ctx *c, int64_t padded) {
   if (padded <= c->list_cap) return TSH_OK;
   hipFree(c->d_list);
@@ -1064,12 +1098,16 @@ int ctx_reserve_list(Ctx *c, int64_t padded) {
   return TSH_OK;
 }
 
+// A search with at most TSH_OPT_EXACT_SCAN_ROWS rows to look at takes the exact path (tsh_exact.hip.h); its block must
+// have room for the k rows it will hold
+bool exact_applies(const Shard *s, int64_t n_exam, int32_t k, int32_t entries) {
+  return n_exam > 0 && n_exam <= std::min<int64_t>(s->exact_rows, EX_MAX_ROWS) && k <= entries;
+}
 // (list_mask_bits / popcount_words: tsh_host_sync.h -- pure host functions, tested on the CPU)
 // A selective mask (a WHERE clause that keeps a few percent of the rows) is scanned as a LIST of row ids: scan_list_kernel
 // gathers the kept rows, eight per wave, instead of walking tiles that are mostly dead (tsh_kernels.hip.h).  The list
 // pays below one kept row in list_div (tools/r4_list_probe.sh); TSH_LIST_DIV=0 switches it off.  -> ids filled (padded
 // with 0xFFFFFFFF to whole tiles) and true when the scan should use them.
-bool exact_applies(const Shard *s, int64_t n_exam, int32_t k, int32_t entries);
 inline int64_t mask_list_div() {
   static const int64_t v = probe_env("TSH_LIST_DIV") ? atoll(probe_env("TSH_LIST_DIV")) : 24;
   return v;
@@ -1096,6 +1134,33 @@ bool build_row_list(const Shard *s, const uint64_t *mask_words, int32_t n_tiles,
   ids->resize(padded);
   return true;
 }
+// The per-call work on a search's mask, for one shard.  A handle's part was sliced, counted and listed when it was made:
+// only whether its list pays for this k is left to ask.  A pointer mask is sliced into *words, counted (one pass per call:
+// how long will each scan be?) and, when selective, listed into *ids -- the caller's scratch, which the result points into.
+ShardMask resolve_mask(Shard *s, const MaskSrc &mask, int32_t k, int32_t entries, std::vector<uint64_t> *words, std::vector<uint32_t> *ids) {
+  ShardMask m;
+  if (const MaskPart *mp = mask.part) {
+    m.part = mp;
+    m.words = mp->h_words.data();
+    m.rows_est = std::max<int64_t>(mp->kept, 1);
+    if (mp->list_padded > 0 && row_list_pays(s, mp->kept, k, entries)) {
+      m.list.d_ids = mp->d_list;
+      m.list.padded = mp->list_padded;
+    }
+  } else if (mask.bytes) {
+    const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
+    if (words->size() < (size_t)n_tiles) words->resize((size_t)n_tiles);
+    slice_mask(s, mask.bytes, words->data(), n_tiles);
+    m.words = words->data();
+    m.epoch = s->mask_epoch_src.fetch_add(1);
+    m.rows_est = std::max<int64_t>(popcount_words(words->data(), (size_t)n_tiles), 1);
+    if (build_row_list(s, words->data(), n_tiles, m.rows_est, k, entries, ids)) {
+      m.list.ids = ids->data();
+      m.list.padded = (int32_t)ids->size();
+    }
+  }
+  return m;
+}
 
 int ctx_reserve_exact(Ctx *c, int64_t n) {
   if (n <= c->x_cap) return TSH_OK;
@@ -1118,20 +1183,16 @@ int ctx_reserve_exact(Ctx *c, int64_t n) {
   return TSH_OK;
 }
 
-// A search with at most TSH_OPT_EXACT_SCAN_ROWS rows to look at takes the exact path (tsh_exact.hip.h); its block must
-// have room for the k rows it will hold
-bool exact_applies(const Shard *s, int64_t n_exam, int32_t k, int32_t entries) {
-  return n_exam > 0 && n_exam <= std::min<int64_t>(s->exact_rows, EX_MAX_ROWS) && k <= entries;
-}
-// E1's arguments but for where the query is (a.query / a.query_out: the caller's); q: the query, zero-padded to ld
-void fill_exact_args(const Shard *s, const Ctx *c, bool use_list, bool dense_mask, int64_t n_exam, const float *q, ExactArgsQ *xa) {
+// E1's arguments but for where the query is (a.query / a.query_out: the caller's); q: the query, zero-padded to ld;
+// d_mask: the caller's mask words on the device, for entries by row, or NULL; d_list: the entries' rows, or NULL
+void fill_exact_args(const Shard *s, const Ctx *c, const uint64_t *d_mask, const uint32_t *d_list, int64_t n_exam, const float *q, ExactArgsQ *xa) {
   ExactArgs *a = &xa->a;
   a->rows = s->d_rows;
   a->query = c->d_query;
   a->query_out = nullptr;
   a->live = s->d_live;
-  a->mask = dense_mask ? c->d_mask : nullptr;
-  a->list = use_list ? c->d_list : nullptr;
+  a->mask = d_mask;
+  a->list = d_list;
   a->list_out = nullptr;
   a->xkey = c->d_xkey;
   a->xsum = c->d_xsum;
@@ -1143,18 +1204,18 @@ void fill_exact_args(const Shard *s, const Ctx *c, bool use_list, bool dense_mas
   a->dim = s->dim;
 }
 
+// a launch whose events, if any, ride on the kernel's own dispatch packet
+#define TSH_LAUNCH_EV(kern, grid, block, st, start, stop, args)                                                      \
+  do {                                                                                                               \
+    if (start || stop) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, st, start, stop, 0, args);            \
+    else kern<<<grid, block, 0, st>>>(args);                                                                         \
+  } while (0)
 // E1 of a short search (tsh_exact.hip.h): one wave per eight entries, the events on the kernel's own packet
 void launch_exact_scan(const ExactArgsQ &xa, int metric, hipStream_t st, const LaunchEv &ev) {
   const unsigned grid = (unsigned)((xa.a.n_entries + EX_R - 1) / EX_R);
-#define TSH_EXACT_LAUNCH(M)                                                                                      \
-  do {                                                                                                           \
-    if (ev.start || ev.stop) hipExtLaunchKernelGGL(exact_scan_kernel<M>, dim3(grid), dim3(64), 0, st, ev.start, ev.stop, 0, xa); \
-    else exact_scan_kernel<M><<<grid, 64, 0, st>>>(xa);                                                          \
-  } while (0)
-  if (metric == TSH_METRIC_L2) TSH_EXACT_LAUNCH(METRIC_L2);
-  else if (metric == TSH_METRIC_IP) TSH_EXACT_LAUNCH(METRIC_IP);
-  else TSH_EXACT_LAUNCH(METRIC_COS);
-#undef TSH_EXACT_LAUNCH
+  if (metric == TSH_METRIC_L2) TSH_LAUNCH_EV(exact_scan_kernel<METRIC_L2>, grid, 64, st, ev.start, ev.stop, xa);
+  else if (metric == TSH_METRIC_IP) TSH_LAUNCH_EV(exact_scan_kernel<METRIC_IP>, grid, 64, st, ev.start, ev.stop, xa);
+  else TSH_LAUNCH_EV(exact_scan_kernel<METRIC_COS>, grid, 64, st, ev.start, ev.stop, xa);
 }
 
 // ---- the fp16 scan's route (TSH_OPT_SCAN_F16) ---------------------------------------------------------------------
@@ -1231,185 +1292,287 @@ void fill_scan_f16_args(const Shard *s, const ScanF16Band &fb, ScanArgsQ *aq, Se
   }
 }
 
-int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries,
-                const uint64_t *mask_words, uint64_t epoch, uint8_t *dev_target, int64_t rows_est = 0,
-                const RowList *list = nullptr, bool more_coming = false, bool last_of_call = false, uint32_t tag = 0,
-                const MaskPart *mp = nullptr, bool no_f16 = false) {
-  // mp: the mask is a handle's part -- mask_words are its host words, its device words and (list->d_ids) its list
-  // are read in place: nothing of the mask is copied or uploaded here
-  Ctx *c = j->c;
-  int rc = ctx_prepare(s, c, entries, mask_words != nullptr && !mp);
-  if (rc) return rc;
-  const bool use_list = list && (list->ids || list->d_ids) && mask_words;
-  const bool own_list = use_list && !list->d_ids;  // the context's copy of a host-made list
-  if (own_list && (rc = ctx_reserve_list(c, list->padded))) return rc;
-  j->d_mask = mp ? mp->d_words : c->d_mask;
-  j->d_list = use_list ? (own_list ? c->d_list : list->d_ids) : nullptr;
-  j->list_tiles = use_list ? list->padded / 64 : 0;
-  const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
+// The route of one query's scan on this shard, decided here for every caller and without side effects.  m: the search's
+// mask (resolve_mask); masked: a mask or tombstones; q: the query (dim floats are read: zero-padded or not); no_f16:
+// the redo of an fp16 scan.  Caller holds s->mu shared.
+Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, int32_t entries, const float *q, bool no_f16) {
+  Route r;
+  r.use_list = m.listed();
   // A search with only a few thousand rows to look at (a selective mask's list, a small index or shard) takes their
   // exact sums directly and selects among the exact distances: two dispatches instead of three, no f32 keys, no band
   // (tsh_exact.hip.h).  The block must have room for the k rows it will hold.
-  const int64_t n_exam = use_list ? (int64_t)list->padded : s->rows;
-  const bool exact = exact_applies(s, n_exam, k, entries);
-  j->exact = exact;
-  if (exact && (rc = ctx_reserve_exact(c, n_exam))) return rc;
-  j->k = k;
-  j->entries = entries;
-  j->user_mask = mask_words != nullptr;
-  j->masked = j->user_mask || !s->all_live;
-  j->dev_target = dev_target;
+  r.n_exam = r.use_list ? (int64_t)m.list.padded : s->rows;
+  r.exact = exact_applies(s, r.n_exam, k, entries);
+  if (r.exact) {
+    // E2' (the wide pick) bounds the k-th key by the k-th smallest wave minimum: it needs clearly more waves than k
+    r.picked = s->exact_pick && (r.n_exam + EX_R - 1) / EX_R >= 2 * (int64_t)k;
+    return r;
+  }
+  r.band = compute_band(s, q);
+  // the fp16 route: dense, unmasked, all-live scans of big shards, inside the error model on both sides
+  r.f16_eligible = !no_f16 && !r.use_list && !masked && !r.band.force_all && scan_f16_applies(s, &r.v_exp);
+  if (r.f16_eligible) r.fb = scan_f16_band(s->metric, s->dim, s->nch, q, s->max_norm, s->min_norm, r.v_exp);
+  return r;
+}
+// One query for job_enqueue
+struct JobReq {
+  JobReq(const float *q, int32_t k_, int32_t entries_) : query(q), k(k_), entries(entries_) {}
+  const float *query;  // dim floats
+  int32_t k, entries;
+  ShardMask mask;
+  uint8_t *dev_target = nullptr;  // shard mode: the caller's device block
+  bool more_coming = false;       // the caller is about to submit more queries
+  bool last_of_call = false;      // ... or this is the last of several
+  uint32_t tag = 0;               // generation stamped into the block's header
+  bool no_f16 = false;            // the redo of an fp16 scan whose list overflowed: f32 this time
+};
+// the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
+struct JobArgs {
+  ScanArgsQ sa;
+  ExactArgsQ xa;
+  SelectArgs se;
+  RerankArgs ra;
+};
+// (RerankArgs, ExactSelArgs and ExactPickArgs below: in the order of their fields)
+RerankArgs rerank_args(const Shard *s, const Ctx *c, const uint32_t *cand_rows, const uint32_t *count_ptr, BlockEntry *out, int32_t cap) {
+  return RerankArgs{s->d_rows, c->d_query, cand_rows, count_ptr, out, s->ld, s->row_base, s->dim, cap, s->metric};
+}
+// E2' reads what E2 reads (xs), E1's wave minima and its own counter
+ExactPickArgs exact_pick_args(const ExactSelArgs &xs, const Ctx *c) {
+  return ExactPickArgs{xs.xkey, xs.xsum, xs.list, /*wmin*/ c->d_xpick + 1, /*ctr*/ reinterpret_cast<unsigned long long *>(c->d_xpick),
+                       xs.hdr, xs.hdr_host, xs.out, xs.row_base, xs.shard_rows, xs.n_entries,
+                       /*n_groups*/ (xs.n_entries + EX_R - 1) / EX_R, xs.k, xs.cap, xs.metric, xs.tag};
+}
+// Reserves what the job's route needs in its context and stages the inputs on the host: the job's fields, mask and list in
+// the context's pinned buffers where new to it, the query zero-padded at *qp (the scan's argument segment, or c->h_query)
+int job_stage(Shard *s, Job *j, const JobReq &rq, JobArgs *ka, float **qp) {
+  Ctx *c = j->c;
+  const ShardMask &m = rq.mask;
+  const Route &r = j->route;
+  int rc = ctx_prepare(s, c, rq.entries, m.words != nullptr && !m.part);
+  if (rc) return rc;
+  const bool own_list = r.use_list && !m.list.d_ids;  // the context's copy of a host-made list
+  if (own_list && (rc = ctx_reserve_list(c, m.list.padded))) return rc;
+  if (r.exact && (rc = ctx_reserve_exact(c, r.n_exam))) return rc;
+  j->d_mask = m.part ? m.part->d_words : c->d_mask;
+  j->d_list = r.use_list ? (own_list ? c->d_list : m.list.d_ids) : nullptr;
+  j->k = rq.k;
+  j->entries = rq.entries;
+  j->dev_target = rq.dev_target;
   j->quar_sel.clear();
   if (!s->quar_ids.empty()) {
-    quarantine_select(s, mask_words, &j->quar_sel);
-    if (!j->quar_sel.empty() && !dev_target && !c->h_quar) {
+    quarantine_select(s, m.words, &j->quar_sel);
+    if (!j->quar_sel.empty() && !rq.dev_target && !c->h_quar) {
       HIPCHK(hipHostMalloc(&c->h_quar, QUARANTINE_MAX * sizeof(BlockEntry), hipHostMallocMapped));
       HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_quar_dev), c->h_quar, 0));
     }
   }
-  uint8_t *dev_block = dev_target ? dev_target : c->d_block;  // where the device header lives
   // (a list scan needs the mask words on the device only where quarantined rows are matched against them)
-  const bool upload_mask = mask_words && !mp && c->mask_epoch != epoch && (!use_list || (!j->quar_sel.empty() && dev_target));
-  if (upload_mask) {
-    memcpy(c->h_mask, mask_words, (size_t)n_tiles * 8);
-    c->mask_epoch = epoch;
+  j->up_mask = m.words && !m.part && c->mask_epoch != m.epoch && (!r.use_list || (!j->quar_sel.empty() && rq.dev_target));
+  if (j->up_mask) {
+    memcpy(c->h_mask, m.words, (size_t)((s->rows + 63) / 64) * 8);
+    c->mask_epoch = m.epoch;
   }
-  const bool upload_list = own_list && c->list_epoch != epoch;
-  if (upload_list) {
-    memcpy(c->h_list, list->ids, (size_t)list->padded * sizeof(uint32_t));
-    c->list_epoch = epoch;
+  j->up_list = own_list && c->list_epoch != m.epoch;
+  if (j->up_list) {
+    memcpy(c->h_list, m.list.ids, (size_t)m.list.padded * sizeof(uint32_t));
+    c->list_epoch = m.epoch;
   }
-  static thread_local ScanArgsQ sa;  // 4 KiB: keep it off the stack of deep callers
-  static thread_local ExactArgsQ xa;
+  float *q = *qp = s->ld <= SCAN_Q_INLINE ? (r.exact ? ka->xa.q : ka->sa.q) : c->h_query;
+  memcpy(q, rq.query, (size_t)s->dim * sizeof(float));
+  for (int64_t i = s->dim; i < s->ld; ++i) q[i] = 0.f;
+  return TSH_OK;
+}
+
+// The arguments of the job's kernels: E1 and E2 (Job::xsel) of the exact path, or scan, select and re-rank.  q: the
+// staged query (job_stage)
+void fill_job_args(const Shard *s, Job *j, const JobReq &rq, const float *q, JobArgs *ka) {
+  Ctx *c = j->c;
+  const Route &r = j->route;
   const bool inline_q = s->ld <= SCAN_Q_INLINE;
-  float *qdst = inline_q ? (exact ? xa.q : sa.q) : c->h_query;
-  memcpy(qdst, query, (size_t)s->dim * sizeof(float));
-  for (int64_t i = s->dim; i < s->ld; ++i) qdst[i] = 0.f;
-  Band band;
-  ScanF16Band fb;
-  bool f16 = false;
-  if (exact) {
-    fill_exact_args(s, c, use_list, j->user_mask && !use_list, n_exam, qdst, &xa);
-    xa.a.mask = (j->user_mask && !use_list) ? j->d_mask : nullptr;  // (the context's copy, or a handle's resident words)
-    xa.a.list = j->d_list;
-    xa.a.query = inline_q ? nullptr : c->d_query;
+  BlockHeader *hdr = reinterpret_cast<BlockHeader *>(rq.dev_target ? rq.dev_target : c->d_block);  // where the device header lives
+  BlockHeader *hdr_host = reinterpret_cast<BlockHeader *>(c->h_block_dev);
+  BlockEntry *out = reinterpret_cast<BlockEntry *>((rq.dev_target ? rq.dev_target : c->h_block_dev) + sizeof(BlockHeader));
+  if (r.exact) {
+    ExactArgs &a = ka->xa.a;
+    fill_exact_args(s, c, j->user_mask && !r.use_list ? j->d_mask : nullptr, j->d_list, r.n_exam, q, &ka->xa);
+    a.query = inline_q ? nullptr : c->d_query;
     // (only the quarantine kernels read the device copy of an inline query)
-    xa.a.query_out = inline_q && !j->quar_sel.empty() ? c->d_query : nullptr;
-    if (upload_list) {  // a new list: E1 reads it where it is (pinned host memory) and leaves the device copy -- a
-      xa.a.list = c->h_list_dev;  // DMA packet in front of the scan cost a lone masked query ~8 us before anything ran
-      xa.a.list_out = c->d_list;
+    a.query_out = inline_q && !j->quar_sel.empty() ? c->d_query : nullptr;
+    if (j->up_list) {  // a new list: E1 reads it where it is (pinned host memory) and leaves the device copy -- a
+      a.list = c->h_list_dev;  // DMA packet in front of the scan cost a lone masked query ~8 us before anything ran
+      a.list_out = c->d_list;
     }
-    // E2' (the wide pick) bounds the k-th key by the k-th smallest wave minimum: it needs clearly more waves than k
-    j->picked = s->exact_pick && (n_exam + EX_R - 1) / EX_R >= 2 * (int64_t)k;
-    if (j->picked) xa.a.wmin = c->d_xpick + 1;
-    j->eps_rel = j->delta_abs = 0.f;
-    j->force_all = false;
-  } else {
-    fill_scan_args(s, c, j->masked, j->user_mask, &sa);
-    sa.a.mask = (j->masked && j->user_mask) ? j->d_mask : nullptr;
-    if (use_list) {
-      sa.a.list = j->d_list;
-      sa.a.n_tiles = j->list_tiles;
-    }
-    band = compute_band(s, qdst);
-    j->eps_rel = band.eps_rel;
-    j->delta_abs = band.delta_abs;
-    j->force_all = band.force_all != 0;
-    // the fp16 route: dense, unmasked, all-live scans of big shards, inside the error model on both sides
-    int v_exp = 0;
-    if (!no_f16 && !use_list && !j->masked && !band.force_all && scan_f16_applies(s, &v_exp)) {
-      if (s->scan_f16_denied.load() > 0) {
-        s->scan_f16_denied.fetch_sub(1);
-      } else {
-        fb = scan_f16_band(s->metric, s->dim, s->nch, qdst, s->max_norm, s->min_norm, v_exp);
-        f16 = fb.ok && rows16_ensure(s, s->scan_stream, v_exp);
-      }
-    }
-    if (inline_q) {
-      sa.a.query = nullptr;        // read q[] from the kernel-argument segment ...
-      sa.a.query_out = c->d_query;  // ... and leave a device copy for the rerank kernel
-    }
+    if (r.picked) a.wmin = c->d_xpick + 1;
+    j->xsel = ExactSelArgs{c->d_xkey, c->d_xsum, j->d_list, hdr, hdr_host, out, s->row_base, /*shard_rows*/ s->rows, a.n_entries,
+                           rq.k, /*cap*/ rq.entries, s->metric, rq.tag};
+    return;
   }
-  SelectArgs se{};
+  fill_scan_args(s, c, j->user_mask ? j->d_mask : nullptr, j->d_list, r.use_list ? rq.mask.list.padded : 0, &ka->sa);
+  if (inline_q) {
+    ka->sa.a.query = nullptr;        // read q[] from the kernel-argument segment ...
+    ka->sa.a.query_out = c->d_query;  // ... and leave a device copy for the rerank kernel
+  }
+  SelectArgs &se = ka->se = SelectArgs{};
   se.gmin = c->d_gmin;
   se.keys = c->d_keys;
-  se.hdr = reinterpret_cast<BlockHeader *>(dev_block);
-  se.hdr_host = reinterpret_cast<BlockHeader *>(c->h_block_dev);
+  se.hdr = hdr;
+  se.hdr_host = hdr_host;
   se.cand_rows = c->d_cand;
-  se.n_tiles = use_list ? j->list_tiles : n_tiles;
+  se.n_tiles = ka->sa.a.n_tiles;
   se.list = j->d_list;
-  se.tag = tag;
-  se.k = k;
-  se.cand_cap = entries;
-  se.eps_rel = band.eps_rel;
-  se.delta_abs = band.delta_abs;
-  se.force_all = band.force_all;
+  se.tag = rq.tag;
+  se.k = rq.k;
+  se.cand_cap = rq.entries;
+  se.eps_rel = r.band.eps_rel;
+  se.delta_abs = r.band.delta_abs;
+  se.force_all = r.band.force_all;
   se.metric = s->metric;
   se.row_base = s->row_base;
   se.shard_rows = s->rows;
-  j->f16 = f16;
-  if (f16) {
-    fill_scan_f16_args(s, fb, &sa, &se);
-    j->q_f16.assign(query, query + s->dim);
-    j->tag = tag;
+  if (j->f16) fill_scan_f16_args(s, r.fb, &ka->sa, &se);
+  ka->ra = rerank_args(s, c, c->d_cand, &hdr->count, out, rq.entries);
+}
+
+// ---- on which streams a job's kernels run (all of it under the device's scan_mu) ------------------------------------
+// The scan's stream; *which >= 0: one of the two scan streams of a small shard, booked in DeviceStreams::scan_out once
+// the scan is enqueued
+hipStream_t pick_scan_stream(Shard *s, bool overlap, int64_t rows_est, int *which) {
+  *which = -1;
+  // Between two scans on one in-order stream the GPU idles for about 13 us (drain, write-back,
+  // ramp-up).  That is 3 % of a 1 M-row scan but 20 % of a 125 k-row one (a shard of an 8-GPU
+  // index), so small shards alternate between two streams and the next scan's workgroups fill
+  // in as the previous one drains (+12 % queries/s at 125 k and 250 k rows).  The two scans
+  // then run side by side, so each one's own duration roughly doubles; large shards keep one
+  // stream, where a scan's duration is its HBM time.  TSH_SCAN_STREAMS=1 / 2 forces either.
+  static const int forced = probe_env("TSH_SCAN_STREAMS") ? atoi(probe_env("TSH_SCAN_STREAMS")) : 0;
+  // (a selective row mask makes a big shard's scan just as short: count the rows it keeps)
+  const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
+  const int64_t tiles_read = rows_est > 0 ? std::min<int64_t>(n_tiles, (rows_est + 63) / 64) : n_tiles;
+  static const int min_tiles = probe_env("TSH_TWO_STREAM_MIN_TILES") ? atoi(probe_env("TSH_TWO_STREAM_MIN_TILES")) : 0;
+  const bool two = forced == 2 || (forced != 1 && tiles_read < SMALL_SHARD_TILES && tiles_read >= min_tiles);
+  if (!(overlap && two && s->scan_stream2)) return s->scan_stream;
+  DeviceStreams *ds = s->dstreams;
+  for (size_t i = 0; i < ds->scan_out.size();) {  // scans that have finished since the last look
+    if (hipEventQuery(ds->scan_out[i].ev) != hipErrorNotReady) {
+      ds->scans_out[ds->scan_out[i].which]--;
+      ds->scan_out[i] = ds->scan_out.back();
+      ds->scan_out.pop_back();
+    } else {
+      ++i;
+    }
   }
-  RerankArgs ra{};
-  ra.rows = s->d_rows;
-  ra.query = c->d_query;
-  ra.cand_rows = c->d_cand;
-  ra.count_ptr = &se.hdr->count;
-  ra.out = reinterpret_cast<BlockEntry *>((dev_target ? dev_target : c->h_block_dev) + sizeof(BlockHeader));
-  ra.ld = s->ld;
-  ra.row_base = s->row_base;
-  ra.dim = s->dim;
-  ra.cap = entries;
-  ra.metric = s->metric;
+  (void)hipGetLastError();  // (hipErrorNotReady is an answer, not an error)
+  *which = ds->scans_out[0] != ds->scans_out[1] ? (ds->scans_out[1] < ds->scans_out[0] ? 1 : 0) : (int)(s->scan_seq++ & 1);
+  return *which ? s->scan_stream2 : s->scan_stream;
+}
+
+// The stream of what follows the scan (enqueued on ps; `scanned` rides on its packet): ps itself, in order, or one of
+// the tail queues on the reserved CUs, made to wait for the scan.  overlap: ... and this is not the last query of a call
+int pick_tail_stream(Shard *s, const Route &r, bool overlap, int which, hipStream_t ps, hipEvent_t scanned, hipStream_t *out) {
+  *out = ps;
+  // (the last query of a call: nothing follows its scan on that stream, so its tail stays there -- in order, without
+  // the ~10 us of a cross-stream event hand-off in front of the select, on the step every caller waits for)
+  // (the exact path's select stays on its scan stream, in order behind its short scan, while the scan is short: no
+  // cross-stream hand-off, and the two scan streams alternate whole queries -- 64-query calls on 10 k x 128: 20.6 -> 16.2 us
+  // per query, 2 k x 768: 22 -> 16.7, 8 k x 768: 21 -> 18.4; from ~8 k rows of 768 on the tail queues win again: 16 k x
+  // 768 23 against 25; tools/r5_x_inorder.sh)
+#ifndef TSH_X_INORDER_MAX
+#define TSH_X_INORDER_MAX 6500000
+#endif
+  // (round 6: behind the wide pick -- 5-6 us, one workgroup per 256 entries -- the tail queues' 16 CUs and their
+  // cross-stream hand-off, ~10 us in front of the pick under load, never pay: 10 k x 768 in 64-query calls 18.5-23.9 ->
+  // 15.8-19.2 us per query, same box, alternating, tools/r6_inorder_ab.sh)
+  const bool x_inorder = r.exact && (r.picked || r.n_exam * s->ld <= (int64_t)TSH_X_INORDER_MAX);
+  if (!overlap || x_inorder) return TSH_OK;
+  // (one tail queue serialises select + re-rank of consecutive queries: ~40 us per query, which is what short
+  // scans -- selective masks, small shards -- were then limited by)
+  static const bool one_tail = probe_env("TSH_ONE_TAIL") != nullptr && probe_env("TSH_ONE_TAIL")[0] == '1';
+  // (a small shard's two scan streams each have their tail queue: the scans of one stream end a scan's length
+  // apart, longer than a tail, so no tail queues behind another -- alternating blindly put two tails of
+  // near-simultaneous scan ends on one queue at the end of a call, 40 us in full view)
+  if (which >= 0 && !one_tail && s->tail_stream2) *out = which ? s->tail_stream2 : s->tail_stream;
+  else *out = (!one_tail && s->tail_stream2 && (s->tail_seq++ & 1)) ? s->tail_stream2 : s->tail_stream;
+  HIPCHK(hipStreamWaitEvent(*out, scanned, 0));
+  return TSH_OK;
+}
+
+// ---- which kernels run for a job ------------------------------------------------------------------------------------
+// The copies of what is new to the context, then the route's scan, all on ps
+// (short scans as ONE dispatch -- every workgroup scans its tiles, the one drawing the last ticket selects and
+// re-ranks -- were built in round 2 and measured slower than these three launches: C1 45 vs 37 us per call,
+// keep-1 % masks 11.8 k vs 23.8 k queries/s.  Removed in round 3)
+int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipStream_t ps, const LaunchEv &ev) {
+  Ctx *c = j->c;
+  if (j->up_mask)
+    HIPCHK(hipMemcpyAsync(c->d_mask, c->h_mask, (size_t)((s->rows + 63) / 64) * 8, hipMemcpyHostToDevice, ps));
+  if (j->up_list && !j->route.exact)
+    HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, (size_t)rq.mask.list.padded * sizeof(uint32_t), hipMemcpyHostToDevice, ps));
+  if (s->ld > SCAN_Q_INLINE)
+    HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, ps));
+  const int64_t rows_est = rq.mask.rows_est;
+  if (j->route.exact) launch_exact_scan(ka.xa, s->metric, ps, ev);
+  else if (j->route.use_list) launch_scan_list(ka.sa, s->nch, s->metric, ps, ev);
+  else if (j->f16) launch_scan_f16(ka.sa, s->nch, s->metric, ps, ev);
+  else
+    launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev,
+                j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows));
+  return TSH_OK;
+}
+
+// What follows the scan, on ts: the exact path's pick or select, or select + re-rank; then the quarantined rows the
+// mask keeps, if any.  The completion event rides on the last kernel's own dispatch packet unless more kernels follow
+// (a separate hipEventRecord is one more runtime call and one more barrier packet per query)
+// (short rows and lists, config C1: K2 + K4 as ONE dispatch, the selecting workgroup re-ranking its dozen
+// candidates a lane each, was tried -- 17 us against 9 + 4.4 for the two launches: the lone workgroup waits out
+// count -> candidate ids -> rows one after the other, which the second launch's ramp-up hides)
+int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
+  Ctx *c = j->c;
+  const bool quar = !j->quar_sel.empty();
+  const hipEvent_t none = nullptr, done = quar ? none : c->ev_done;
+  if (j->route.picked) {  // E2': one workgroup per 256 entries, a bound from E1's wave minima, no ranking below it
+    const ExactPickArgs xp = exact_pick_args(j->xsel, c);
+    TSH_LAUNCH_EV(exact_pick_kernel, (unsigned)((xp.n_entries + 255) / 256), 256, ts, none, done, xp);
+  } else if (j->route.exact) {
+    TSH_LAUNCH_EV(exact_select_kernel, 1, 1024, ts, none, done, j->xsel);
+  } else {
+    launch_select(ka.se, ka.se.n_tiles, ts);
+    TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, done, ka.ra);
+  }
+  if (!quar) return TSH_OK;
+  if (j->dev_target) launch_quarantine_append(s, c, j, ts);
+  else launch_quarantine(s, c, ts);
+  HIPCHK(hipEventRecord(c->ev_done, ts));
+  return TSH_OK;
+}
+
+int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
+  Ctx *c = j->c;
+  static thread_local JobArgs ka;  // ScanArgsQ, ExactArgsQ: 4 KiB each: keep them off the stack of deep callers
+  j->user_mask = rq.mask.words != nullptr;
+  j->masked = j->user_mask || !s->all_live;
+  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16);
+  float *q;
+  int rc = job_stage(s, j, rq, &ka, &q);
+  if (rc) return rc;
+  // (an eligible scan uses up a denial, if any are left, whatever its band)
+  const bool denied = r.f16_eligible && s->scan_f16_denied.load() > 0;
+  if (denied) s->scan_f16_denied.fetch_sub(1);
+  j->f16 = r.f16_eligible && !denied && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp);
+  if (j->f16) {
+    j->q_f16.assign(rq.query, rq.query + s->dim);
+    j->tag = rq.tag;
+  }
+  fill_job_args(s, j, rq, q, &ka);
   // with other queries already in flight -- or the caller about to submit more (the first query of a multi-query
   // call: left alone it kept its select + re-rank on the pipeline stream, in front of the call's third scan) -- the
   // tail moves to the reserved CUs; a lone query keeps everything in order on one stream (no hand-off latency)
-  const bool overlap = (s->inflight.fetch_add(1) > 0 || more_coming) && s->cu_split;
+  const bool overlap = (s->inflight.fetch_add(1) > 0 || rq.more_coming) && s->cu_split;
   j->counted = true;
   {
     std::lock_guard<std::mutex> lk(*s->scan_mu);
-    hipStream_t ps = s->scan_stream;
-    int which = -1;  // >= 0: one of the two scan streams of a small shard, booked in DeviceStreams::scan_out
-    {
-      // Between two scans on one in-order stream the GPU idles for about 13 us (drain, write-back,
-      // ramp-up).  That is 3 % of a 1 M-row scan but 20 % of a 125 k-row one (a shard of an 8-GPU
-      // index), so small shards alternate between two streams and the next scan's workgroups fill
-      // in as the previous one drains (+12 % queries/s at 125 k and 250 k rows).  The two scans
-      // then run side by side, so each one's own duration roughly doubles; large shards keep one
-      // stream, where a scan's duration is its HBM time.  TSH_SCAN_STREAMS=1 / 2 forces either.
-      static const int forced = probe_env("TSH_SCAN_STREAMS") ? atoi(probe_env("TSH_SCAN_STREAMS")) : 0;
-      // (a selective row mask makes a big shard's scan just as short: count the rows it keeps)
-      const int64_t tiles_read = rows_est > 0 ? std::min<int64_t>(n_tiles, (rows_est + 63) / 64) : n_tiles;
-      static const int min_tiles = probe_env("TSH_TWO_STREAM_MIN_TILES") ? atoi(probe_env("TSH_TWO_STREAM_MIN_TILES")) : 0;
-      const bool two = forced == 2 || (forced != 1 && tiles_read < SMALL_SHARD_TILES && tiles_read >= min_tiles);
-      if (overlap && two && s->scan_stream2) {
-        DeviceStreams *ds = s->dstreams;
-        for (size_t i = 0; i < ds->scan_out.size();) {  // scans that have finished since the last look
-          if (hipEventQuery(ds->scan_out[i].ev) != hipErrorNotReady) {
-            ds->scans_out[ds->scan_out[i].which]--;
-            ds->scan_out[i] = ds->scan_out.back();
-            ds->scan_out.pop_back();
-          } else {
-            ++i;
-          }
-        }
-        (void)hipGetLastError();  // (hipErrorNotReady is an answer, not an error)
-        which = ds->scans_out[0] != ds->scans_out[1] ? (ds->scans_out[1] < ds->scans_out[0] ? 1 : 0) : (int)(s->scan_seq++ & 1);
-        if (which) ps = s->scan_stream2;
-      }
-    }
-    if (upload_mask)
-      HIPCHK(hipMemcpyAsync(c->d_mask, c->h_mask, (size_t)n_tiles * 8, hipMemcpyHostToDevice, ps));
-    if (upload_list && !exact)
-      HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, (size_t)list->padded * sizeof(uint32_t), hipMemcpyHostToDevice, ps));
-    if (!inline_q)
-      HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, ps));
-    // (short scans as ONE dispatch -- every workgroup scans its tiles, the one drawing the last ticket selects and
-    // re-ranks -- were built in round 2 and measured slower than these three launches: C1 45 vs 37 us per call,
-    // keep-1 % masks 11.8 k vs 23.8 k queries/s.  Removed in round 3)
+    int which;
+    hipStream_t ps = pick_scan_stream(s, overlap, rq.mask.rows_est, &which), ts;
     j->timed = (s->c_scans.load() & 3) == 0;  // sample every 4th scan with timing events
     LaunchEv ev;  // start / stop ride on the scan's own packet: no barrier packets between scans
     if (j->timed) {
@@ -1418,127 +1581,20 @@ int job_enqueue(Shard *s, Job *j, const float *query, int32_t k, int32_t entries
     } else if (overlap) {
       ev.stop = c->ev_scanned;
     }
-    if (exact) launch_exact_scan(xa, s->metric, ps, ev);
-    else if (use_list) launch_scan_list(sa, s->nch, s->metric, ps, ev);
-    else if (f16) launch_scan_f16(sa, s->nch, s->metric, ps, ev);
-    else
-      launch_scan(sa, s->nch, s->metric, j->masked, ps, ev,
-                  j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows));
+    if ((rc = launch_job_scan(s, j, rq, ka, ps, ev))) return rc;
     if (which >= 0 && ev.stop) {
       s->dstreams->scan_out.push_back({c, ev.stop, which});
       s->dstreams->scans_out[which]++;
     }
-    hipStream_t ts = ps;
-    // (the last query of a call: nothing follows its scan on that stream, so its tail stays there -- in order, without
-    // the ~10 us of a cross-stream event hand-off in front of the select, on the step every caller waits for)
-    // (the exact path's select stays on its scan stream, in order behind its short scan, while the scan is short: no
-    // cross-stream hand-off, and the two scan streams alternate whole queries -- 64-query calls on 10 k x 128: 20.6 -> 16.2 us
-    // per query, 2 k x 768: 22 -> 16.7, 8 k x 768: 21 -> 18.4; from ~8 k rows of 768 on the tail queues win again: 16 k x
-    // 768 23 against 25; tools/r5_x_inorder.sh)
-#ifndef TSH_X_INORDER_MAX
-#define TSH_X_INORDER_MAX 6500000
-#endif
-    // (round 6: behind the wide pick -- 5-6 us, one workgroup per 256 entries -- the tail queues' 16 CUs and their
-    // cross-stream hand-off, ~10 us in front of the pick under load, never pay: 10 k x 768 in 64-query calls 18.5-23.9 ->
-    // 15.8-19.2 us per query, same box, alternating, tools/r6_inorder_ab.sh)
-    const bool x_inorder = exact && (j->picked || n_exam * s->ld <= (int64_t)TSH_X_INORDER_MAX);
-    if (overlap && !last_of_call && !x_inorder) {
-      // (one tail queue serialises select + re-rank of consecutive queries: ~40 us per query, which is what short
-      // scans -- selective masks, small shards -- were then limited by)
-      static const bool one_tail = probe_env("TSH_ONE_TAIL") != nullptr && probe_env("TSH_ONE_TAIL")[0] == '1';
-      // (a small shard's two scan streams each have their tail queue: the scans of one stream end a scan's length
-      // apart, longer than a tail, so no tail queues behind another -- alternating blindly put two tails of
-      // near-simultaneous scan ends on one queue at the end of a call, 40 us in full view)
-      if (which >= 0 && !one_tail && s->tail_stream2) ts = which ? s->tail_stream2 : s->tail_stream;
-      else ts = (!one_tail && s->tail_stream2 && (s->tail_seq++ & 1)) ? s->tail_stream2 : s->tail_stream;
-      HIPCHK(hipStreamWaitEvent(ts, ev.stop, 0));
-    }
-    // (short rows and lists, config C1: K2 + K4 as ONE dispatch, the selecting workgroup re-ranking its dozen
-    // candidates a lane each, was tried -- 17 us against 9 + 4.4 for the two launches: the lone workgroup waits out
-    // count -> candidate ids -> rows one after the other, which the second launch's ramp-up hides)
+    if ((rc = pick_tail_stream(s, r, overlap && !rq.last_of_call, which, ps, ev.stop, &ts))) return rc;
     j->last_stream = ts;
     j->enq_seq = ++s->dstreams->enq_counter;
-    // the completion event rides on the last kernel's own dispatch packet unless more kernels follow (a separate
-    // hipEventRecord is one more runtime call and one more barrier packet per query)
-    bool done_recorded = false;
-    if (exact) {
-      ExactSelArgs xs{};
-      xs.xkey = c->d_xkey;
-      xs.xsum = c->d_xsum;
-      xs.list = j->d_list;
-      xs.hdr = se.hdr;
-      xs.hdr_host = se.hdr_host;
-      xs.out = ra.out;
-      xs.row_base = s->row_base;
-      xs.shard_rows = s->rows;
-      xs.n_entries = xa.a.n_entries;
-      xs.k = k;
-      xs.cap = entries;
-      xs.metric = s->metric;
-      xs.tag = tag;
-      j->xsel = xs;
-      if (j->picked) {  // E2': one workgroup per 256 entries, a bound from E1's wave minima, no ranking below it
-        ExactPickArgs xp{};
-        xp.xkey = xs.xkey;
-        xp.xsum = xs.xsum;
-        xp.list = xs.list;
-        xp.wmin = c->d_xpick + 1;
-        xp.ctr = reinterpret_cast<unsigned long long *>(c->d_xpick);
-        xp.hdr = xs.hdr;
-        xp.hdr_host = xs.hdr_host;
-        xp.out = xs.out;
-        xp.row_base = xs.row_base;
-        xp.shard_rows = xs.shard_rows;
-        xp.n_entries = xs.n_entries;
-        xp.n_groups = (xs.n_entries + EX_R - 1) / EX_R;
-        xp.k = k;
-        xp.cap = entries;
-        xp.metric = s->metric;
-        xp.tag = tag;
-        const unsigned pg = (unsigned)((xs.n_entries + 255) / 256);
-        if (j->quar_sel.empty()) {
-          hipExtLaunchKernelGGL(exact_pick_kernel, dim3(pg), dim3(256), 0, ts, nullptr, c->ev_done, 0, xp);
-          done_recorded = true;
-        } else {
-          exact_pick_kernel<<<pg, 256, 0, ts>>>(xp);
-        }
-      } else if (j->quar_sel.empty()) {
-        hipExtLaunchKernelGGL(exact_select_kernel, dim3(1), dim3(1024), 0, ts, nullptr, c->ev_done, 0, xs);
-        done_recorded = true;
-      } else {
-        exact_select_kernel<<<1, 1024, 0, ts>>>(xs);
-      }
-    } else {
-      launch_select(se, se.n_tiles, ts);
-      if (j->quar_sel.empty()) {
-        hipExtLaunchKernelGGL(rerank_kernel, dim3((unsigned)std::min(entries, 1024)), dim3(64), 0, ts, nullptr, c->ev_done, 0, ra);
-        done_recorded = true;
-      } else {
-        rerank_kernel<<<std::min(entries, 1024), 64, 0, ts>>>(ra);
-      }
-    }
-    if (!j->quar_sel.empty() && dev_target) {
-      launch_quarantine_append(s, c, j, ts);
-    } else if (!j->quar_sel.empty()) {
-      QuarArgs qa{};
-      qa.rows = s->d_rows;
-      qa.Q = c->d_query;
-      qa.list = s->d_quar;
-      qa.out = c->h_quar_dev;
-      qa.ld = s->ld;
-      qa.ldq = s->ld;
-      qa.row_base = s->row_base;
-      qa.dim = s->dim;
-      qa.cap = (int32_t)QUARANTINE_MAX;
-      qa.metric = s->metric;
-      quarantine_kernel<<<dim3((unsigned)((s->quar_ids.size() + 63) / 64), 1), 64, 0, ts>>>(qa);
-    }
-    if (!done_recorded) HIPCHK(hipEventRecord(c->ev_done, ts));
+    if ((rc = launch_job_tail(s, j, ka, ts))) return rc;
   }
   s->c_scans++;
-  if (use_list) s->c_list_scans++;
-  if (exact) s->c_exact_scans++;
-  if (f16) s->c_f16_scans++;
+  if (r.use_list) s->c_list_scans++;
+  if (r.exact) s->c_exact_scans++;
+  if (j->f16) s->c_f16_scans++;
   return TSH_OK;
 }
 
@@ -1572,8 +1628,8 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
   Ctx *c = j->c;
   hipStream_t st = s->aux_stream;
   // (a list scan left its keys in list order: fewer keys, and the filter maps positions back to row ids)
-  const int64_t n_keys = j->list_tiles > 0 ? (int64_t)j->list_tiles * 64 : ((s->rows + 63) / 64) * 64;
-  const uint32_t *list = j->list_tiles > 0 ? j->d_list : nullptr;
+  const int64_t n_keys = j->route.use_list ? j->route.n_exam : ((s->rows + 63) / 64) * 64;
+  const uint32_t *list = j->route.use_list ? j->d_list : nullptr;
   if (s->cap > c->big_cap) {
     hipFree(c->d_big_rows);
     hipFree(c->d_big_entries);
@@ -1585,7 +1641,8 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
     c->big_cap = s->cap;
   }
   int fgrid = (int)std::min<int64_t>((n_keys + 255) / 256, 4096);
-  if (band_key >= KEY_NAN && !j->force_all && j->k < n_keys) {
+  const Band &band = j->route.band;
+  if (band_key >= KEY_NAN && !band.force_all && j->k < n_keys) {
     // K2 could not bound the k-th key (k beyond its tile-minimum scheme, or fewer than k live tiles and a full
     // list): find the exact k-th smallest key with a 4-pass radix select over all keys -- 4 small kernels and
     // host round trips instead of an f64 rerank of every row (k = 2000 on 1 M rows: 0.9 ms instead of 9)
@@ -1611,7 +1668,7 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
         prefix |= (uint32_t)b << shift;
       }
     }
-    if (found) band_key = h_band_of(prefix, j->eps_rel, j->delta_abs);
+    if (found) band_key = h_band_of(prefix, band.eps_rel, band.delta_abs);
   }
   HIPCHK(hipMemsetAsync(c->d_big_count, 0, 4, st));
   filter_kernel<<<fgrid, 256, 0, st>>>(c->d_keys, c->d_gmin, n_keys, band_key, c->d_big_rows, c->d_big_count,
@@ -1619,17 +1676,8 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
   uint32_t count = 0;
   HIPCHK(hipMemcpyAsync(&count, c->d_big_count, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  RerankArgs ra{};
-  ra.rows = s->d_rows;
-  ra.query = c->d_query;
-  ra.cand_rows = c->d_big_rows;
-  ra.count_ptr = c->d_big_count;
-  ra.out = c->d_big_entries;
-  ra.ld = s->ld;
-  ra.row_base = s->row_base;
-  ra.dim = s->dim;
-  ra.cap = (int32_t)std::min<int64_t>(c->big_cap, 0x7FFFFFFF);
-  ra.metric = s->metric;
+  const RerankArgs ra = rerank_args(s, c, c->d_big_rows, c->d_big_count, c->d_big_entries,
+                                    (int32_t)std::min<int64_t>(c->big_cap, 0x7FFFFFFF));
   if (count > 0) {
     int rgrid = (int)std::min<uint32_t>(count, 16384u);
     rerank_kernel<<<rgrid, 64, 0, st>>>(ra);
@@ -1685,8 +1733,12 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
         s->scan_f16_denied.store(SCAN_F16_DENIED_SCANS);
       }
       const std::vector<float> q(j->q_f16);
-      int rc = job_enqueue(s, j, q.data(), j->k, j->entries, nullptr, 0, j->dev_target, 0, nullptr, false, true, j->tag, nullptr,
-                           /*no_f16=*/true);
+      JobReq rq(q.data(), j->k, j->entries);  // (an fp16 scan had no mask)
+      rq.dev_target = j->dev_target;
+      rq.last_of_call = true;
+      rq.tag = j->tag;
+      rq.no_f16 = true;
+      int rc = job_enqueue(s, j, rq);
       if (j->counted) {
         s->inflight.fetch_sub(1);
         j->counted = false;
@@ -1707,19 +1759,19 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   }
   BlockHeader *h = reinterpret_cast<BlockHeader *>(c->h_block);
 #ifdef TSH_PROBES
-  if (j->exact && probe_env("TSH_X2_TRACE"))
+  if (j->route.exact && probe_env("TSH_X2_TRACE"))
     fprintf(stderr, "[x2] keys %.2f select %.2f entries %.2f us, %u histogram rounds, %u ranked, %u out adds %.2f scan %.2f\n", h->tau_key * 0.01,
             h->band_key * 0.01, h->tiles_hit * 0.01, h->pad[2], h->pad[3], h->count, (h->pad[0] >> 16) * 0.01, (h->pad[0] & 0xFFFF) * 0.01);
 #endif
   if ((h->flags & FLAG_LIST_OVERFLOW) && j->leave_overflow && j->dev_target) {
     s->c_cands += std::min(h->count, h->entries);  // (the block stays as it is: see Job::leave_overflow)
-  } else if ((h->flags & FLAG_LIST_OVERFLOW) && j->exact) {
+  } else if ((h->flags & FLAG_LIST_OVERFLOW) && j->route.exact) {
     // The wide pick emits every row up to its cut bin: ties by the hundred, or a k-th neighbour outside the histogram's
     // window, and the bin holds more rows than the block.  The keys and sums of all entries are still in the context:
     // exact_select_kernel ranks them and writes exactly min(k, live rows) entries -- into a block exact_applies sized for
     // k, so THAT cannot overflow (should the invariant ever slip: an error, never the wide-band pass, for which the
     // context holds no f32 keys).
-    if (!j->picked) return set_err(TSH_E_HIP, "the exact path's block overflowed (%u of %u entries): internal error", h->count, h->entries);
+    if (!j->route.picked) return set_err(TSH_E_HIP, "the exact path's block overflowed (%u of %u entries): internal error", h->count, h->entries);
     hipStream_t st = s->aux_stream;
     exact_select_kernel<<<1, 1024, 0, st>>>(j->xsel);
     if (!j->quar_sel.empty() && j->dev_target) launch_quarantine_append(s, c, j, st);  // (the block's count was rewritten)
@@ -1781,9 +1833,8 @@ struct SearchOut {
 // One submitting thread's share of a multi-query call: queries [q0, q1) of the call, at most
 // `depth` of them in flight on separate contexts so one query's select / rerank / copies hide
 // behind the next query's scan.
-int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, int32_t k, const uint64_t *mask_words,
-                       uint64_t epoch, int32_t entries, SearchOut *out, int depth, int64_t rows_est,
-                       const RowList *list = nullptr, int32_t stride = 1, const MaskPart *mp = nullptr) {
+int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, int32_t k, const ShardMask &mask,
+                       int32_t entries, SearchOut *out, int depth, int32_t stride = 1) {
   // this thread's queries: q0, q0 + stride, ... below q1 (cnt of them; i-th = q0 + i * stride)
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
   const int32_t cnt = q1 > q0 ? (q1 - q0 + stride - 1) / stride : 0;
@@ -1811,9 +1862,13 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       j.c = c;
       j.leave_overflow = out->leave_overflow;
       const int32_t q = q0 + submitted * stride;
-      rc = job_enqueue(s, &j, queries + (size_t)q * s->dim, k, entries, mask_words, epoch,
-                       out->d_blocks ? out->d_blocks + (size_t)q * bb : nullptr, rows_est, list, cnt > 1,
-                       cnt > 1 && submitted == cnt - 1, out->tag, mp);
+      JobReq rq(queries + (size_t)q * s->dim, k, entries);
+      rq.mask = mask;
+      rq.dev_target = out->d_blocks ? out->d_blocks + (size_t)q * bb : nullptr;
+      rq.more_coming = cnt > 1;
+      rq.last_of_call = cnt > 1 && submitted == cnt - 1;
+      rq.tag = out->tag;
+      rc = job_enqueue(s, &j, rq);
       if (rc) {
         release_all();
         return rc;
@@ -1845,41 +1900,17 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
 // Caller holds s->mu shared.
 int shard_search_blocks(Shard *s, const float *queries, int32_t nq, int32_t k, const MaskSrc &mask,
                         int32_t entries, SearchOut *out, int depth) {
-  const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
   // (the calling thread's buffers, kept between calls: a lone masked query does not pay for two allocations)
   static thread_local std::vector<uint64_t> mask_words;
   static thread_local std::vector<uint32_t> list_ids;
-  uint64_t epoch = 0;
-  int64_t rows_est = 0;
-  const MaskPart *mp = mask.part;
-  RowList list;
-  if (mp) {  // a handle: sliced, counted and listed when it was made -- nothing to do per call
-    rows_est = std::max<int64_t>(mp->kept, 1);
-    if (mp->list_padded > 0 && row_list_pays(s, mp->kept, k, entries)) {
-      list.d_ids = mp->d_list;
-      list.padded = mp->list_padded;
-    }
-  } else if (mask) {
-    if (mask_words.size() < (size_t)n_tiles) mask_words.resize((size_t)n_tiles);
-    slice_mask(s, mask.bytes, mask_words.data(), n_tiles);
-    epoch = s->mask_epoch_src.fetch_add(1);
-    // one pass over the mask per call: how long will each scan be?  (decides one- or two-stream pipelining)
-    rows_est = popcount_words(mask_words.data(), (size_t)n_tiles);
-    if (rows_est == 0) rows_est = 1;
-    // (made here once for all queries of the call)
-    if (build_row_list(s, mask_words.data(), n_tiles, rows_est, k, entries, &list_ids)) {
-      list.ids = list_ids.data();
-      list.padded = (int32_t)list_ids.size();
-    }
-  }
-  const RowList *lp = (list.ids || list.d_ids) ? &list : nullptr;
-  const uint64_t *mw = mp ? mp->h_words.data() : (mask ? mask_words.data() : nullptr);
+  // (made here once for all queries of the call)
+  const ShardMask m = resolve_mask(s, mask, k, entries, &mask_words, &list_ids);
   // short scans (small shards, selective masks) are bound by the submitting thread's ~25 us per query: two threads
-  const int64_t scan_bytes = (rows_est > 0 ? rows_est : s->rows) * s->ld * 4;
+  const int64_t scan_bytes = (m.rows_est > 0 ? m.rows_est : s->rows) * s->ld * 4;
   static const int forced_threads = probe_env("TSH_SUBMIT_THREADS") ? atoi(probe_env("TSH_SUBMIT_THREADS")) : 0;
   const int want = forced_threads > 0 ? forced_threads : (scan_bytes <= (160ll << 20) ? 2 : SUBMIT_THREADS);
   const int T = std::min(want, nq / 8);
-  if (T <= 1) return shard_search_slice(s, queries, 0, nq, k, mw, epoch, entries, out, depth, rows_est, lp, 1, mp);
+  if (T <= 1) return shard_search_slice(s, queries, 0, nq, k, m, entries, out, depth);
   std::vector<int> rcs((size_t)T, TSH_OK);
   std::vector<std::string> errs((size_t)T);
   const int per_depth = std::max(2, depth / T);
@@ -1887,8 +1918,7 @@ int shard_search_blocks(Shard *s, const float *queries, int32_t nq, int32_t k, c
   auto run = [&](int t) {
     const int32_t q0 = interleave ? t : (int32_t)((int64_t)nq * t / T);
     const int32_t q1 = interleave ? nq : (int32_t)((int64_t)nq * (t + 1) / T);
-    rcs[(size_t)t] = shard_search_slice(s, queries, q0, q1, k, mw, epoch, entries, out, per_depth, rows_est, lp,
-                                        interleave ? T : 1, mp);
+    rcs[(size_t)t] = shard_search_slice(s, queries, q0, q1, k, m, entries, out, per_depth, interleave ? T : 1);
     if (rcs[(size_t)t]) errs[(size_t)t] = g_err;
   };
   std::vector<std::thread> th;
@@ -2599,32 +2629,15 @@ static int32_t submit_impl(tsh_index *idx, const float *query, int32_t k, const 
     t->jobs[g].c = c;
     std::vector<uint64_t> words;
     std::vector<uint32_t> list_ids;  // (job_enqueue copies what it keeps of either before it returns)
-    RowList list;
-    int64_t rows_est = 0;
-    uint64_t epoch = 0;
-    const MaskPart *mp = nullptr;
+    MaskSrc src(row_mask);
     if (mask_h) {
-      mp = mask_part(mask_h, g, s, &rc);
+      const MaskPart *mp = mask_part(mask_h, g, s, &rc);
       if (!mp) break;
-      rows_est = std::max<int64_t>(mp->kept, 1);
-      if (mp->list_padded > 0 && row_list_pays(s, mp->kept, k, t->entries)) {
-        list.d_ids = mp->d_list;
-        list.padded = mp->list_padded;
-      }
-    } else if (row_mask) {
-      int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
-      words.resize((size_t)n_tiles);
-      slice_mask(s, row_mask, words.data(), n_tiles);
-      epoch = s->mask_epoch_src.fetch_add(1);
-      rows_est = popcount_words(words.data(), words.size());
-      if (rows_est == 0) rows_est = 1;
-      if (build_row_list(s, words.data(), n_tiles, rows_est, k, t->entries, &list_ids)) {  // a selective mask: its rows as a list
-        list.ids = list_ids.data();
-        list.padded = (int32_t)list_ids.size();
-      }
+      src = MaskSrc(mp);
     }
-    rc = job_enqueue(s, &t->jobs[g], query, k, t->entries, mp ? mp->h_words.data() : (row_mask ? words.data() : nullptr),
-                     epoch, nullptr, rows_est, (list.ids || list.d_ids) ? &list : nullptr, false, false, 0, mp);
+    JobReq rq(query, k, t->entries);
+    rq.mask = resolve_mask(s, src, k, t->entries, &words, &list_ids);
+    rc = job_enqueue(s, &t->jobs[g], rq);
   }
   if (rc != TSH_OK) {
     std::string keep = g_err;
@@ -3117,6 +3130,12 @@ int32_t tsh_get_counters(tsh_index *idx, tsh_counters *out) {
   return TSH_OK;
 }
 
+struct CtxHold {  // a measurement / probe entry's context, given back when it returns
+  Shard *s;
+  Ctx *c;
+  ~CtxHold() { ctx_release(s, c); }
+};
+
 int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const uint8_t *row_mask,
                        double *out_avg_us) {
   if (!idx || idx->shards.size() != 1 || !query || iters <= 0 || !out_avg_us)
@@ -3125,61 +3144,49 @@ int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const 
   std::shared_lock<RwLock> sl = share(idx, s);
   if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
   Ctx *c = ctx_acquire(s, true);
-  struct Rel {
-    Shard *s;
-    Ctx *c;
-    ~Rel() { ctx_release(s, c); }
-  } rel{s, c};
-  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), row_mask != nullptr);
+  CtxHold rel{s, c};
+  // the kernel a search with this mask would run: a search's mask resolution and route, for k = 100 and its default block
+  const int32_t k = 100, entries = tsh_default_block_entries(k);
+  int rc = ctx_prepare(s, c, entries, row_mask != nullptr);
   if (rc) return rc;
   hipStream_t st = s->aux_stream;
-  bool masked = row_mask != nullptr || !s->all_live;
-  int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
-  if (row_mask) {
-    slice_mask(s, row_mask, c->h_mask, n_tiles);
+  std::vector<uint64_t> words;
+  std::vector<uint32_t> list_ids;
+  const ShardMask m = resolve_mask(s, MaskSrc(row_mask), k, entries, &words, &list_ids);
+  const bool masked = m.words != nullptr || !s->all_live;
+  const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
+  if (m.words) {
+    memcpy(c->h_mask, m.words, (size_t)n_tiles * 8);
     HIPCHK(hipMemcpyAsync(c->d_mask, c->h_mask, (size_t)n_tiles * 8, hipMemcpyHostToDevice, st));
     c->mask_epoch = 0;
   }
   memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
   for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
   HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
-  static thread_local ScanArgsQ sa;
-  fill_scan_args(s, c, masked, row_mask != nullptr, &sa);
-  int64_t live_rows = s->rows - s->deleted;
-  if (row_mask) {
-    live_rows = 0;
-    live_rows = popcount_words(c->h_mask, (size_t)n_tiles);
-  }
-  const bool ml = masked && scan_mostly_live(live_rows, s->rows);
-  std::vector<uint32_t> list_ids;  // the kernel a search with this mask would run: the list scan for selective ones
-  const bool use_list = row_mask && build_row_list(s, c->h_mask, n_tiles, live_rows, 100, tsh_default_block_entries(100), &list_ids);
-  if (use_list) {
-    if ((rc = ctx_reserve_list(c, (int64_t)list_ids.size()))) return rc;
-    memcpy(c->h_list, list_ids.data(), list_ids.size() * sizeof(uint32_t));
+  const Route r = choose_route(s, m, masked, k, entries, c->h_query, false);
+  if (r.use_list) {
+    if ((rc = ctx_reserve_list(c, m.list.padded))) return rc;
+    memcpy(c->h_list, m.list.ids, (size_t)m.list.padded * sizeof(uint32_t));
     c->list_epoch = 0;
-    HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, list_ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    sa.a.list = c->d_list;
-    sa.a.n_tiles = (int32_t)(list_ids.size() / 64);
+    HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, (size_t)m.list.padded * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
-  // (a search with few enough rows to look at takes their exact sums instead: that kernel, then)
-  const int64_t n_exam = use_list ? (int64_t)list_ids.size() : s->rows;
-  const bool exact = exact_applies(s, n_exam, 100, tsh_default_block_entries(100));
+  const bool ml = masked && scan_mostly_live(m.rows_est > 0 ? m.rows_est : s->rows - s->deleted, s->rows);
+  const uint32_t *d_list = r.use_list ? c->d_list : nullptr;
+  static thread_local ScanArgsQ sa;
   static thread_local ExactArgsQ xa;
-  if (exact) {
-    if ((rc = ctx_reserve_exact(c, n_exam))) return rc;
-    fill_exact_args(s, c, use_list, row_mask && !use_list, n_exam, c->h_query, &xa);
-  }
-  // (... and a dense scan of a big shard reads the fp16 copy: the routing of job_enqueue, but for the denial counter)
   bool f16 = false;
-  int v_exp = 0;
-  if (!exact && !use_list && !masked && scan_f16_applies(s, &v_exp) && !compute_band(s, c->h_query).force_all) {
-    const ScanF16Band fb = scan_f16_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, v_exp);
-    f16 = fb.ok && rows16_ensure(s, st, v_exp);
-    if (f16) fill_scan_f16_args(s, fb, &sa, nullptr);
+  if (r.exact) {  // (no wave minima: the scan alone is timed, nothing picks behind it)
+    if ((rc = ctx_reserve_exact(c, r.n_exam))) return rc;
+    fill_exact_args(s, c, m.words && !r.use_list ? c->d_mask : nullptr, d_list, r.n_exam, c->h_query, &xa);
+  } else {
+    fill_scan_args(s, c, m.words ? c->d_mask : nullptr, d_list, m.list.padded, &sa);
+    // (the denial counter is a search's business: the hook neither reads nor consumes it)
+    f16 = r.f16_eligible && r.fb.ok && rows16_ensure(s, st, r.v_exp);
+    if (f16) fill_scan_f16_args(s, r.fb, &sa, nullptr);
   }
   auto launch = [&]() {
-    if (exact) launch_exact_scan(xa, s->metric, st, LaunchEv());
-    else if (use_list) launch_scan_list(sa, s->nch, s->metric, st);
+    if (r.exact) launch_exact_scan(xa, s->metric, st, LaunchEv());
+    else if (r.use_list) launch_scan_list(sa, s->nch, s->metric, st);
     else if (f16) launch_scan_f16(sa, s->nch, s->metric, st);
     else launch_scan(sa, s->nch, s->metric, masked, st, LaunchEv(), ml);
   };
@@ -3302,11 +3309,7 @@ int32_t tsh_probe_scan_keys(tsh_index *idx, const float *query, float *out_keys,
   std::shared_lock<RwLock> sl = share(idx, s);
   if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
   Ctx *c = ctx_acquire(s, true);
-  struct Rel {
-    Shard *s;
-    Ctx *c;
-    ~Rel() { ctx_release(s, c); }
-  } rel{s, c};
+  CtxHold rel{s, c};
   int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
   if (rc) return rc;
   hipStream_t st = s->aux_stream;
@@ -3317,7 +3320,7 @@ int32_t tsh_probe_scan_keys(tsh_index *idx, const float *query, float *out_keys,
   HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
   static thread_local ScanArgsQ sa;
   const bool masked = !s->all_live;
-  fill_scan_args(s, c, masked, false, &sa);
+  fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
   launch_scan(sa, s->nch, s->metric, masked, st);
   std::vector<uint32_t> keys((size_t)s->rows);
   HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
@@ -3350,11 +3353,7 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
   std::shared_lock<RwLock> sl = share(idx, s);
   if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
   Ctx *c = ctx_acquire(s, true);
-  struct Rel {
-    Shard *s;
-    Ctx *c;
-    ~Rel() { ctx_release(s, c); }
-  } rel{s, c};
+  CtxHold rel{s, c};
   int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
   if (rc) return rc;
   hipStream_t st = s->aux_stream;
@@ -3368,7 +3367,7 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
   if (!rows16_ensure(s, st, v_exp)) return set_err(TSH_E_OOM, "no room on the device for the fp16 copy of the rows");
   HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
   static thread_local ScanArgsQ sa;
-  fill_scan_args(s, c, false, false, &sa);
+  fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
   fill_scan_f16_args(s, fb, &sa, nullptr);
   launch_scan_f16(sa, s->nch, s->metric, st);
   std::vector<uint32_t> keys((size_t)s->rows);
