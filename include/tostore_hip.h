@@ -46,7 +46,8 @@ extern "C" {
  *    that lives on the device across queries; tsh_index_open_ngh_shard (a rank cold-starts its own row range);
  *    tsh_ngh_info grew (row_base, row_end); tsh_comm_timeline's sampled fields are scaled by exchanges / timed
  *    exchanges instead of a constant.
- *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys. */
+ *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
+ *    TSH_OPT_SCAN_F16_MASKED. */
 
 /* status codes */
 #define TSH_OK 0
@@ -525,10 +526,12 @@ int32_t tsh_probe_batch_row_band(tsh_index *idx, int32_t nq, float *out_alpha2, 
 /* tsh_probe_scan_f16_keys: the fp16 scan's (TSH_OPT_SCAN_F16) stored key of every row -- the UPPER side key + w of the
  * row's band -- and that band w: |out_keys[i] - out_w[i] - exact_i| <= out_w[i] with exact = |v|^2 - 2 q.v (L2: the
  * common |q|^2 is left out), -q.v, -q.v / |v|.  An error when the index or the query is not eligible for that scan.
+ * On an index with dead rows (tombstones, quarantined rows, gaps: TSH_OPT_SCAN_F16_MASKED must allow the scan)
+ * out_keys[i] is NaN for every row that is not live; out_w[i] is still the row's band.
  * tsh_probe_scan_keys keeps probing the f32 kernel. */
 int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_keys, float *out_w);
 /* The fp16 scan's own counters (tsh_counters keeps its layout), summed over the shards: out[0] = scans launched over
- * the fp16 copy, out[1] = of those, queries whose candidate list overflowed and that were redone through the f32 scan,
+ * the fp16 copy (dense and masked ones alike), out[1] = of those, queries whose candidate list overflowed and that were redone through the f32 scan,
  * out[2] = rows converted into the copy so far, out[3] = bytes of the copy resident now (part of bytes_resident). */
 int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out);
 
@@ -603,6 +606,13 @@ int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out);
  * alpha |v| + beta; a query whose candidate list overflows on them is redone through the f32 scan, and two such queries
  * in a row move the index's next 256 eligible scans to f32.  Results are identical either way. */
 #define TSH_OPT_SCAN_F16 8
+/* TSH_OPT_SCAN_F16_MASKED (default 1): the same for single-query tile scans that are NOT dense -- behind a caller's row
+ * mask (pointer or handle; masks selective enough for the list scan or the exact path keep those), tombstones,
+ * quarantined rows or gaps of absent ids: only the live rows' halves are read, and a query redone through the f32 scan
+ * keeps its mask.  0 = never; 1 = auto: shards whose row store is larger than 256 MiB; 2 = every eligible masked scan
+ * whatever the size (tests, A/B runs).  TSH_OPT_SCAN_F16 = 0 switches both routes off; its value 2 does not force this
+ * one.  Results are identical either way; the scans count in tsh_scan_f16_stats. */
+#define TSH_OPT_SCAN_F16_MASKED 9
 /* TSH_OPT_TEST_HOOKS (process-wide; idx is ignored and may be NULL): value TSH_TEST_HOOKS_MAGIC switches the
  * library's TEST hooks on, 0 off.  Only then does it read the environment variables that change what it loads or make
  * it fail on purpose -- TSH_RCCL_LIB (a stand-in for librccl: tests/fake_rccl), TSH_TEST_FAIL_ALLOC_OVER (device

@@ -295,6 +295,12 @@ class HipVectorIndex:
         whose row store is larger than 256 MiB), 2 every eligible scan whatever the size.  Results are identical."""
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_F16, int(mode)))
 
+    def set_scan_f16_masked(self, mode: int) -> None:
+        """The same for tile scans behind a row mask, tombstones, quarantined rows or gaps of absent ids: 0 never, 1 auto
+        (default: shards whose row store is larger than 256 MiB), 2 every eligible masked scan whatever the size.
+        set_scan_f16(0) switches both off.  Results are identical."""
+        _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_F16_MASKED, int(mode)))
+
     def scan_f16_stats(self) -> dict:
         """The fp16 scan's counters: scans launched, queries redone through the f32 scan, rows converted, copy bytes."""
         out = (ctypes.c_int64 * 4)()

@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_kernel(ScanArgsQ aq) {
 }
 
 // ---------------------------------------------------------------------------
-// K1 over the fp16 copy of the rows (dense, unmasked, all-live scans of big shards): half the HBM bytes per query.
+// K1 over the fp16 copy of the rows (big shards' tile scans, dense or MASKED): half the HBM bytes per query.
 // scan_kernel's structure -- one wave per 64-row tile, two register buffers with the next group in flight, the
 // same fences and butterfly -- with 8-byte loads per lane: a lane holds the same four ELEMENTS of a chunk as in the
 // f32 kernel (chunk = 256 elements = 512 contiguous bytes per wave instruction), so NCH, FULL, the query registers
@@ -333,13 +333,17 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_kernel(ScanArgsQ aq) {
 //   cosine  key = -(acc / S) / |v_i|
 // and what is STORED is the upper side key + w_i of the band |key - exact| <= w_i = w_alpha |v_i| + w_beta that the
 // host proved for this query (tsh_scan_f16_band.h).  select_body then runs on upper sides.
+// MASKED is scan_kernel's: a tile's word is live & caller mask, only its live rows are loaded (in 8-row batches over
+// the compacted slots), dead lanes store KEY_DEAD and a dead tile only its gmin.  The band is per row and the norm
+// bounds cover every row ever ingested, so nothing of the error model depends on which rows are live; |row|^2 and
+// 1/|row| are read for live rows only (a quarantined row's are not finite, an absent row's were never written).
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float scan_f16_w(float alpha, float beta, float sqnorm) {
   return __builtin_fmaf(alpha, __builtin_sqrtf(sqnorm), beta);
 }
 
-template <int NCH, int METRIC, bool FULL, int R, int WAVES, int MINW>
+template <int NCH, int METRIC, bool FULL, bool MASKED, int R, int WAVES, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) scan_f16_kernel(ScanArgsQ aq) {
   static_assert(R == 2 || R == 4, "R must give an even number of groups per 8-row batch");
   const ScanArgs &a = aq.a;
@@ -376,14 +380,41 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_f16_kernel(ScanArgsQ aq
         *reinterpret_cast<f32x4 *>(a.query_out + 4 * lane + c * 256) = q[c];
   }
 
-  for (int t = (int)blockIdx.x * wpb + wave; t < a.n_tiles; t += stride) {
+  // (masked scans hand consecutive tiles to different workgroups: see scan_kernel)
+  for (int t = MASKED ? wave * (int)gridDim.x + (int)blockIdx.x : (int)blockIdx.x * wpb + wave; t < a.n_tiles;
+       t += stride) {
     const _Float16 *tbase = rows16 + (int64_t)t * 64 * a.ld + 4 * lane;
+    uint64_t bits = ~0ull;
+    int cnt = 64;
+    if (MASKED) {
+      uint64_t w = a.live[t];
+      if (a.mask) w &= a.mask[t];
+      uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)w);
+      uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(w >> 32));
+      bits = ((uint64_t)hi << 32) | lo;
+      cnt = __popcll(bits);
+      if (cnt == 0) {
+        if (lane == 0) a.gmin[t] = KEY_DEAD;  // (keys[] of a dead tile stay stale: every reader checks gmin first)
+        continue;
+      }
+    }
+    const int nb = MASKED ? (cnt + 7) >> 3 : 8;  // 8-row batches, wave-uniform
     f16x4 v[2][R][NCH];
-    int next_dense = 0;
+    uint64_t rem = bits;
+    int last = 0, next_dense = 0;
     auto load_group = [&](int buf) {
 #pragma unroll
       for (int j = 0; j < R; ++j) {
-        const int r = next_dense++;
+        int r;
+        if (MASKED) {  // next live row (a short last batch repeats the final row)
+          if (rem) {
+            last = __builtin_ctzll(rem);
+            rem &= rem - 1;
+          }
+          r = last;
+        } else {
+          r = next_dense++;
+        }
         if (FULL) {
           const _Float16 *rp = tbase + (int64_t)r * a.ld;
 #pragma unroll
@@ -428,11 +459,21 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_f16_kernel(ScanArgsQ aq
       if ((lane >> 3) == b) val = o;
     };
 #pragma nounroll
-    for (int b = 0; b < 7; ++b) batch(b, std::false_type{});
-    batch(7, std::true_type{});
+    for (int b = 0; b < nb - 1; ++b) batch(b, std::false_type{});
+    batch(nb - 1, std::true_type{});
+    // dense: val = dot product of row t*64+lane; masked: of the lane-th live row
 
     const int64_t row = (int64_t)t * 64 + lane;
-    const bool alive = row < a.n;
+    bool alive;
+    if (MASKED) {
+      // expand compact slots back to row positions
+      uint64_t below = bits & ((1ull << lane) - 1ull);
+      int rank = __popcll(below);
+      val = __shfl(val, rank);
+      alive = (bits >> lane) & 1ull;
+    } else {
+      alive = row < a.n;
+    }
     const float dot = val * a.inv_scale;
     float x, w;
     if (METRIC == METRIC_COS) {

@@ -31,10 +31,12 @@ inline bool scan_mostly_live(int64_t live_rows, int64_t rows) { return live_rows
 bool scan_list_supported(int nch, int64_t ld);
 void launch_scan_list(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev = LaunchEv());
 
-// K1 over the fp16 copy of the rows (a.a.rows16 and the band fields of ScanArgs set): dense, unmasked scans of rows of at
-// least 256 elements, a multiple of 8 (scan_f16_supported).  tsh_scan_tu.hip
+// K1 over the fp16 copy of the rows (a.a.rows16 and the band fields of ScanArgs set): tile scans, dense or masked, of
+// rows of at least 256 elements, a multiple of 8 (scan_f16_supported).  masked / mostly_live: launch_scan's.
+// tsh_scan_tu.hip
 bool scan_f16_supported(int nch, int dim);
-void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev = LaunchEv());
+void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev = LaunchEv(),
+                     bool mostly_live = false);
 
 // batched key pass (f32 MFMA / bf16x3 / f16 by a.Vs and a.dot_scale).  cus: compute units of the device the stream
 // belongs to (the persistent f16 kernels run one workgroup per CU).  tsh_batch_tu.hip

@@ -466,6 +466,8 @@ struct Shard {
   bool rows16_denied = false;  // the copy did not fit on the device: f32 scans until the row store is reallocated
   std::mutex rows16_mu;
   int scan_f16 = 1;  // TSH_OPT_SCAN_F16: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible dense scan
+  int scan_f16_masked = 1;  // TSH_OPT_SCAN_F16_MASKED: the same three for tile scans behind a mask, tombstones, quarantined
+                            // rows or gaps (none of them while scan_f16 == 0)
   std::atomic<int64_t> c_f16_scans{0}, c_f16_redone{0}, c_f16_converted{0};
   std::atomic<int> scan_f16_strikes{0};  // fp16 scans in a row whose candidate list overflowed
   std::atomic<int> scan_f16_denied{0};   // eligible scans left that go straight to f32 (two overflows in a row: 256)
@@ -951,38 +953,6 @@ struct Route {
   ScanF16Band fb;
 };
 
-// One query in flight on one context.  Its three kernels (scan, select,
-// rerank) are enqueued back to back on the shard's single in-order pipeline
-// stream with NO copy and NO cross-stream dependency between them: the query
-// rides in the scan kernel's argument segment, the result block is stored
-// straight into pinned host memory, completion is one event.
-struct Job {
-  Ctx *c = nullptr;
-  int32_t k = 0, entries = 0;
-  bool masked = false, user_mask = false;
-  uint8_t *dev_target = nullptr;  // shard mode: caller's device block (header + entries land there)
-  bool timed = false;             // ev0/ev1 bracket this job's scan kernel
-  bool counted = false;           // contributes to Shard::inflight
-  Route route;  // the kernels it was enqueued with; its band is also the fallback's own threshold.  (A list scan leaves
-                // the context's keys / gmin in list order, route.n_exam of them)
-  bool up_mask = false, up_list = false;  // staged in the context's pinned buffers: copied to the device in front of the scan
-  const uint64_t *d_mask = nullptr;  // the caller's mask words on the device: the context's copy, or a mask handle's
-  const uint32_t *d_list = nullptr;  // the scanned list on the device: the context's copy, or a mask handle's
-  ExactSelArgs xsel{};     // the exact path: a pick whose cut bin was too full for the block is finished by
-                           // exact_select_kernel on the same keys (these arguments), job_finish
-  bool leave_overflow = false;  // shard mode under TSH_OPT_EXCHANGE_AHEAD: an exchange enqueued behind this job's kernels
-                                // may be reading the device block when the host looks at it -- a block whose list
-                                // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
-                                // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
-                                // redoing the group with larger blocks, not ahead
-  bool f16 = false;        // scanned over the fp16 copy (scan_f16_kernel): a list overflow is redone through the f32 scan,
-  std::vector<float> q_f16;  // from this copy of the query, with this tag
-  uint32_t tag = 0;
-  hipStream_t last_stream = nullptr;  // where the job's last kernel was enqueued (ev_done rides on it)
-  uint64_t enq_seq = 0;               // ... and its place in the device's enqueue order (DeviceStreams::enq_counter)
-  std::vector<uint32_t> quar_sel;  // entries of c->h_quar that belong to this query's candidates
-};
-
 // A selective caller mask as a list: local ids of the kept rows, ascending, padded with 0xFFFFFFFF to whole tiles of
 // 64.  Made once per call (shard_search_blocks) and shared by the call's queries; nullptr = scan by tiles.
 struct RowList {
@@ -1030,6 +1000,40 @@ struct ShardMask {
   RowList list;                     // a selective mask's kept rows
   const MaskPart *part = nullptr;   // a handle's: its device words and list are read in place, nothing is copied or uploaded
   bool listed() const { return list.ids || list.d_ids; }
+};
+
+// One query in flight on one context.  Its three kernels (scan, select,
+// rerank) are enqueued back to back on the shard's single in-order pipeline
+// stream with NO copy and NO cross-stream dependency between them: the query
+// rides in the scan kernel's argument segment, the result block is stored
+// straight into pinned host memory, completion is one event.
+struct Job {
+  Ctx *c = nullptr;
+  int32_t k = 0, entries = 0;
+  bool masked = false, user_mask = false;
+  uint8_t *dev_target = nullptr;  // shard mode: caller's device block (header + entries land there)
+  bool timed = false;             // ev0/ev1 bracket this job's scan kernel
+  bool counted = false;           // contributes to Shard::inflight
+  Route route;  // the kernels it was enqueued with; its band is also the fallback's own threshold.  (A list scan leaves
+                // the context's keys / gmin in list order, route.n_exam of them)
+  bool up_mask = false, up_list = false;  // staged in the context's pinned buffers: copied to the device in front of the scan
+  const uint64_t *d_mask = nullptr;  // the caller's mask words on the device: the context's copy, or a mask handle's
+  const uint32_t *d_list = nullptr;  // the scanned list on the device: the context's copy, or a mask handle's
+  ExactSelArgs xsel{};     // the exact path: a pick whose cut bin was too full for the block is finished by
+                           // exact_select_kernel on the same keys (these arguments), job_finish
+  bool leave_overflow = false;  // shard mode under TSH_OPT_EXCHANGE_AHEAD: an exchange enqueued behind this job's kernels
+                                // may be reading the device block when the host looks at it -- a block whose list
+                                // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
+                                // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
+                                // redoing the group with larger blocks, not ahead
+  bool f16 = false;        // scanned over the fp16 copy (scan_f16_kernel): a list overflow is redone through the f32 scan,
+  std::vector<float> q_f16;  // from this copy of the query, with this tag
+  uint32_t tag = 0;
+  ShardMask mask_f16;      // ... behind the same mask: a handle's part, or the context's own copy of a pointer mask's words
+                           // (job_enqueue: the caller's slice may be gone when a ticket is waited for)
+  hipStream_t last_stream = nullptr;  // where the job's last kernel was enqueued (ev_done rides on it)
+  uint64_t enq_seq = 0;               // ... and its place in the device's enqueue order (DeviceStreams::enq_counter)
+  std::vector<uint32_t> quar_sel;  // entries of c->h_quar that belong to this query's candidates
 };
 
 void launch_select(const SelectArgs &se, int32_t n_tiles, hipStream_t st) {
@@ -1224,11 +1228,14 @@ inline bool device_has_room(int64_t bytes);
 constexpr int64_t SCAN_F16_MIN_BYTES = 256ll << 20;  // the Infinity Cache: a row store below it is not HBM-bound
 constexpr int SCAN_F16_DENIED_SCANS = 256;
 
-// Could a dense, unmasked scan of this shard read the fp16 copy?  (the shard's side of the decision: caller holds s->mu)
-bool scan_f16_applies(const Shard *s, int *v_exp) {
-  if (s->scan_f16 == 0 || !s->all_live || s->rows16_denied || s->safe_mode()) return false;
+// Could a tile scan of this shard read the fp16 copy?  masked: behind a caller's mask, tombstones, quarantined rows or
+// gaps -- TSH_OPT_SCAN_F16_MASKED decides for those, TSH_OPT_SCAN_F16 for dense scans and, at 0, for both.  (The shard's
+// side of the decision: caller holds s->mu)
+bool scan_f16_applies(const Shard *s, bool masked, int *v_exp) {
+  const int mode = masked ? s->scan_f16_masked : s->scan_f16;
+  if (s->scan_f16 == 0 || mode == 0 || s->rows16_denied || s->safe_mode()) return false;
   if (!scan_f16_supported(s->nch, s->dim)) return false;
-  if (s->scan_f16 == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
+  if (mode == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
   if (s->metric == TSH_METRIC_COSINE && !(s->min_norm > 0.f)) return false;  // (a zero row: no uniform cosine band)
   return scan_f16_exp(s->max_abs, v_exp);
 }
@@ -1309,8 +1316,8 @@ Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, i
     return r;
   }
   r.band = compute_band(s, q);
-  // the fp16 route: dense, unmasked, all-live scans of big shards, inside the error model on both sides
-  r.f16_eligible = !no_f16 && !r.use_list && !masked && !r.band.force_all && scan_f16_applies(s, &r.v_exp);
+  // the fp16 route: tile scans of big shards, dense or masked, inside the error model on both sides
+  r.f16_eligible = !no_f16 && !r.use_list && !r.band.force_all && scan_f16_applies(s, masked, &r.v_exp);
   if (r.f16_eligible) r.fb = scan_f16_band(s->metric, s->dim, s->nch, q, s->max_norm, s->min_norm, r.v_exp);
   return r;
 }
@@ -1513,10 +1520,11 @@ int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipSt
   const int64_t rows_est = rq.mask.rows_est;
   if (j->route.exact) launch_exact_scan(ka.xa, s->metric, ps, ev);
   else if (j->route.use_list) launch_scan_list(ka.sa, s->nch, s->metric, ps, ev);
-  else if (j->f16) launch_scan_f16(ka.sa, s->nch, s->metric, ps, ev);
-  else
-    launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev,
-                j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows));
+  else {
+    const bool ml = j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows);
+    if (j->f16) launch_scan_f16(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
+    else launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
+  }
   return TSH_OK;
 }
 
@@ -1562,6 +1570,13 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   if (j->f16) {
     j->q_f16.assign(rq.query, rq.query + s->dim);
     j->tag = rq.tag;
+    // (no list: an fp16 scan walks tiles, and so does its redo.  A pointer mask's words were staged in c->h_mask under
+    // rq.mask.epoch -- by this job or an earlier one of the call -- and stay there while the job holds the context)
+    j->mask_f16 = ShardMask();
+    j->mask_f16.words = rq.mask.part ? rq.mask.words : (rq.mask.words ? c->h_mask : nullptr);
+    j->mask_f16.epoch = rq.mask.epoch;
+    j->mask_f16.rows_est = rq.mask.rows_est;
+    j->mask_f16.part = rq.mask.part;
   }
   fill_job_args(s, j, rq, q, &ka);
   // with other queries already in flight -- or the caller about to submit more (the first query of a multi-query
@@ -1733,7 +1748,8 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
         s->scan_f16_denied.store(SCAN_F16_DENIED_SCANS);
       }
       const std::vector<float> q(j->q_f16);
-      JobReq rq(q.data(), j->k, j->entries);  // (an fp16 scan had no mask)
+      JobReq rq(q.data(), j->k, j->entries);
+      rq.mask = j->mask_f16;  // the WHERE clause holds for the redo too
       rq.dev_target = j->dev_target;
       rq.last_of_call = true;
       rq.tag = j->tag;
@@ -3187,7 +3203,7 @@ int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const 
   auto launch = [&]() {
     if (r.exact) launch_exact_scan(xa, s->metric, st, LaunchEv());
     else if (r.use_list) launch_scan_list(sa, s->nch, s->metric, st);
-    else if (f16) launch_scan_f16(sa, s->nch, s->metric, st);
+    else if (f16) launch_scan_f16(sa, s->nch, s->metric, masked, st, LaunchEv(), ml);
     else launch_scan(sa, s->nch, s->metric, masked, st, LaunchEv(), ml);
   };
   launch();  // warm
@@ -3256,6 +3272,14 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
     for (auto &sh : idx->shards) {
       std::unique_lock<RwLock> xl(sh->mu);
       sh->scan_f16 = (int)value;
+    }
+    return TSH_OK;
+  }
+  if (option == TSH_OPT_SCAN_F16_MASKED) {
+    if (value < 0 || value > 2) return set_err(TSH_E_BAD_ARG, "scan f16 masked must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible masked scan)");
+    for (auto &sh : idx->shards) {
+      std::unique_lock<RwLock> xl(sh->mu);
+      sh->scan_f16_masked = (int)value;
     }
     return TSH_OK;
   }
@@ -3360,8 +3384,9 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
   memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
   for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
   int v_exp = 0;
-  if (!scan_f16_applies(s, &v_exp) || compute_band(s, c->h_query).force_all)
-    return set_err(TSH_E_BAD_ARG, "no fp16 scan for this index / query (TSH_OPT_SCAN_F16, row width, tombstones, error model)");
+  const bool masked = !s->all_live;  // (dead rows: the keys of TSH_OPT_SCAN_F16_MASKED's route, NaN where a row is not live)
+  if (!scan_f16_applies(s, masked, &v_exp) || compute_band(s, c->h_query).force_all)
+    return set_err(TSH_E_BAD_ARG, "no fp16 scan for this index / query (TSH_OPT_SCAN_F16, TSH_OPT_SCAN_F16_MASKED, row width, error model)");
   const ScanF16Band fb = scan_f16_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, v_exp);
   if (!fb.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the fp16 scan's error model");
   if (!rows16_ensure(s, st, v_exp)) return set_err(TSH_E_OOM, "no room on the device for the fp16 copy of the rows");
@@ -3369,7 +3394,9 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
   static thread_local ScanArgsQ sa;
   fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
   fill_scan_f16_args(s, fb, &sa, nullptr);
-  launch_scan_f16(sa, s->nch, s->metric, st);
+  // (a dead tile's keys stay as they were: the probe reads them all, so they start out dead)
+  if (masked) HIPCHK(hipMemsetAsync(c->d_keys, 0xFF, (size_t)((s->rows + 63) / 64) * 64 * 4, st));
+  launch_scan_f16(sa, s->nch, s->metric, masked, st);
   std::vector<uint32_t> keys((size_t)s->rows);
   HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
   // (the rows' bands, by the function the kernel adds them with -- into gmin's neighbour: the keys buffer is free again

@@ -94,25 +94,35 @@ void launch_scan_list_n(const ScanArgsQ &a, int metric, hipStream_t s, const Lau
 
 // The fp16 scan: a row is half the bytes, so two register buffers of R rows are R*NCH*2 VGPRs each, and the launch shape
 // is ScanShape's for a row of half as many 1 KiB chunks (d = 768: 1.5 KiB rows, eight waves per CU; d = 1536: four).
-template <int NCH> struct ScanF16Tune {
+// MASKED: the same (R, MINW) at every width -- the masked instantiations fit the dense ones' register budgets without
+// scratch (the compiler's resource-usage remarks: profiles/scan_f16_masked_resources.txt) -- and launch_scan_t's three shapes.
+template <int NCH, bool MASKED> struct ScanF16Tune {
   static constexpr int R = NCH <= 6 ? 4 : 2;
   static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 8 ? 3 : 2);
 };
-template <int NCH, int METRIC, bool FULL>
-void launch_scan_f16_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev) {
-  using T = ScanF16Tune<NCH>;
+template <int NCH, int METRIC, bool FULL, bool MASKED>
+void launch_scan_f16_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev, bool mostly_live) {
+  using T = ScanF16Tune<NCH, MASKED>;
   using S = ScanShape<(NCH + 1) / 2>;
-  if (grid > 0)
-    TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, T::R, 4, T::MINW>), (a.a.n_tiles + S::WPB - 1) / S::WPB, 64 * S::WPB, S::LDS, s, ev, a);
-  else TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, T::R, 4, T::MINW>), -grid, 64, 0, s, ev, a);
+  // grid > 0: a big shard -- dense and mostly-live scans in the shape of ScanShape, scattered ones in 4-wave workgroups;
+  // grid < 0: -grid one-wave workgroups (small shards)
+  if (grid > 0 && (!MASKED || mostly_live))
+    TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>), (a.a.n_tiles + S::WPB - 1) / S::WPB, 64 * S::WPB, S::LDS, s, ev, a);
+  else if (grid > 0) TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>), grid, 256, 0, s, ev, a);
+  else TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>), -grid, 64, 0, s, ev, a);
 }
 template <int NCH>
-void launch_scan_f16_n(const ScanArgsQ &a, int metric, int grid, hipStream_t s, const LaunchEv &ev) {
+void launch_scan_f16_n(const ScanArgsQ &a, int metric, bool masked, int grid, hipStream_t s, const LaunchEv &ev, bool ml) {
   const bool full = a.a.d4 == NCH * 64;
-#define TSH_F16(M)                                              \
-  do {                                                          \
-    if (full) launch_scan_f16_t<NCH, M, true>(a, grid, s, ev);  \
-    else launch_scan_f16_t<NCH, M, false>(a, grid, s, ev);      \
+#define TSH_F16(M)                                                            \
+  do {                                                                        \
+    if (full) {                                                               \
+      if (masked) launch_scan_f16_t<NCH, M, true, true>(a, grid, s, ev, ml);  \
+      else launch_scan_f16_t<NCH, M, true, false>(a, grid, s, ev, ml);        \
+    } else {                                                                  \
+      if (masked) launch_scan_f16_t<NCH, M, false, true>(a, grid, s, ev, ml); \
+      else launch_scan_f16_t<NCH, M, false, false>(a, grid, s, ev, ml);       \
+    }                                                                         \
   } while (0)
   if (metric == TSH_METRIC_L2) TSH_F16(METRIC_L2);
   else if (metric == TSH_METRIC_IP) TSH_F16(METRIC_IP);
@@ -125,22 +135,24 @@ void launch_scan_f16_n(const ScanArgsQ &a, int metric, int grid, hipStream_t s, 
 // (rows of more than 14 chunks that end inside a chunk would spill: they stay on f32)
 bool scan_f16_supported(int nch, int dim) { return dim >= 256 && dim % 8 == 0 && nch >= 1 && nch <= 14; }
 
-void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev) {
+void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev, bool ml) {
   if (a.a.n_tiles <= 0) return;
-  int grid = 1;  // (> 0: the big shards' shape, one workgroup per ScanShape::WPB tiles)
+  // (> 0: the big shards' shapes -- one workgroup per ScanShape::WPB tiles, or this many 4-wave workgroups for a
+  // scattered masked scan)
+  int grid = std::max(1, (a.a.n_tiles + 3) / 4);
   if (a.a.n_tiles < SMALL_SHARD_TILES) grid = -std::max(1, (int)a.a.n_tiles);
   switch (nch) {
-    case 1: launch_scan_f16_n<1>(a, metric, grid, s, ev); break;
-    case 2: launch_scan_f16_n<2>(a, metric, grid, s, ev); break;
-    case 3: launch_scan_f16_n<3>(a, metric, grid, s, ev); break;
-    case 4: launch_scan_f16_n<4>(a, metric, grid, s, ev); break;
-    case 5: launch_scan_f16_n<5>(a, metric, grid, s, ev); break;
-    case 6: launch_scan_f16_n<6>(a, metric, grid, s, ev); break;
-    case 7: launch_scan_f16_n<7>(a, metric, grid, s, ev); break;
-    case 8: launch_scan_f16_n<8>(a, metric, grid, s, ev); break;
-    case 10: launch_scan_f16_n<10>(a, metric, grid, s, ev); break;
-    case 12: launch_scan_f16_n<12>(a, metric, grid, s, ev); break;
-    default: launch_scan_f16_n<14>(a, metric, grid, s, ev); break;
+    case 1: launch_scan_f16_n<1>(a, metric, masked, grid, s, ev, ml); break;
+    case 2: launch_scan_f16_n<2>(a, metric, masked, grid, s, ev, ml); break;
+    case 3: launch_scan_f16_n<3>(a, metric, masked, grid, s, ev, ml); break;
+    case 4: launch_scan_f16_n<4>(a, metric, masked, grid, s, ev, ml); break;
+    case 5: launch_scan_f16_n<5>(a, metric, masked, grid, s, ev, ml); break;
+    case 6: launch_scan_f16_n<6>(a, metric, masked, grid, s, ev, ml); break;
+    case 7: launch_scan_f16_n<7>(a, metric, masked, grid, s, ev, ml); break;
+    case 8: launch_scan_f16_n<8>(a, metric, masked, grid, s, ev, ml); break;
+    case 10: launch_scan_f16_n<10>(a, metric, masked, grid, s, ev, ml); break;
+    case 12: launch_scan_f16_n<12>(a, metric, masked, grid, s, ev, ml); break;
+    default: launch_scan_f16_n<14>(a, metric, masked, grid, s, ev, ml); break;
   }
 }
 
