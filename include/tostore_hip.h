@@ -47,7 +47,7 @@ extern "C" {
  *    tsh_ngh_info grew (row_base, row_end); tsh_comm_timeline's sampled fields are scaled by exchanges / timed
  *    exchanges instead of a constant.
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
- *    TSH_OPT_SCAN_F16_MASKED. */
+ *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys. */
 
 /* status codes */
 #define TSH_OK 0
@@ -534,6 +534,13 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
  * the fp16 copy (dense and masked ones alike), out[1] = of those, queries whose candidate list overflowed and that were redone through the f32 scan,
  * out[2] = rows converted into the copy so far, out[3] = bytes of the copy resident now (part of bytes_resident). */
 int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out);
+/* tsh_probe_scan_i8_keys: the int8 scan's (TSH_OPT_SCAN_I8, which must allow the scan) two sides of every row's
+ * ranking key, out_lower[i] <= exact key of row i <= out_upper[i] being what its band claims (single-shard indexes
+ * without dead rows; rows floats each).  For the band test. */
+int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper);
+/* tsh_scan_i8_stats: out[0] scans over the int8 copy, out[1] queries redone through the f32 scan (survivor list
+ * overflow), out[2] rows converted into the copy, out[3] device bytes the copy holds. */
+int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
 
 /* Tuning knobs (no reference counterpart).  TSH_OPT_BATCH_MIN_NQ: when tsh_search /
  * tsh_search_shard answer a multi-query call on the batched matrix-core path:
@@ -613,6 +620,15 @@ int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out);
  * whatever the size (tests, A/B runs).  TSH_OPT_SCAN_F16 = 0 switches both routes off; its value 2 does not force this
  * one.  Results are identical either way; the scans count in tsh_scan_f16_stats. */
 #define TSH_OPT_SCAN_F16_MASKED 9
+/* TSH_OPT_SCAN_I8 (default 1): whether a dense single-query scan -- no caller mask, no tombstones, no quarantined rows or
+ * gaps -- runs as a COARSE first pass over an int8 copy of the rows (a quarter of the f32 bytes; a scale per row, built
+ * lazily by the first such scan and kept current like the fp16 copy), whose survivors -- the rows whose proven lower
+ * side is at or below the k-th smallest tile minimum of proven upper sides, at most 4096 of them -- are answered by the
+ * exact scan + select.  0: never (the library then behaves exactly as without the option), 1: shards whose rows exceed
+ * 256 MiB, 2: every eligible scan whatever the size (tests, A/B runs).  A survivor list that overflows is redone through
+ * the f32 scan; two in a row keep the shard's next 256 eligible scans off the route.  Results are identical either way;
+ * the scans count in tsh_scan_i8_stats. */
+#define TSH_OPT_SCAN_I8 10
 /* TSH_OPT_TEST_HOOKS (process-wide; idx is ignored and may be NULL): value TSH_TEST_HOOKS_MAGIC switches the
  * library's TEST hooks on, 0 off.  Only then does it read the environment variables that change what it loads or make
  * it fail on purpose -- TSH_RCCL_LIB (a stand-in for librccl: tests/fake_rccl), TSH_TEST_FAIL_ALLOC_OVER (device

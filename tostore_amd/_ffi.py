@@ -127,6 +127,8 @@ SIGNATURES = {
     "tsh_probe_batch_row_band": (c_i32, [p_void, c_i32, p_f32, p_f32]),
     "tsh_probe_scan_f16_keys": (c_i32, [p_void, p_f32, p_f32, p_f32]),
     "tsh_scan_f16_stats": (c_i32, [p_void, p_i64]),
+    "tsh_probe_scan_i8_keys": (c_i32, [p_void, p_f32, p_f32, p_f32]),
+    "tsh_scan_i8_stats": (c_i32, [p_void, p_i64]),
     "tsh_index_set_option": (c_i32, [p_void, c_i32, c_i64]),
 }
 
@@ -173,6 +175,7 @@ TSH_OPT_BATCH_HUB = 6
 TSH_OPT_BATCH_GROUP = 7
 TSH_OPT_SCAN_F16 = 8
 TSH_OPT_SCAN_F16_MASKED = 9
+TSH_OPT_SCAN_I8 = 10
 TSH_OPT_TEST_HOOKS = 1000
 TSH_TEST_HOOKS_MAGIC = 0x7465737468
 

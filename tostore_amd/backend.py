@@ -316,6 +316,27 @@ class HipVectorIndex:
                                                       w.ctypes.data_as(_ffi.p_f32)))
         return keys, w
 
+    def set_scan_i8(self, mode: int) -> None:
+        """Dense, all-live single-query scans as a coarse pass over the int8 copy of the rows (a quarter of the HBM bytes)
+        whose survivors the exact scan + select answer: 0 never, 1 auto (default: shards whose row store is larger
+        than 256 MiB), 2 every eligible scan whatever the size.  Results are identical."""
+        _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_I8, int(mode)))
+
+    def scan_i8_stats(self) -> dict:
+        """The int8 scan's counters: scans launched, queries redone through the f32 scan, rows converted, copy bytes."""
+        out = (ctypes.c_int64 * 4)()
+        _ffi.check(_ffi.lib().tsh_scan_i8_stats(self._h, out))
+        return {"scans": out[0], "redone": out[1], "rows_converted": out[2], "copy_bytes": out[3]}
+
+    def probe_scan_i8_keys(self, query):
+        """(lower side, upper side) of every row's key from the int8 scan kernel: tests of the error model."""
+        q = _f32c(query).reshape(-1)
+        lo = np.empty(self.size - self.row_base, dtype=np.float32)
+        up = np.empty(self.size - self.row_base, dtype=np.float32)
+        _ffi.check(_ffi.lib().tsh_probe_scan_i8_keys(self._h, q.ctypes.data_as(_ffi.p_f32), lo.ctypes.data_as(_ffi.p_f32),
+                                                     up.ctypes.data_as(_ffi.p_f32)))
+        return lo, up
+
     def set_exact_scan_rows(self, rows: int) -> None:
         """Single-query searches with at most `rows` rows to look at (a selective mask's kept rows, a small index) take
         the exact sums of all of them and select among the exact distances (two dispatches, no f32 pre-filter):

@@ -242,8 +242,13 @@ struct ExactSelArgs {
   int32_t cap;  // >= k
   int32_t metric;
   uint32_t tag;
+  // the coarse int8 scan's survivor list (tsh_scan_i8.hip.h; NULL otherwise): how many rows survived, and how many of
+  // them the list holds -- more survivors than that and the block is marked FLAG_LIST_OVERFLOW | FLAG_I8_OVERFLOW
+  const uint32_t *list_total;
+  uint32_t list_cap;
 };
 constexpr uint32_t FLAG_EXACT = 8u;  // informational: the block holds the exact top k (E1 + E2), not a band's candidates
+constexpr uint32_t FLAG_I8_OVERFLOW = 32u;  // with FLAG_LIST_OVERFLOW: the int8 scan's survivors did not fit their list
 
 // one more key into a 256-bin histogram in LDS: a wave whose members all name one bin (rounds among ties) adds its count
 // once, otherwise lane by lane.  (A version that took up to two popular values out of every wave spent 40-60 instructions
@@ -520,6 +525,7 @@ __global__ void __launch_bounds__(1024) exact_select_kernel(ExactSelArgs a) {
     hv.tiles_hit = (uint32_t)(wall_clock64() - pt2);  // the entries
 #endif
     hv.flags = FLAG_EXACT | (s_out > (uint32_t)a.cap ? FLAG_LIST_OVERFLOW : 0u);  // (cap >= k: never)
+    if (a.list_total && *a.list_total > a.list_cap) hv.flags |= FLAG_LIST_OVERFLOW | FLAG_I8_OVERFLOW;
     hv.k = (uint32_t)a.k;
     hv.metric = (uint32_t)a.metric;
     hv.row_base = a.row_base;
@@ -571,6 +577,8 @@ struct ExactPickArgs {
   int32_t cap;
   int32_t metric;
   uint32_t tag;
+  const uint32_t *list_total;  // ExactSelArgs's
+  uint32_t list_cap;
 };
 
 __global__ void __launch_bounds__(256) exact_pick_kernel(ExactPickArgs a) {
@@ -709,6 +717,7 @@ __global__ void __launch_bounds__(256) exact_pick_kernel(ExactPickArgs a) {
     hv.band_key = KEY_NAN;
     hv.tiles_hit = 0u;
     hv.flags = FLAG_EXACT | (s_final > (uint32_t)a.cap ? FLAG_LIST_OVERFLOW : 0u);
+    if (a.list_total && *a.list_total > a.list_cap) hv.flags |= FLAG_LIST_OVERFLOW | FLAG_I8_OVERFLOW;
     hv.k = (uint32_t)a.k;
     hv.metric = (uint32_t)a.metric;
     hv.row_base = a.row_base;

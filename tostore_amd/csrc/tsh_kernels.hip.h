@@ -131,6 +131,13 @@ struct ScanArgs {
   const float *sqnorm;
   float inv_scale, w_alpha, w_beta;
   int32_t pad_;
+  // scan_i8_kernel only (zero otherwise): rows16 is the int8 copy (n x ld biased bytes, row-major), scale8 its per-row
+  // scales, inv_scale the bias term fl(128 sum q_j), and the band is w_i = w_s * scale8_i + w_alpha * |row_i| + w_beta
+  // (cosine: w_s * scale8_i / |row_i| + w_beta; tsh_scan_i8_band.h): the kernel stores the LOWER side key - w_i per row
+  // and the minimum of the UPPER sides per tile
+  const float *scale8;
+  float w_s;
+  int32_t pad2_;
 };
 
 // Kernel parameter block: the scan arguments plus up to 960 query floats inline,
@@ -512,6 +519,186 @@ static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqn
   if (i < n) out[i] = sqnorm ? scan_f16_w(alpha, beta, sqnorm[i]) : beta;
 }
 
+// ---------------------------------------------------------------------------
+// K1 over the int8 copy of the rows (big shards' dense, all-live tile scans): a quarter of the f32 scan's HBM bytes.
+// A COARSE first pass: its keys only have to name a set of rows that provably holds the top k -- the survivors go
+// through the exact path (tsh_scan_i8.hip.h, tsh_exact.hip.h), so no second band and no re-rank follow it.
+// scan_f16_kernel's dense structure with 4-byte loads per lane: a lane holds the same four ELEMENTS of a chunk (chunk =
+// 256 elements = 256 contiguous bytes per wave instruction), so NCH, FULL, the query registers and the inline query are
+// the f32 kernel's.  A load is a quarter of the f32 kernel's bytes, so a register buffer holds R = 8 rows (a whole batch
+// of the butterfly) and two of them keep as many bytes in flight per wave as the fp16 kernel's two buffers of four rows.
+// The buffers hold the raw words; the bytes are widened where they are consumed, behind the fence.
+// All metrics are dot products: acc = sum q_j * float(b_ij) over the biased bytes b = code + 128, in f32 FMAs; then with
+// t = acc - qbias (qbias = fl(128 sum q_j), from the host) and dot = scale8_i * t
+//   L2      key = |v_i|^2 - 2 dot        IP      key = -dot        cosine  key = -dot / |v_i|
+// and the band |key - exact| <= w_i of tsh_scan_i8_band.h.  keys[row] = the LOWER side key - w_i; gmin[tile] = the minimum
+// of the UPPER sides key + w_i: k distinct tiles hold a row whose exact key is at or below tau = the k-th smallest
+// gmin, so every row of the top k has a lower side <= tau, and the threshold step needs no band arithmetic.
+template <int NCH, int METRIC, bool FULL, int WAVES, int MINW>
+__global__ void __launch_bounds__(WAVES * 64, MINW) scan_i8_kernel(ScanArgsQ aq) {
+  const ScanArgs &a = aq.a;
+  const float *qsrc = a.query;
+  if (!qsrc) {
+    typedef const char __attribute__((address_space(4))) * karg_ptr;
+    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
+  }
+  constexpr int R = 8;
+  const uint8_t *rows8 = reinterpret_cast<const uint8_t *>(a.rows16);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wpb = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
+  const int stride = gridDim.x * wpb;
+  uint32_t vmask = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) vmask |= (FULL || c * 64 + lane < a.d4) ? (1u << c) : 0u;
+  auto has = [&](int c) { return FULL || ((vmask >> c) & 1u) != 0u; };
+  auto off = [&](int c) { return has(c) ? c * 256 : -4 * lane; };
+  uint32_t loff[NCH];  // !FULL: this lane's byte offset into a row, per chunk (lanes past the row's end: its start)
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) loff[c] = has(c) ? (uint32_t)(4 * lane + c * 256) : 0u;
+
+  f32x4 q[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    q[c] = *reinterpret_cast<const f32x4 *>(qsrc + 4 * lane + off(c));
+    if (!has(c)) q[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (a.query_out && blockIdx.x == 0 && wave == 0) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (has(c))
+        *reinterpret_cast<f32x4 *>(a.query_out + 4 * lane + c * 256) = q[c];
+  }
+
+  for (int t = (int)blockIdx.x * wpb + wave; t < a.n_tiles; t += stride) {
+    const uint8_t *tbase = rows8 + (int64_t)t * 64 * a.ld + 4 * lane;
+    uint32_t v[2][R][NCH];
+    int next_row = 0;
+    auto load_group = [&](int buf) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const int r = next_row++;
+        if (FULL) {
+          const uint8_t *rp = tbase + (int64_t)r * a.ld;
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(rp + off(c)));
+        } else {
+          // (a scalar row base + one 32-bit lane offset per chunk: see scan_kernel)
+          const uint64_t rbi = (uint64_t)(rows8 + ((int64_t)t * 64 + r) * a.ld);
+          const uint8_t *rb = reinterpret_cast<const uint8_t *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rbi >> 32)) << 32) |
+                                                                (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rbi));
+#pragma unroll
+          for (int c = 0; c < NCH; ++c)
+            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(rb + loff[c]));
+        }
+      }
+    };
+    float val = 0.f;
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the previous tile's stores (see scan_kernel)
+    load_group(0);
+    // eight rows: the other buffer's loads go out first, then this one's words are widened and consumed
+    auto group = [&](int b, auto BUF, auto LAST) {
+      constexpr int buf = decltype(BUF)::value;
+      if (!decltype(LAST)::value) load_group(buf ^ 1);
+      TSH_FENCE();
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+          if (has(c)) {
+            const uint32_t x = v[buf][j][c];
+            const f32x4 f = f32x4{(float)(x & 255u), (float)((x >> 8) & 255u), (float)((x >> 16) & 255u), (float)(x >> 24)};
+            s = accum4<METRIC_IP>(s, q[c], f);
+          }
+        asm volatile("" : "+v"(s)::"memory");
+        acc[j] = s;
+      }
+      TSH_FENCE();
+      float o = treduce8<0>(acc, lane);
+      o += __shfl_xor(o, 8);
+      o += __shfl_xor(o, 16);
+      o += __shfl_xor(o, 32);
+      if ((lane >> 3) == b) val = o;
+    };
+#pragma nounroll
+    for (int b = 0; b < 6; b += 2) {
+      group(b, std::integral_constant<int, 0>{}, std::false_type{});
+      group(b + 1, std::integral_constant<int, 1>{}, std::false_type{});
+    }
+    group(6, std::integral_constant<int, 0>{}, std::false_type{});
+    group(7, std::integral_constant<int, 1>{}, std::true_type{});
+    // val = sum q_j b_ij of row t*64+lane
+
+    const int64_t row = (int64_t)t * 64 + lane;
+    const bool alive = row < a.n;
+    const float sc = alive ? a.scale8[row] : 0.f;
+    const float dot = sc * (val - a.inv_scale);
+    float x, w;
+    if (METRIC == METRIC_COS) {
+      const float inv = alive ? a.inv_norm[row] : 0.f;
+      x = -(dot * inv);
+      w = __builtin_fmaf(a.w_s * sc, inv, a.w_beta);
+    } else {
+      const float sq = alive ? a.sqnorm[row] : 0.f;
+      x = METRIC == METRIC_L2 ? __builtin_fmaf(-2.f, dot, sq) : -dot;
+      w = __builtin_fmaf(a.w_s, sc, __builtin_fmaf(a.w_alpha, __builtin_sqrtf(sq), a.w_beta));
+    }
+    a.keys[row] = alive ? f2key(x - w) : KEY_DEAD;
+    const uint32_t m = wave_min_u32(alive ? f2key(x + w) : KEY_DEAD);
+    if (lane == 0) a.gmin[t] = m;
+  }
+}
+
+// rows [r0, r1) of the f32 store -> the int8 copy and its scales: a wave per row.  scale = the row's largest |element| /
+// 127, rounded up, at least 2^-126 (tsh_scan_i8_band.h scan_i8_scale); code = rint(v / scale), stored as code + 128.
+// Elementwise over the padded rows (ld is a multiple of 4): 16-byte loads, one 4-byte store per lane and step.  A row
+// with a non-finite element gets codes nobody reads (it is quarantined: the shard then scans by another route).
+static __global__ void __launch_bounds__(256) rows8_convert_kernel(const float *rows, void *rows8, float *scale8, int64_t ld,
+                                                                   int64_t r0, int64_t r1) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
+  const int d4 = (int)(ld / 4);
+  for (int64_t r = r0 + w0; r < r1; r += nw) {
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(rows + r * ld);
+    float mx = 0.f;
+    for (int i = lane; i < d4; i += 64) {
+      const f32x4 x = src[i];
+      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w))));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float s = mx / 127.0f;
+    if ((double)s * 127.0 < (double)mx) s = __uint_as_float(__float_as_uint(s) + 1u);  // (positive and finite: the next float up)
+    if (!(s >= 1.17549435e-38f)) s = 1.17549435e-38f;
+    if (!(mx < __builtin_inff())) s = 1.0f;
+    uint32_t *dst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(rows8) + r * ld);
+    for (int i = lane; i < d4; i += 64) {
+      const f32x4 x = src[i];
+      uint32_t word = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float c = fminf(fmaxf(rintf(x[e] / s), -127.0f), 127.0f) + 128.0f;
+        word |= (uint32_t)c << (8 * e);
+      }
+      dst[i] = word;
+    }
+    if (lane == 0) scale8[r] = s;
+  }
+}
+
+// every row's band (tsh_probe_scan_i8_keys): what scan_i8_kernel took off / added to its key
+static __global__ void __launch_bounds__(256) scan_i8_w_kernel(const float *sqnorm, const float *inv_norm, const float *scale8,
+                                                               int64_t n, float w_s, float w_alpha, float w_beta, float *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float sc = scale8[i];
+  out[i] = inv_norm ? __builtin_fmaf(w_s * sc, inv_norm[i], w_beta)
+                    : __builtin_fmaf(w_s, sc, __builtin_fmaf(w_alpha, __builtin_sqrtf(sqnorm[i]), w_beta));
+}
+
 // K1 for SELECTIVE row masks (a WHERE clause that keeps a few percent of the rows; config C5): the host compacts the
 // kept row ids into a list once per mask, and the scan is a gather over that list instead of a walk over tiles that
 // are mostly dead.  Why: a masked scan_kernel wave meets 0.6 live rows per tile at keep 1 %, reads the tile's mask
@@ -883,6 +1070,142 @@ __device__ __forceinline__ uint32_t band_of(uint32_t tau_key, float eps_rel, flo
   return f2key(f);
 }
 
+// LDS of select_tau (and, after it, of its caller: `list` is free again once tau is known)
+template <int NT> struct SelectTauLds {
+  uint32_t lm[2 * NT];
+  uint32_t list[SEL_LIST_CAP];
+  uint32_t n, U, tau;
+};
+
+// Steps (a)-(c) of K2 (select_body below; the coarse scan's threshold kernel, tsh_scan_i8.hip.h): s.tau = the k-th smallest
+// of gmin[0 .. M) -- KEY_NAN when fewer than k of them are alive, or when the bound does not apply (force_all, k beyond
+// the scheme) --, by the whole workgroup of NT threads; g[]: the thread's tile minima, left in registers (IN_REGS).
+// Ends with a barrier: every thread may read s.tau.
+template <int NT, bool IN_REGS>
+__device__ __forceinline__ void select_tau(const uint32_t *gmin, int M, uint32_t k, bool force_all, uint32_t (&g)[SEL_VPT],
+                                           SelectTauLds<NT> &s) {
+  constexpr int SEL_THREADS = NT;  // shadows the namespace constant inside this kernel
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) {
+    s.n = 0;
+    s.U = KEY_DEAD;
+    s.tau = KEY_NAN;
+  }
+
+  uint32_t lmin = KEY_DEAD, lodd = KEY_DEAD;  // lodd: minimum over this thread's odd-numbered elements
+  if (IN_REGS) {
+#pragma unroll
+    for (int i = 0; i < SEL_VPT; ++i) {
+      int t = tid + i * SEL_THREADS;
+      g[i] = t < M ? gmin[t] : KEY_DEAD;
+      lmin = g[i] < lmin ? g[i] : lmin;
+      if (i & 1) lodd = g[i] < lodd ? g[i] : lodd;
+    }
+  } else {
+    int it = 0;
+    for (int t = tid; t < M; t += SEL_THREADS, ++it) {
+      uint32_t x = gmin[t];
+      lmin = x < lmin ? x : lmin;
+      if (it & 1) lodd = x < lodd ? x : lodd;
+    }
+  }
+  const bool narrow = !force_all && (uint32_t)M >= k && k <= (uint32_t)SEL_THREADS;
+  const bool groups4 = NT == 1024 && k <= 128;  // 256 group minima are plenty for small k
+  // above k = 512 the k-th of 1024 thread minima gets loose (G ln(G/(G-k)) entries below
+  // it): split every thread into its even and odd elements, 2048 groups
+  const bool groups2k = k > 512;
+  if (narrow && M > SEL_PREFILTER_MIN) {
+    uint32_t m = lmin;
+    if (groups4) {
+      uint32_t t1 = (uint32_t)__shfl_xor((int)m, 1);
+      m = t1 < m ? t1 : m;
+      uint32_t t2 = (uint32_t)__shfl_xor((int)m, 2);
+      m = t2 < m ? t2 : m;
+    }
+    s.lm[tid] = m;
+    if (groups2k) {  // even-element minimum and odd-element minimum as separate groups
+      uint32_t leven = KEY_DEAD;
+      if (IN_REGS) {
+#pragma unroll
+        for (int i = 0; i < SEL_VPT; i += 2) leven = g[i] < leven ? g[i] : leven;
+      } else {
+        int it = 0;
+        for (int t = tid; t < M; t += SEL_THREADS, ++it)
+          if (!(it & 1)) {
+            uint32_t x = gmin[t];
+            leven = x < leven ? x : leven;
+          }
+      }
+      s.lm[tid] = leven;
+      s.lm[SEL_THREADS + tid] = lodd;
+    }
+  }
+  __syncthreads();
+  if (narrow && M > SEL_PREFILTER_MIN && wave == 0) {
+    uint32_t U;
+    if (groups2k) {
+      uint32_t v[2 * NT / 64];
+#pragma unroll
+      for (int i = 0; i < 2 * NT / 64; ++i) v[i] = s.lm[lane + i * 64];
+      U = wave_kth_bisect<2 * NT / 64>(v, k);
+    } else if (groups4) {
+      uint32_t v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = s.lm[(lane + i * 64) * 4];
+      U = wave_kth_bisect<4>(v, k);
+    } else {
+      uint32_t v[NT / 64];
+#pragma unroll
+      for (int i = 0; i < NT / 64; ++i) v[i] = s.lm[lane + i * 64];
+      U = wave_kth_bisect<NT / 64>(v, k);
+    }
+    if (lane == 0) s.U = U;
+  }
+  __syncthreads();
+  if (narrow) {
+    const uint32_t U = s.U;  // KEY_DEAD when the list holds everything (M <= SEL_PREFILTER_MIN)
+    if (IN_REGS) {
+#pragma unroll
+      for (int i = 0; i < SEL_VPT; ++i) {
+        if (tid + i * SEL_THREADS < M && g[i] <= U) {
+          uint32_t p = atomicAdd(&s.n, 1u);
+          if (p < SEL_LIST_CAP) s.list[p] = g[i];
+        }
+      }
+    } else {
+      for (int t = tid; t < M; t += SEL_THREADS) {
+        uint32_t x = gmin[t];
+        if (x <= U) {
+          uint32_t p = atomicAdd(&s.n, 1u);
+          if (p < SEL_LIST_CAP) s.list[p] = x;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (narrow && wave == 0) {
+    const uint32_t n = s.n;
+    uint32_t tau;
+    if (n > SEL_LIST_CAP) {
+      tau = s.U;  // ties flooded the list: U is still a valid (looser) bound
+    } else if (n <= 512) {
+      uint32_t v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = (uint32_t)(lane + i * 64) < n ? s.list[lane + i * 64] : KEY_DEAD;
+      tau = wave_kth_bisect<8>(v, k);
+    } else {
+      uint32_t v[SEL_LIST_CAP / 64];
+#pragma unroll
+      for (int i = 0; i < SEL_LIST_CAP / 64; ++i)
+        v[i] = (uint32_t)(lane + i * 64) < n ? s.list[lane + i * 64] : KEY_DEAD;
+      tau = wave_kth_bisect<SEL_LIST_CAP / 64>(v, k);
+    }
+    if (tau == KEY_DEAD) tau = KEY_NAN;  // fewer than k live tiles: every live row
+    if (lane == 0) s.tau = tau;
+  }
+  __syncthreads();
+}
+
 // K2.  One workgroup.  Each thread keeps its share of gmin[] in registers
 // (IN_REGS: n_tiles <= 16384) so global memory is read once.
 //  (a) per-thread minimum -> LDS; wave 0 bisects those 1024 values (or 256
@@ -896,132 +1219,17 @@ template <int NT, bool IN_REGS>
 __device__ __forceinline__ void select_body(const SelectArgs &a) {
   static_assert(NT == 1024 || NT == 256, "thread minima are bisected by one wave as 16 or 4 per lane");
   constexpr int SEL_THREADS = NT;  // shadows the namespace constant inside this kernel
-  __shared__ uint32_t s_lm[2 * SEL_THREADS];
-  __shared__ uint32_t s_list[SEL_LIST_CAP];
-  __shared__ uint32_t s_n, s_tiles, s_cand, s_U, s_tau;
+  __shared__ SelectTauLds<NT> s_t;
+  __shared__ uint32_t s_tiles, s_cand;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int M = a.n_tiles;
   const uint32_t k = (uint32_t)a.k;
   if (tid == 0) {
-    s_n = 0;
     s_tiles = 0;
     s_cand = 0;
-    s_U = KEY_DEAD;
-    s_tau = KEY_NAN;
   }
   uint32_t g[SEL_VPT];
-  uint32_t lmin = KEY_DEAD, lodd = KEY_DEAD;  // lodd: minimum over this thread's odd-numbered elements
-  if (IN_REGS) {
-#pragma unroll
-    for (int i = 0; i < SEL_VPT; ++i) {
-      int t = tid + i * SEL_THREADS;
-      g[i] = t < M ? a.gmin[t] : KEY_DEAD;
-      lmin = g[i] < lmin ? g[i] : lmin;
-      if (i & 1) lodd = g[i] < lodd ? g[i] : lodd;
-    }
-  } else {
-    int it = 0;
-    for (int t = tid; t < M; t += SEL_THREADS, ++it) {
-      uint32_t x = a.gmin[t];
-      lmin = x < lmin ? x : lmin;
-      if (it & 1) lodd = x < lodd ? x : lodd;
-    }
-  }
-  const bool narrow = !a.force_all && (uint32_t)M >= k && k <= (uint32_t)SEL_THREADS;
-  const bool groups4 = NT == 1024 && k <= 128;  // 256 group minima are plenty for small k
-  // above k = 512 the k-th of 1024 thread minima gets loose (G ln(G/(G-k)) entries below
-  // it): split every thread into its even and odd elements, 2048 groups
-  const bool groups2k = k > 512;
-  if (narrow && M > SEL_PREFILTER_MIN) {
-    uint32_t m = lmin;
-    if (groups4) {
-      uint32_t t1 = (uint32_t)__shfl_xor((int)m, 1);
-      m = t1 < m ? t1 : m;
-      uint32_t t2 = (uint32_t)__shfl_xor((int)m, 2);
-      m = t2 < m ? t2 : m;
-    }
-    s_lm[tid] = m;
-    if (groups2k) {  // even-element minimum and odd-element minimum as separate groups
-      uint32_t leven = KEY_DEAD;
-      if (IN_REGS) {
-#pragma unroll
-        for (int i = 0; i < SEL_VPT; i += 2) leven = g[i] < leven ? g[i] : leven;
-      } else {
-        int it = 0;
-        for (int t = tid; t < M; t += SEL_THREADS, ++it)
-          if (!(it & 1)) {
-            uint32_t x = a.gmin[t];
-            leven = x < leven ? x : leven;
-          }
-      }
-      s_lm[tid] = leven;
-      s_lm[SEL_THREADS + tid] = lodd;
-    }
-  }
-  __syncthreads();
-  if (narrow && M > SEL_PREFILTER_MIN && wave == 0) {
-    uint32_t U;
-    if (groups2k) {
-      uint32_t v[2 * NT / 64];
-#pragma unroll
-      for (int i = 0; i < 2 * NT / 64; ++i) v[i] = s_lm[lane + i * 64];
-      U = wave_kth_bisect<2 * NT / 64>(v, k);
-    } else if (groups4) {
-      uint32_t v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = s_lm[(lane + i * 64) * 4];
-      U = wave_kth_bisect<4>(v, k);
-    } else {
-      uint32_t v[NT / 64];
-#pragma unroll
-      for (int i = 0; i < NT / 64; ++i) v[i] = s_lm[lane + i * 64];
-      U = wave_kth_bisect<NT / 64>(v, k);
-    }
-    if (lane == 0) s_U = U;
-  }
-  __syncthreads();
-  if (narrow) {
-    const uint32_t U = s_U;  // KEY_DEAD when the list holds everything (M <= SEL_PREFILTER_MIN)
-    if (IN_REGS) {
-#pragma unroll
-      for (int i = 0; i < SEL_VPT; ++i) {
-        if (tid + i * SEL_THREADS < M && g[i] <= U) {
-          uint32_t p = atomicAdd(&s_n, 1u);
-          if (p < SEL_LIST_CAP) s_list[p] = g[i];
-        }
-      }
-    } else {
-      for (int t = tid; t < M; t += SEL_THREADS) {
-        uint32_t x = a.gmin[t];
-        if (x <= U) {
-          uint32_t p = atomicAdd(&s_n, 1u);
-          if (p < SEL_LIST_CAP) s_list[p] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (narrow && wave == 0) {
-    const uint32_t n = s_n;
-    uint32_t tau;
-    if (n > SEL_LIST_CAP) {
-      tau = s_U;  // ties flooded the list: U is still a valid (looser) bound
-    } else if (n <= 512) {
-      uint32_t v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = (uint32_t)(lane + i * 64) < n ? s_list[lane + i * 64] : KEY_DEAD;
-      tau = wave_kth_bisect<8>(v, k);
-    } else {
-      uint32_t v[SEL_LIST_CAP / 64];
-#pragma unroll
-      for (int i = 0; i < SEL_LIST_CAP / 64; ++i)
-        v[i] = (uint32_t)(lane + i * 64) < n ? s_list[lane + i * 64] : KEY_DEAD;
-      tau = wave_kth_bisect<SEL_LIST_CAP / 64>(v, k);
-    }
-    if (tau == KEY_DEAD) tau = KEY_NAN;  // fewer than k live tiles: every live row
-    if (lane == 0) s_tau = tau;
-  }
-  __syncthreads();
+  select_tau<NT, IN_REGS>(a.gmin, M, k, a.force_all != 0, g, s_t);
   // A list scan of fewer tiles than k (a selective mask: a few thousand kept rows): the tile minima bound nothing, every
   // tile would be a hit and step (f) would bisect for the k-th key in up to 32 block-wide rounds.  The list-ordered keys
   // are one short contiguous array, every entry written (padding = KEY_DEAD): take the k-th smallest KEY directly,
@@ -1029,10 +1237,10 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
   if (a.list && !a.force_all && (uint32_t)M < k && (uint32_t)M * 64u >= k) {  // workgroup-uniform (fewer entries than k: all)
     __shared__ RadixSelScratch s_rs;
     const uint32_t x = block_kth_radix<NT>(a.keys, (uint32_t)M * 64u, k, &s_rs);
-    if (tid == 0) s_tau = x >= KEY_DEAD ? KEY_NAN : x;  // fewer than k live rows: every live row
+    if (tid == 0) s_t.tau = x >= KEY_DEAD ? KEY_NAN : x;  // fewer than k live rows: every live row
     __syncthreads();
   }
-  const uint32_t tau = s_tau;
+  const uint32_t tau = s_t.tau;
   const uint32_t band = a.force_all ? KEY_NAN : band_of(tau, a.eps_rel, a.delta_abs);
 
   // (d) tiles whose minimum is inside the band (KEY_DEAD > band always)
@@ -1041,14 +1249,14 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
     for (int i = 0; i < SEL_VPT; ++i) {
       if (g[i] <= band) {
         uint32_t p = atomicAdd(&s_tiles, 1u);
-        if (p < SEL_LIST_CAP) s_list[p] = (uint32_t)(tid + i * SEL_THREADS);
+        if (p < SEL_LIST_CAP) s_t.list[p] = (uint32_t)(tid + i * SEL_THREADS);
       }
     }
   } else {
     for (int t = tid; t < M; t += SEL_THREADS) {
       if (a.gmin[t] <= band) {
         uint32_t p = atomicAdd(&s_tiles, 1u);
-        if (p < SEL_LIST_CAP) s_list[p] = (uint32_t)t;
+        if (p < SEL_LIST_CAP) s_t.list[p] = (uint32_t)t;
       }
     }
   }
@@ -1065,7 +1273,7 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
       uint32_t tile[4], key[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        tile[u] = j0 + u < nt ? s_list[j0 + u] : 0xFFFFFFFFu;
+        tile[u] = j0 + u < nt ? s_t.list[j0 + u] : 0xFFFFFFFFu;
         key[u] = tile[u] != 0xFFFFFFFFu ? a.keys[(int64_t)tile[u] * 64 + lane] : KEY_DEAD;
       }
 #pragma unroll
@@ -1109,12 +1317,12 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
 #pragma unroll
       for (int i = 0; i < RV; ++i) {
         uint32_t j = (uint32_t)(wave + i * NW);
-        kr[i] = j < nt ? a.keys[(int64_t)s_list[j] * 64 + lane] : KEY_DEAD;
+        kr[i] = j < nt ? a.keys[(int64_t)s_t.list[j] * 64 + lane] : KEY_DEAD;
         lo = kr[i] < lo ? kr[i] : lo;
       }
     } else {
       for (uint32_t j = wave; j < nt; j += NW) {
-        uint32_t x = a.keys[(int64_t)s_list[j] * 64 + lane];
+        uint32_t x = a.keys[(int64_t)s_t.list[j] * 64 + lane];
         lo = x < lo ? x : lo;
       }
     }
@@ -1142,7 +1350,7 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
           for (int i = 0; i < RV; ++i) c += (uint32_t)__popcll(__ballot(kr[i] <= T));
         } else {
           for (uint32_t j = wave; j < nt; j += NW)
-            c += (uint32_t)__popcll(__ballot(a.keys[(int64_t)s_list[j] * 64 + lane] <= T));
+            c += (uint32_t)__popcll(__ballot(a.keys[(int64_t)s_t.list[j] * 64 + lane] <= T));
         }
         if (lane == 0) atomicAdd(&s_cnt[slot], c);
         const int nxt = slot == 2 ? 0 : slot + 1;

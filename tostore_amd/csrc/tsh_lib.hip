@@ -40,6 +40,8 @@
 #include "tsh_mask.hip.h"
 #include "tsh_pq.hip.h"
 #include "tsh_scan_f16_band.h"
+#include "tsh_scan_i8.hip.h"
+#include "tsh_scan_i8_band.h"
 
 using namespace tsh;
 
@@ -301,6 +303,10 @@ struct Ctx {
   double *d_xsum = nullptr;
   uint64_t *d_xpick = nullptr;  // exact_pick_kernel: [0] its counter (zero between searches), [1 ..] E1's wave minima
   int64_t x_cap = 0;
+  // the coarse int8 scan's tail (tsh_scan_i8.hip.h): [tau, survivor total | M1's counts | the survivors' ballot words] and
+  // the survivor list of I8_LIST_CAP ids
+  uint32_t *d_i8 = nullptr, *d_i8_list = nullptr;
+  int64_t i8_tiles = 0;
   int64_t bytes = 0;
 };
 
@@ -471,6 +477,20 @@ struct Shard {
   std::atomic<int64_t> c_f16_scans{0}, c_f16_redone{0}, c_f16_converted{0};
   std::atomic<int> scan_f16_strikes{0};  // fp16 scans in a row whose candidate list overflowed
   std::atomic<int> scan_f16_denied{0};   // eligible scans left that go straight to f32 (two overflows in a row: 256)
+  // The int8 copy of the rows that big shards' dense, all-live single-query scans read as a coarse first pass
+  // (scan_i8_kernel): row-major, ld biased bytes per row, and behind them (same allocation) a scale per row.  Kept
+  // current exactly like the fp16 copy (rows8_ensure / rows16_ensure share row_copy_ensure, and rows16_mu guards both).
+  void *d_rows8 = nullptr;
+  float *d_scale8 = nullptr;
+  int64_t rows8_cap = 0, rows8_valid = 0, rows8_bytes = 0;
+  bool rows8_denied = false;  // the copy did not fit on the device: no int8 scans until the row store is reallocated
+#ifndef TSH_SCAN_I8_DEFAULT
+#define TSH_SCAN_I8_DEFAULT 1  // (A/B builds: -DTSH_SCAN_I8_DEFAULT=0, a variant library of its own -- tostore_amd/build.py)
+#endif
+  int scan_i8 = TSH_SCAN_I8_DEFAULT;  // TSH_OPT_SCAN_I8: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible scan
+  std::atomic<int64_t> c_i8_scans{0}, c_i8_redone{0}, c_i8_converted{0};
+  std::atomic<int> scan_i8_strikes{0};  // int8 scans in a row whose survivor list overflowed
+  std::atomic<int> scan_i8_denied{0};   // eligible scans left that skip the route (two overflows in a row: 256)
 
   bool safe_mode() const {
     if (nonfinite_rows) return true;
@@ -659,6 +679,15 @@ int shard_reserve(Shard *s, int64_t want_rows) {
   }
   s->rows16_cap = s->rows16_valid = 0;
   s->rows16_denied = false;
+  if (s->d_rows8) {
+    hipFree(s->d_rows8);
+    s->d_rows8 = nullptr;
+    s->d_scale8 = nullptr;
+    s->bytes -= s->rows8_bytes;
+    s->rows8_bytes = 0;
+  }
+  s->rows8_cap = s->rows8_valid = 0;
+  s->rows8_denied = false;
   s->d_rows = nrows;
   s->d_inv_norm = ninv;
   s->d_sqnorm = nsq;
@@ -756,6 +785,7 @@ int shard_append(Shard *s, int64_t first, int64_t n, const float *src, bool src_
   if (first + n > s->rows) s->rows = first + n;
   s->split_valid = std::min(s->split_valid, first);  // overwritten / new rows need re-splitting
   if (first < s->rows16_valid) s->rows16_valid = 0;  // a stored row overwritten: the fp16 copy is rebuilt
+  if (first < s->rows8_valid) s->rows8_valid = 0;    // ... and the int8 copy
   if (first < s->hub_rows_built) s->hub_rows_built = -1;  // (an overwritten row may be a hub row: its copy is stale)
   return TSH_OK;
 }
@@ -784,6 +814,8 @@ void ctx_free_all(Ctx *c) {
   hipFree(c->d_xkey);
   hipFree(c->d_xsum);
   hipFree(c->d_xpick);
+  hipFree(c->d_i8);
+  hipFree(c->d_i8_list);
 }
 
 int ctx_prepare(Shard *s, Ctx *c, int32_t entries, bool need_mask) {
@@ -934,6 +966,9 @@ void fill_scan_args(const Shard *s, const Ctx *c, const uint64_t *d_mask, const 
   a->sqnorm = nullptr;
   a->inv_scale = a->w_alpha = a->w_beta = 0.f;
   a->pad_ = 0;
+  a->scale8 = nullptr;
+  a->w_s = 0.f;
+  a->pad2_ = 0;
 }
 
 // slice the caller's GLOBAL keep mask into this shard's tile words (tsh_host_sync.h: no bit past the last row is kept)
@@ -951,6 +986,8 @@ struct Route {
   bool f16_eligible = false;  // the fp16 scan may run (the caller still owes the denial counter and rows16_ensure) ...
   int v_exp = 0;              // ... over a copy of this scale, its keys inside this band
   ScanF16Band fb;
+  bool i8_eligible = false;  // the coarse int8 scan + the exact path over its survivors may run (the caller still owes
+  ScanI8Band ib;             // the denial counter and rows8_ensure); `picked`: E2' behind it instead of E2
 };
 
 // A selective caller mask as a list: local ids of the kept rows, ascending, padded with 0xFFFFFFFF to whole tiles of
@@ -1026,6 +1063,7 @@ struct Job {
                                 // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
                                 // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
                                 // redoing the group with larger blocks, not ahead
+  bool i8 = false;         // scanned over the int8 copy, survivors through the exact path (q_f16 / tag: the redo's)
   bool f16 = false;        // scanned over the fp16 copy (scan_f16_kernel): a list overflow is redone through the f32 scan,
   std::vector<float> q_f16;  // from this copy of the query, with this tag
   uint32_t tag = 0;
@@ -1240,47 +1278,121 @@ bool scan_f16_applies(const Shard *s, bool masked, int *v_exp) {
   return scan_f16_exp(s->max_abs, v_exp);
 }
 
-// Brings the fp16 copy up to the shard's rows: allocation on first use, conversion of the rows past the watermark (all
-// of them after a reset) on `st`, waited for -- a scan on any stream may follow.  false: the copy does not fit on the
-// device; the shard scans f32 from now on (rows16_denied) instead of asking again with every query.
-bool rows16_ensure(Shard *s, hipStream_t st, int v_exp) {
-  std::lock_guard<std::mutex> lk(s->rows16_mu);
-  if (s->rows16_denied) return false;
-  if (s->d_rows16 && s->rows16_cap == s->cap && s->rows16_exp == v_exp && s->rows16_valid == s->rows) return true;
+// One lazily kept copy of the rows (the fp16 copy, the int8 copy): its device buffer and watermark, as fields of the shard
+struct RowCopyRef {
+  void *&d;
+  int64_t &cap, &valid, &bytes;
+  bool &denied;
+};
+// Brings a copy up to the shard's rows: allocation on first use (`bytes` for the row store's capacity), conversion of the
+// rows past the watermark (all of them after a reset, or with `rebuild`) by convert(r0, r1) on `st`, waited for -- a scan
+// on any stream may follow.  false: the copy does not fit on the device; the shard stays off it from now on (denied)
+// instead of asking again with every query.  Caller holds rows16_mu.
+template <class Convert>
+bool row_copy_ensure(Shard *s, RowCopyRef c, int64_t bytes, bool rebuild, hipStream_t st, std::atomic<int64_t> *converted, Convert convert) {
+  if (c.denied) return false;
+  if (c.d && c.cap == s->cap && !rebuild && c.valid == s->rows) return true;
   if (hipSetDevice(s->device) != hipSuccess) return false;
-  if (!s->d_rows16 || s->rows16_cap != s->cap) {
-    if (s->d_rows16) {
-      hipFree(s->d_rows16);
-      s->d_rows16 = nullptr;
-      s->bytes -= s->rows16_bytes;
-      s->rows16_bytes = 0;
+  if (!c.d || c.cap != s->cap) {
+    if (c.d) {
+      hipFree(c.d);
+      c.d = nullptr;
+      s->bytes -= c.bytes;
+      c.bytes = 0;
     }
-    s->rows16_cap = s->rows16_valid = 0;
-    const int64_t bytes = s->cap * s->ld * 2;
-    if (alloc_fault(bytes) || !device_has_room(bytes) || hipMalloc(&s->d_rows16, (size_t)bytes) != hipSuccess) {
+    c.cap = c.valid = 0;
+    if (alloc_fault(bytes) || !device_has_room(bytes) || hipMalloc(&c.d, (size_t)bytes) != hipSuccess) {
       (void)hipGetLastError();
-      s->d_rows16 = nullptr;
-      s->rows16_denied = true;
+      c.d = nullptr;
+      c.denied = true;
       return false;
     }
-    s->rows16_cap = s->cap;
-    s->rows16_bytes = bytes;
+    c.cap = s->cap;
+    c.bytes = bytes;
     s->bytes += bytes;
   }
-  if (s->rows16_exp != v_exp) s->rows16_valid = 0;  // another scale: every row again
-  s->rows16_exp = v_exp;
+  if (rebuild) c.valid = 0;
   // whole tiles: the scan reads the last tile's rows past the shard's end (zeros in the f32 store) and drops them
-  const int64_t r0 = s->rows16_valid, r1 = std::min(round_up(s->rows, 64), s->cap);
-  const int64_t groups = (r1 - r0) * s->ld / 4;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 8192));
-  rows16_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->d_rows16, s->ld, r0, r1, std::ldexp(1.0f, v_exp));
+  const int64_t r0 = c.valid, r1 = std::min(round_up(s->rows, 64), s->cap);
+  convert(r0, r1);
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-    s->rows16_valid = 0;
+    c.valid = 0;
     return false;
   }
-  s->c_f16_converted += s->rows - r0;
-  s->rows16_valid = s->rows;
+  *converted += s->rows - r0;
+  c.valid = s->rows;
   return true;
+}
+
+// The fp16 copy, of scale 2^v_exp (another scale: every row again)
+bool rows16_ensure(Shard *s, hipStream_t st, int v_exp) {
+  std::lock_guard<std::mutex> lk(s->rows16_mu);
+  const bool rescale = s->rows16_exp != v_exp;
+  s->rows16_exp = v_exp;
+  return row_copy_ensure(s, RowCopyRef{s->d_rows16, s->rows16_cap, s->rows16_valid, s->rows16_bytes, s->rows16_denied},
+                         s->cap * s->ld * 2, rescale, st, &s->c_f16_converted, [&](int64_t r0, int64_t r1) {
+                           const int64_t groups = (r1 - r0) * s->ld / 4;
+                           const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 8192));
+                           rows16_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->d_rows16, s->ld, r0, r1, std::ldexp(1.0f, v_exp));
+                         });
+}
+
+// The int8 copy and, behind its rows, their scales
+bool rows8_ensure(Shard *s, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(s->rows16_mu);
+  const bool ok = row_copy_ensure(s, RowCopyRef{s->d_rows8, s->rows8_cap, s->rows8_valid, s->rows8_bytes, s->rows8_denied},
+                                  s->cap * s->ld + s->cap * 4, false, st, &s->c_i8_converted, [&](int64_t r0, int64_t r1) {
+                                    float *scale8 = reinterpret_cast<float *>(static_cast<uint8_t *>(s->d_rows8) + s->cap * s->ld);
+                                    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((r1 - r0 + 3) / 4, 16384));
+                                    rows8_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->d_rows8, scale8, s->ld, r0, r1);
+                                  });
+  s->d_scale8 = ok ? reinterpret_cast<float *>(static_cast<uint8_t *>(s->d_rows8) + s->cap * s->ld) : nullptr;
+  return ok;
+}
+
+// Could a scan of this shard take the coarse int8 route?  Dense and all-live only (the callers know about masks); the
+// exact path behind it needs a block of at least k entries.  (The shard's side of the decision: caller holds s->mu)
+constexpr int SCAN_I8_DENIED_SCANS = 256;
+bool scan_i8_applies(const Shard *s, int32_t k, int32_t entries) {
+  if (s->scan_i8 == 0 || s->rows8_denied || s->safe_mode() || !s->all_live || !s->quar_ids.empty()) return false;
+  if (!scan_i8_supported(s->nch) || k > entries || k > I8_LIST_CAP || s->rows <= 0) return false;
+  if (s->scan_i8 == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
+  if (s->metric == TSH_METRIC_COSINE && !(s->min_norm > 0.f)) return false;
+  return true;
+}
+
+// the int8 scan's arguments on top of the f32 scan's (fill_scan_args)
+void fill_scan_i8_args(const Shard *s, const ScanI8Band &ib, ScanArgsQ *aq) {
+  aq->a.rows16 = s->d_rows8;
+  aq->a.scale8 = s->d_scale8;
+  aq->a.sqnorm = s->d_sqnorm;
+  aq->a.inv_scale = ib.qbias;
+  aq->a.w_s = ib.a_s;
+  aq->a.w_alpha = ib.a_v;
+  aq->a.w_beta = ib.beta;
+}
+
+// the device buffers of the int8 scan's tail, for a shard of n_tiles tiles
+int ctx_reserve_i8(Ctx *c, int64_t n_tiles) {
+  if (!c->d_i8_list) {
+    HIPCHK(hipMalloc(&c->d_i8_list, (size_t)I8_LIST_CAP * sizeof(uint32_t)));
+    c->bytes += I8_LIST_CAP * 4;
+  }
+  if (n_tiles <= c->i8_tiles) return TSH_OK;
+  hipFree(c->d_i8);
+  c->d_i8 = nullptr;
+  c->bytes -= c->i8_tiles * 9 + 16;
+  c->i8_tiles = 0;
+  const int64_t want = round_up(n_tiles + n_tiles / 2, MASK_BLOCK_WORDS);
+  // [0] tau, [1] the survivors' total, [4 ..) M1's counts (one per MASK_BLOCK_WORDS tiles), then the ballot words
+  HIPCHK(hipMalloc(&c->d_i8, (size_t)(16 + round_up(want / MASK_BLOCK_WORDS * 4, 16) + want * 8)));
+  c->i8_tiles = want;
+  c->bytes += want * 9 + 16;
+  return TSH_OK;
+}
+inline uint32_t *i8_bsum(const Ctx *c) { return c->d_i8 + 4; }
+inline uint64_t *i8_words(const Ctx *c) {
+  return reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(c->d_i8) + 16 + round_up(c->i8_tiles / MASK_BLOCK_WORDS * 4, 16));
 }
 
 // the fp16 scan's arguments on top of the f32 scan's (fill_scan_args) and the select's
@@ -1302,7 +1414,8 @@ void fill_scan_f16_args(const Shard *s, const ScanF16Band &fb, ScanArgsQ *aq, Se
 // The route of one query's scan on this shard, decided here for every caller and without side effects.  m: the search's
 // mask (resolve_mask); masked: a mask or tombstones; q: the query (dim floats are read: zero-padded or not); no_f16:
 // the redo of an fp16 scan.  Caller holds s->mu shared.
-Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, int32_t entries, const float *q, bool no_f16) {
+Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, int32_t entries, const float *q, bool no_f16,
+                   bool no_i8 = false) {
   Route r;
   r.use_list = m.listed();
   // A search with only a few thousand rows to look at (a selective mask's list, a small index or shard) takes their
@@ -1310,6 +1423,16 @@ Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, i
   // (tsh_exact.hip.h).  The block must have room for the k rows it will hold.
   r.n_exam = r.use_list ? (int64_t)m.list.padded : s->rows;
   r.exact = exact_applies(s, r.n_exam, k, entries);
+  // the coarse int8 route: dense, all-live tile scans inside the error model (TSH_OPT_SCAN_I8 = 2, the tests' setting,
+  // takes it for shards the exact path would answer whole, too)
+  if (!no_i8 && !masked && !r.use_list && (!r.exact || s->scan_i8 == 2) && scan_i8_applies(s, k, entries) && !compute_band(s, q).force_all) {
+    r.ib = scan_i8_band(s->metric, s->dim, s->nch, q, s->max_norm, s->min_norm, s->max_abs);
+    r.i8_eligible = true;
+    if (r.exact && r.ib.ok) r.exact = false;  // (mode 2; a denial or a full device below leaves such a shard to its f32 scan)
+    // E2' needs as many live waves as k; the survivors -- at least k rows, at the front of the list -- guarantee
+    // ceil(k / EX_R) of them, and the host knows no more: the wide pick where that is enough, E2 otherwise
+    r.picked = s->exact_pick && (k + EX_R - 1) / EX_R >= k;
+  }
   if (r.exact) {
     // E2' (the wide pick) bounds the k-th key by the k-th smallest wave minimum: it needs clearly more waves than k
     r.picked = s->exact_pick && (r.n_exam + EX_R - 1) / EX_R >= 2 * (int64_t)k;
@@ -1332,6 +1455,7 @@ struct JobReq {
   bool last_of_call = false;      // ... or this is the last of several
   uint32_t tag = 0;               // generation stamped into the block's header
   bool no_f16 = false;            // the redo of an fp16 scan whose list overflowed: f32 this time
+  bool no_i8 = false;             // the redo of an int8 scan whose survivor list overflowed (with no_f16: f32)
 };
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
 struct JobArgs {
@@ -1348,7 +1472,7 @@ RerankArgs rerank_args(const Shard *s, const Ctx *c, const uint32_t *cand_rows, 
 ExactPickArgs exact_pick_args(const ExactSelArgs &xs, const Ctx *c) {
   return ExactPickArgs{xs.xkey, xs.xsum, xs.list, /*wmin*/ c->d_xpick + 1, /*ctr*/ reinterpret_cast<unsigned long long *>(c->d_xpick),
                        xs.hdr, xs.hdr_host, xs.out, xs.row_base, xs.shard_rows, xs.n_entries,
-                       /*n_groups*/ (xs.n_entries + EX_R - 1) / EX_R, xs.k, xs.cap, xs.metric, xs.tag};
+                       /*n_groups*/ (xs.n_entries + EX_R - 1) / EX_R, xs.k, xs.cap, xs.metric, xs.tag, xs.list_total, xs.list_cap};
 }
 // Reserves what the job's route needs in its context and stages the inputs on the host: the job's fields, mask and list in
 // the context's pinned buffers where new to it, the query zero-padded at *qp (the scan's argument segment, or c->h_query)
@@ -1438,6 +1562,15 @@ void fill_job_args(const Shard *s, Job *j, const JobReq &rq, const float *q, Job
   se.row_base = s->row_base;
   se.shard_rows = s->rows;
   if (j->f16) fill_scan_f16_args(s, r.fb, &ka->sa, &se);
+  if (j->i8) {
+    // the coarse scan, then E1 + E2 / E2' over the survivor list: I8_LIST_CAP entries, the padding dead.  E1 reads the
+    // query's device copy (the scan's workgroup 0 leaves it, or it was uploaded in front of the scan)
+    fill_scan_i8_args(s, r.ib, &ka->sa);
+    fill_exact_args(s, c, nullptr, c->d_i8_list, I8_LIST_CAP, q, &ka->xa);
+    if (r.picked) ka->xa.a.wmin = c->d_xpick + 1;
+    j->xsel = ExactSelArgs{c->d_xkey, c->d_xsum, c->d_i8_list, hdr, hdr_host, out, s->row_base, /*shard_rows*/ s->rows, I8_LIST_CAP,
+                           rq.k, /*cap*/ rq.entries, s->metric, rq.tag, /*list_total*/ c->d_i8 + 1, /*list_cap*/ (uint32_t)I8_LIST_CAP};
+  }
   ka->ra = rerank_args(s, c, c->d_cand, &hdr->count, out, rq.entries);
 }
 
@@ -1522,7 +1655,8 @@ int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipSt
   else if (j->route.use_list) launch_scan_list(ka.sa, s->nch, s->metric, ps, ev);
   else {
     const bool ml = j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows);
-    if (j->f16) launch_scan_f16(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
+    if (j->i8) launch_scan_i8(ka.sa, s->nch, s->metric, ps, ev);
+    else if (j->f16) launch_scan_f16(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
     else launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
   }
   return TSH_OK;
@@ -1538,10 +1672,21 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
   Ctx *c = j->c;
   const bool quar = !j->quar_sel.empty();
   const hipEvent_t none = nullptr, done = quar ? none : c->ev_done;
+  if (j->i8) {
+    // threshold, survivors' ballot words, their count and ascending list (capped and padded by M2), E1 over the list
+    const int32_t n_tiles = ka.sa.a.n_tiles, n_blocks = (n_tiles + MASK_BLOCK_WORDS - 1) / MASK_BLOCK_WORDS;
+    if (n_tiles <= SEL_VPT * SEL_THREADS) i8_tau_kernel<true><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
+    else i8_tau_kernel<false><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
+    i8_survivor_kernel<<<(unsigned)((n_tiles + 4 * I8_SURV_TILES - 1) / (4 * I8_SURV_TILES)), 256, 0, ts>>>(c->d_keys, c->d_i8, n_tiles, i8_words(c));
+    mask_block_count_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, ts>>>(i8_words(c), n_tiles, i8_bsum(c));
+    mask_compact_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, ts>>>(i8_words(c), n_tiles, i8_bsum(c), c->d_i8_list, c->d_i8 + 1,
+                                                              (uint32_t)I8_LIST_CAP, (uint32_t)I8_LIST_CAP);
+    launch_exact_scan(ka.xa, s->metric, ts, LaunchEv());
+  }
   if (j->route.picked) {  // E2': one workgroup per 256 entries, a bound from E1's wave minima, no ranking below it
     const ExactPickArgs xp = exact_pick_args(j->xsel, c);
     TSH_LAUNCH_EV(exact_pick_kernel, (unsigned)((xp.n_entries + 255) / 256), 256, ts, none, done, xp);
-  } else if (j->route.exact) {
+  } else if (j->route.exact || j->i8) {
     TSH_LAUNCH_EV(exact_select_kernel, 1, 1024, ts, none, done, j->xsel);
   } else {
     launch_select(ka.se, ka.se.n_tiles, ts);
@@ -1559,14 +1704,25 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   static thread_local JobArgs ka;  // ScanArgsQ, ExactArgsQ: 4 KiB each: keep them off the stack of deep callers
   j->user_mask = rq.mask.words != nullptr;
   j->masked = j->user_mask || !s->all_live;
-  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16);
+  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8);
   float *q;
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
+  // (an eligible scan uses up a denial of the int8 route, if any are left, whatever its band; a scan that takes the
+  // route neither asks for the fp16 copy nor touches the fp16 route's denials)
+  const bool denied8 = r.i8_eligible && s->scan_i8_denied.load() > 0;
+  if (denied8) s->scan_i8_denied.fetch_sub(1);
+  j->i8 = r.i8_eligible && !denied8 && r.ib.ok && rows8_ensure(s, s->scan_stream);
+  if (j->i8 && ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c, (s->rows + 63) / 64)))) return rc;
+  if (!j->i8 && !r.exact) j->route.picked = false;
   // (an eligible scan uses up a denial, if any are left, whatever its band)
-  const bool denied = r.f16_eligible && s->scan_f16_denied.load() > 0;
+  const bool denied = !j->i8 && r.f16_eligible && s->scan_f16_denied.load() > 0;
   if (denied) s->scan_f16_denied.fetch_sub(1);
-  j->f16 = r.f16_eligible && !denied && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp);
+  j->f16 = !j->i8 && r.f16_eligible && !denied && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp);
+  if (j->i8) {
+    j->q_f16.assign(rq.query, rq.query + s->dim);
+    j->tag = rq.tag;
+  }
   if (j->f16) {
     j->q_f16.assign(rq.query, rq.query + s->dim);
     j->tag = rq.tag;
@@ -1610,6 +1766,7 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   if (r.use_list) s->c_list_scans++;
   if (r.exact) s->c_exact_scans++;
   if (j->f16) s->c_f16_scans++;
+  if (j->i8) s->c_i8_scans++;
   return TSH_OK;
 }
 
@@ -1733,6 +1890,36 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipEventSynchronize(c->ev_done));
   HIPCHK(hipGetLastError());
+  if (j->i8) {
+    // An int8 scan whose survivors did not fit their list (crowded neighbours; fewer live tiles than k in a big shard): the
+    // query is redone through the f32 scan, as an fp16 overflow is.  Two in a row and the shard's next
+    // SCAN_I8_DENIED_SCANS eligible scans skip the route.
+    const BlockHeader *h8 = reinterpret_cast<const BlockHeader *>(c->h_block);
+    const bool over = (h8->flags & FLAG_I8_OVERFLOW) != 0;
+    if (!over) {
+      s->scan_i8_strikes.store(0);
+    } else if (!(j->leave_overflow && j->dev_target)) {  // (left as it is: see Job::leave_overflow)
+      s->c_i8_redone++;
+      if (s->scan_i8_strikes.fetch_add(1) + 1 >= 2) {
+        s->scan_i8_strikes.store(0);
+        s->scan_i8_denied.store(SCAN_I8_DENIED_SCANS);
+      }
+      const std::vector<float> q(j->q_f16);
+      JobReq rq(q.data(), j->k, j->entries);
+      rq.dev_target = j->dev_target;
+      rq.last_of_call = true;
+      rq.tag = j->tag;
+      rq.no_f16 = rq.no_i8 = true;
+      int rc = job_enqueue(s, j, rq);
+      if (j->counted) {
+        s->inflight.fetch_sub(1);
+        j->counted = false;
+      }
+      if (rc) return rc;
+      HIPCHK(hipEventSynchronize(c->ev_done));
+      HIPCHK(hipGetLastError());
+    }
+  }
   if (j->f16) {
     // An fp16 scan whose candidate list overflowed (crowded neighbours: ties, near-duplicates) is NOT widened over its
     // fp16 keys: the query is redone through the f32 scan, whose own overflow handling follows below as ever.  Two
@@ -1781,7 +1968,7 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
 #endif
   if ((h->flags & FLAG_LIST_OVERFLOW) && j->leave_overflow && j->dev_target) {
     s->c_cands += std::min(h->count, h->entries);  // (the block stays as it is: see Job::leave_overflow)
-  } else if ((h->flags & FLAG_LIST_OVERFLOW) && j->route.exact) {
+  } else if ((h->flags & FLAG_LIST_OVERFLOW) && (j->route.exact || j->i8)) {
     // The wide pick emits every row up to its cut bin: ties by the hundred, or a k-th neighbour outside the histogram's
     // window, and the bin holds more rows than the block.  The keys and sums of all entries are still in the context:
     // exact_select_kernel ranks them and writes exactly min(k, live rows) entries -- into a block exact_applies sized for
@@ -2042,6 +2229,7 @@ void shard_destroy(Shard *s) {
   hipFree(s->d_live);
   hipFree(s->d_split);
   hipFree(s->d_rows16);
+  hipFree(s->d_rows8);
   hipFree(s->d_perm);
   hipFree(s->d_psq);
   hipFree(s->d_hub);
@@ -3283,6 +3471,14 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
     }
     return TSH_OK;
   }
+  if (option == TSH_OPT_SCAN_I8) {
+    if (value < 0 || value > 2) return set_err(TSH_E_BAD_ARG, "scan i8 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible scan)");
+    for (auto &sh : idx->shards) {
+      std::unique_lock<RwLock> xl(sh->mu);
+      sh->scan_i8 = (int)value;
+    }
+    return TSH_OK;
+  }
   if (option == TSH_OPT_BATCH_KERNEL) {
     if (value < 0 || value > 3) return set_err(TSH_E_BAD_ARG, "batch kernel must be 0 (f32 MFMA), 1 (bf16x3), 2 (f16) or 3 (auto)");
     for (auto &sh : idx->shards) {
@@ -3367,6 +3563,63 @@ int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out) {
     out[2] += s->c_f16_converted.load();
     std::lock_guard<std::mutex> lk(s->rows16_mu);
     out[3] += s->rows16_bytes;
+  }
+  return TSH_OK;
+}
+
+int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  for (auto &sp : idx->shards) {
+    Shard *s = sp.get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    out[0] += s->c_i8_scans.load();
+    out[1] += s->c_i8_redone.load();
+    out[2] += s->c_i8_converted.load();
+    std::lock_guard<std::mutex> lk(s->rows16_mu);
+    out[3] += s->rows8_bytes;
+  }
+  return TSH_OK;
+}
+
+int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper) {
+  if (!idx || idx->shards.size() != 1 || !query || !out_lower || !out_upper) return set_err(TSH_E_BAD_ARG, "bad arguments");
+  Shard *s = idx->shards[0].get();
+  std::shared_lock<RwLock> sl = share(idx, s);
+  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
+  Ctx *c = ctx_acquire(s, true);
+  CtxHold rel{s, c};
+  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
+  if (rc) return rc;
+  hipStream_t st = s->aux_stream;
+  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
+  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
+  if (!scan_i8_applies(s, 1, 1) || compute_band(s, c->h_query).force_all)
+    return set_err(TSH_E_BAD_ARG, "no int8 scan for this index / query (TSH_OPT_SCAN_I8, dead rows, row width, error model)");
+  const ScanI8Band ib = scan_i8_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, s->max_abs);
+  if (!ib.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the int8 scan's error model");
+  if (!rows8_ensure(s, st)) return set_err(TSH_E_OOM, "no room on the device for the int8 copy of the rows");
+  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
+  static thread_local ScanArgsQ sa;
+  fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
+  fill_scan_i8_args(s, ib, &sa);
+  launch_scan_i8(sa, s->nch, s->metric, st);
+  std::vector<uint32_t> keys((size_t)s->rows);
+  std::vector<float> w((size_t)s->rows);
+  HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
+  // (the rows' bands, by the arithmetic the kernel forms them with -- into the keys buffer, free again once copied)
+  float *d_w = reinterpret_cast<float *>(c->d_keys);
+  scan_i8_w_kernel<<<(unsigned)((s->rows + 255) / 256), 256, 0, st>>>(s->d_sqnorm, s->metric == TSH_METRIC_COSINE ? s->d_inv_norm : nullptr,
+                                                                     s->d_scale8, s->rows, ib.a_s, ib.a_v, ib.beta, d_w);
+  HIPCHK(hipMemcpyAsync(w.data(), d_w, (size_t)s->rows * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  // the upper side as the kernel forms it: (lower + w) + w would round twice -- the key itself is lower + w up to one
+  // rounding, which the band's own slack (1.001) covers on either side
+  for (int64_t i = 0; i < s->rows; ++i) {
+    const float lo = keys[(size_t)i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[(size_t)i]);
+    out_lower[i] = lo;
+    out_upper[i] = lo + 2.0f * w[(size_t)i];
   }
   return TSH_OK;
 }

@@ -156,6 +156,51 @@ void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipSt
   }
 }
 
+// The int8 scan: a row is a quarter of the bytes, two register buffers of eight rows are 16 * NCH VGPRs, and the launch
+// shape is the fp16 scan's (ScanShape of half as many chunks: as many bytes in flight per CU as there).  Rows of up to
+// eight chunks (d <= 2048): beyond that the two buffers and the query leave the register budget.
+template <int NCH> struct ScanI8Tune {
+  static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 6 ? 3 : 2);
+};
+template <int NCH, int METRIC, bool FULL>
+void launch_scan_i8_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev) {
+  using S = ScanShape<(NCH + 1) / 2>;
+  constexpr int MINW = ScanI8Tune<NCH>::MINW;
+  if (grid > 0) TSH_LAUNCH((scan_i8_kernel<NCH, METRIC, FULL, 4, MINW>), (a.a.n_tiles + S::WPB - 1) / S::WPB, 64 * S::WPB, S::LDS, s, ev, a);
+  else TSH_LAUNCH((scan_i8_kernel<NCH, METRIC, FULL, 4, MINW>), -grid, 64, 0, s, ev, a);
+}
+template <int NCH>
+void launch_scan_i8_n(const ScanArgsQ &a, int metric, int grid, hipStream_t s, const LaunchEv &ev) {
+  const bool full = a.a.d4 == NCH * 64;
+#define TSH_I8(M)                                                  \
+  do {                                                             \
+    if (full) launch_scan_i8_t<NCH, M, true>(a, grid, s, ev);      \
+    else launch_scan_i8_t<NCH, M, false>(a, grid, s, ev);          \
+  } while (0)
+  if (metric == TSH_METRIC_L2) TSH_I8(METRIC_L2);
+  else if (metric == TSH_METRIC_IP) TSH_I8(METRIC_IP);
+  else TSH_I8(METRIC_COS);
+#undef TSH_I8
+}
+
+bool scan_i8_supported(int nch) { return nch >= 1 && nch <= 8; }
+
+void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev) {
+  if (a.a.n_tiles <= 0) return;
+  int grid = 1;  // (> 0: the big shards' shape; < 0: one-wave workgroups)
+  if (a.a.n_tiles < SMALL_SHARD_TILES) grid = -std::max(1, (int)a.a.n_tiles);
+  switch (nch) {
+    case 1: launch_scan_i8_n<1>(a, metric, grid, s, ev); break;
+    case 2: launch_scan_i8_n<2>(a, metric, grid, s, ev); break;
+    case 3: launch_scan_i8_n<3>(a, metric, grid, s, ev); break;
+    case 4: launch_scan_i8_n<4>(a, metric, grid, s, ev); break;
+    case 5: launch_scan_i8_n<5>(a, metric, grid, s, ev); break;
+    case 6: launch_scan_i8_n<6>(a, metric, grid, s, ev); break;
+    case 7: launch_scan_i8_n<7>(a, metric, grid, s, ev); break;
+    default: launch_scan_i8_n<8>(a, metric, grid, s, ev); break;
+  }
+}
+
 bool scan_list_supported(int nch, int64_t ld) { return nch >= 1 && nch <= 8 && ld != 128 && ld != 64 && ld != 32; }
 
 void launch_scan_list(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev) {

@@ -104,6 +104,10 @@ typedef _ScanF16StatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
 typedef _ScanF16StatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanF16C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanF16D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _ScanI8StatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _ScanI8StatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
 typedef _SetOptionD = int Function(Pointer<Void>, int, int);
 typedef _BlockBytesC = Int64 Function(Int32);
@@ -310,6 +314,8 @@ final class HipVectorBackend {
   static late final _SetOptionD _setOption;
   static late final _ScanF16StatsD _scanF16Stats;
   static late final _ProbeScanF16D _probeScanF16;
+  static late final _ScanI8StatsD _scanI8Stats;
+  static late final _ProbeScanI8D _probeScanI8;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
   static late final _SearchShardD _searchShard;
@@ -366,6 +372,8 @@ final class HipVectorBackend {
       _setOption = lib.lookupFunction<_SetOptionC, _SetOptionD>('tsh_index_set_option');
       _scanF16Stats = lib.lookupFunction<_ScanF16StatsC, _ScanF16StatsD>('tsh_scan_f16_stats');
       _probeScanF16 = lib.lookupFunction<_ProbeScanF16C, _ProbeScanF16D>('tsh_probe_scan_f16_keys');
+      _scanI8Stats = lib.lookupFunction<_ScanI8StatsC, _ScanI8StatsD>('tsh_scan_i8_stats');
+      _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
       _searchShard = lib.lookupFunction<_SearchShardC, _SearchShardD>('tsh_search_shard');
@@ -809,7 +817,7 @@ final class HipVectorBackend {
 
   /// tsh_index_set_option: 1 = TSH_OPT_BATCH_MIN_NQ, 2 = TSH_OPT_BATCH_KERNEL, 4 = TSH_OPT_EXACT_SCAN_ROWS,
   /// 5 = TSH_OPT_EXACT_SELECT, 6 = TSH_OPT_BATCH_HUB, 7 = TSH_OPT_BATCH_GROUP, 8 = TSH_OPT_SCAN_F16,
-  /// 9 = TSH_OPT_SCAN_F16_MASKED (tuning only: results never depend on them).
+  /// 9 = TSH_OPT_SCAN_F16_MASKED, 10 = TSH_OPT_SCAN_I8 (tuning only: results never depend on them).
   bool setOption(int option, int value) => _setOption(_handle, option, value) == 0;
 
   /// The fp16 scan's counters (TSH_OPT_SCAN_F16): scans over the fp16 copy of the rows, queries redone through the
@@ -828,6 +836,23 @@ final class HipVectorBackend {
   /// `keys` and `w` hold one float per row.
   bool probeScanF16Keys(Pointer<Float> query, Pointer<Float> keys, Pointer<Float> w) =>
       _probeScanF16(_handle, query, keys, w) == 0;
+
+  /// The int8 scan's counters (TSH_OPT_SCAN_I8): scans over the int8 copy of the rows, queries redone through the
+  /// f32 scan, rows converted, bytes of the copy resident.
+  Map<String, int>? scanI8Stats() {
+    final o = calloc<Int64>(4);
+    try {
+      if (_scanI8Stats(_handle, o) != 0) return null;
+      return {'scans': o[0], 'redone': o[1], 'rowsConverted': o[2], 'copyBytes': o[3]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
+  /// Diagnostics: the two sides of the int8 scan's band around every row's key for one query; `lower` and `upper`
+  /// hold one float per row.
+  bool probeScanI8Keys(Pointer<Float> query, Pointer<Float> lower, Pointer<Float> upper) =>
+      _probeScanI8(_handle, query, lower, upper) == 0;
 
   int get nativeDimensions => _dim(_handle);
   int get nativeMetric => _metric(_handle);
