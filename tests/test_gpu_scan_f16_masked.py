@@ -161,6 +161,27 @@ def test_big_shard_launch_shapes(hip_lib, oracle_mod):
 
 
 @pytest.mark.parametrize("metric", [L2, COS])
+def test_row_with_a_wholly_empty_chunk(hip_lib, oracle_mod, metric):
+    """d = 2120 is 530 groups of four elements: nine chunks per row, scanned by the kernels for ten (the widths come from
+    a short list), so lanes 0-17 of chunk 8 hold data and chunk 9 none at all.  The f32 scan, the fp16 scan dense, and the
+    fp16 scan with tombstones on both sides of a tile edge."""
+    d, k = 2120, 10
+    n = 64 * TILE + 37
+    rng = np.random.default_rng(2120 + metric)
+    rows, qs = _corpus(rng, n, d, metric, nq=4, oracle_mod=oracle_mod)
+    ref = oracle_mod.search_heap_many_mt(rows, qs, metric, k)
+    with _open(d, metric, rows, mode=0, dense_mode=0) as idx:
+        _same(idx.search(qs, k), ref, "f32")
+        assert idx.scan_f16_stats()["scans"] == 0
+    with _open(d, metric, rows, dense_mode=2) as idx:
+        _search_f16(idx, qs, k, ref, None, "fp16, dense")
+        dead = np.union1d(np.unique(ref[0][:, :2]), np.arange(3 * TILE - 2, 3 * TILE + 2))
+        idx.set_deleted(dead)
+        live = ~np.isin(np.arange(n), dead)
+        _search_f16(idx, qs, k, oracle_mod.search_heap_many_mt(rows, qs, metric, k, None, _bits(live)), None, "fp16, tombstones")
+
+
+@pytest.mark.parametrize("metric", [L2, COS])
 def test_not_all_live_without_deletes(hip_lib, oracle_mod, metric):
     d, k = 768, 25
     rng = np.random.default_rng(41 + metric)

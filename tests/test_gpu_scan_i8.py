@@ -147,6 +147,23 @@ def test_k_around_the_number_of_tiles(hip_lib, oracle_mod):
             _ran(idx, s0, len(qs), "k=%d" % k)
 
 
+def test_big_shard_launch_shape(hip_lib, oracle_mod):
+    """From 6144 tiles on the scan is launched in the dense scans' shape -- several waves per workgroup, a workgroup per
+    two or four tiles -- where every shard above runs one-wave workgroups: the smallest such shard (d = 256: 403 MB of
+    rows), its last tile ragged."""
+    d, k, metric = 256, 20, L2
+    n = 6144 * 64 + 37
+    rng = np.random.default_rng(17)
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    rows *= rng.uniform(0.5, 2.0, size=(n, 1)).astype(np.float32)
+    qs = rng.standard_normal((4, d), dtype=np.float32)
+    ref = oracle_mod.search_heap_many_mt(rows, qs, metric, k)
+    with _open(d, metric, rows) as idx:
+        s0 = idx.scan_i8_stats()
+        _same(idx.search(qs, k), ref)
+        _ran(idx, s0, len(qs))
+
+
 @pytest.mark.parametrize("metric", [L2, IP, COS])
 def test_band_probe_on_midpoint_rows(hip_lib, metric):
     """Rows whose elements sit at quantisation midpoints (codes +/- 1/2), every error of the sign of its q_j: every exact

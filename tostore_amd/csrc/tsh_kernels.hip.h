@@ -149,6 +149,17 @@ struct ScanArgsQ {
 };
 static_assert(sizeof(ScanArgsQ) <= 4096, "kernel arguments are limited to 4 KiB");
 
+// The query of a scan kernel: a.query, or (NULL) the floats that ride in the kernel-argument segment behind the ScanArgs
+// (ScanArgsQ::q).  Takes the pointer, not the arguments: a helper that is handed `a` itself moves where the optimiser
+// sees the argument loads, and the kernels' code with them.
+__device__ __forceinline__ const float *scan_query_ptr(const float *query) {
+  if (!query) {
+    typedef const char __attribute__((address_space(4))) * karg_ptr;
+    query = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
+  }
+  return query;
+}
+
 // K1.  NCH >= ceil(d4/64) 16-byte chunks per lane per row.  FULL: d4 == NCH*64;
 // otherwise lanes past the row end re-read their chunk 0 (a cache hit) and the
 // value is zeroed, so there is no branch around any load.
@@ -164,154 +175,52 @@ static_assert(sizeof(ScanArgsQ) <= 4096, "kernel arguments are limited to 4 KiB"
     __builtin_amdgcn_sched_barrier(0);    \
   } while (0)
 
+// ---------------------------------------------------------------------------
+// scan_kernel, scan_f16_kernel and scan_i8_kernel are one skeleton -- lane setup, per tile its word and the pipelined
+// sum of its rows -- that lives in tsh_scan_tile.inc.h, over one of the row stores below, and an epilogue of their own
+// that turns a row's sum into the stored key or keys.
+// A row store: elem, an element in memory; chunk, the registers of one lane's load of four elements; widen, to f32,
+// called where the chunk is consumed; SUM, the metric the per-row sum is taken in (the reduced stores take dot products,
+// whatever the shard's metric).  (The helpers take values, not the ScanArgs: see scan_query_ptr.)
+template <int METRIC, bool NT>
+struct RowsF32 {  // 16-byte loads, 1 KiB per wave instruction
+  typedef float elem;
+  typedef f32x4 chunk;
+  static constexpr int SUM = METRIC;
+  static __device__ __forceinline__ const elem *rows(const float *rows, const void *) { return rows; }
+  static __device__ __forceinline__ chunk load(const elem *p) { return ld16<NT>(p); }
+  static __device__ __forceinline__ f32x4 widen(chunk x) { return x; }
+};
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+struct RowsF16 {  // the fp16 copy: 8-byte loads, 512 B per wave instruction
+  typedef _Float16 elem;
+  typedef f16x4 chunk;
+  static constexpr int SUM = METRIC_IP;
+  static __device__ __forceinline__ const elem *rows(const float *, const void *rows16) { return reinterpret_cast<const elem *>(rows16); }
+  static __device__ __forceinline__ chunk load(const elem *p) { return __builtin_nontemporal_load(reinterpret_cast<const chunk *>(p)); }
+  static __device__ __forceinline__ f32x4 widen(chunk x) { return __builtin_convertvector(x, f32x4); }
+};
+struct RowsI8 {  // the int8 copy, biased bytes: 4-byte loads, 256 B per wave instruction
+  typedef uint8_t elem;
+  typedef uint32_t chunk;
+  static constexpr int SUM = METRIC_IP;
+  static __device__ __forceinline__ const elem *rows(const float *, const void *rows8) { return reinterpret_cast<const elem *>(rows8); }
+  static __device__ __forceinline__ chunk load(const elem *p) { return __builtin_nontemporal_load(reinterpret_cast<const chunk *>(p)); }
+  static __device__ __forceinline__ f32x4 widen(chunk x) {
+    return f32x4{(float)(x & 255u), (float)((x >> 8) & 255u), (float)((x >> 16) & 255u), (float)(x >> 24)};
+  }
+};
+
+// K1 over the f32 rows
 template <int NCH, int METRIC, bool FULL, bool MASKED, int R, bool NT, int WAVES, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) scan_kernel(ScanArgsQ aq) {
-  static_assert(R == 2 || R == 4, "R must give an even number of groups per 8-row batch");
-  const ScanArgs &a = aq.a;
-  const float *qsrc = a.query;
-  if (!qsrc) {
-    typedef const char __attribute__((address_space(4))) * karg_ptr;
-    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
-  }
-  constexpr int G = 8 / R;  // groups per batch
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // WAVES bounds the workgroup size; small shards are launched with one wave
-  // per workgroup so the dispatcher can balance tiles across CUs
-  const int wpb = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
-  const int stride = gridDim.x * wpb;
-  // !FULL: the row ends inside chunk d4/64 and every later chunk is empty (NCH comes from a short list of
-  // widths, so more than the last chunk can lie beyond the row).  vmask bit c = this lane's 16 bytes of chunk
-  // c exist; lanes without them reload the row's first 16 bytes (valid memory) and contribute zeros.
-  uint32_t vmask = 0;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) vmask |= (FULL || c * 64 + lane < a.d4) ? (1u << c) : 0u;
-  auto has = [&](int c) { return FULL || ((vmask >> c) & 1u) != 0u; };
-  // (row and query pointers already include + 4 * lane: lanes without data fall back to element 0 of the row --
-  // 4 * lane floats further on may be past the end of the last row's allocation when rows are narrow)
-  auto off = [&](int c) { return has(c) ? c * 256 : -4 * lane; };
-  uint32_t loff[NCH];  // !FULL: this lane's float offset into a row, per chunk
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) loff[c] = has(c) ? (uint32_t)(4 * lane + c * 256) : 0u;
-
-  f32x4 q[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    q[c] = *reinterpret_cast<const f32x4 *>(qsrc + 4 * lane + off(c));
-    if (!has(c)) q[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  if (a.query_out && blockIdx.x == 0 && wave == 0) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (has(c))
-        *reinterpret_cast<f32x4 *>(a.query_out + 4 * lane + c * 256) = q[c];
-  }
-
-  // masked scans hand consecutive tiles to different WORKGROUPS: a contiguous id-range
-  // filter leaves one run of live tiles, which would otherwise land on a few CUs
+  typedef RowsF32<METRIC, NT> Store;
+#define TSH_SCAN_TILE_SETUP
+#include "tsh_scan_tile.inc.h"
   for (int t = MASKED ? wave * (int)gridDim.x + (int)blockIdx.x : (int)blockIdx.x * wpb + wave; t < a.n_tiles;
        t += stride) {
-    const float *tbase = a.rows + (int64_t)t * 64 * a.ld + 4 * lane;
-    uint64_t bits = ~0ull;
-    int cnt = 64;
-    if (MASKED) {
-      uint64_t w = a.live[t];
-      if (a.mask) w &= a.mask[t];
-      uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)w);
-      uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(w >> 32));
-      bits = ((uint64_t)hi << 32) | lo;
-      cnt = __popcll(bits);
-      if (cnt == 0) {
-        if (lane == 0) a.gmin[t] = KEY_DEAD;  // keys[] of a dead tile stay stale: every reader checks gmin first
-        continue;
-      }
-    }
-    const int nb = MASKED ? (cnt + 7) >> 3 : 8;  // 8-row batches, wave-uniform
-
-    f32x4 v[2][R][NCH];
-    uint64_t rem = bits;
-    int last = 0, next_dense = 0;
-    auto load_group = [&](int buf) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        int r;
-        if (MASKED) {  // next live row (a short last batch repeats the final row)
-          if (rem) {
-            last = __builtin_ctzll(rem);
-            rem &= rem - 1;
-          }
-          r = last;
-        } else {
-          r = next_dense++;
-        }
-        if (FULL) {
-          const float *rp = tbase + (int64_t)r * a.ld;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) v[buf][j][c] = ld16<NT>(rp + off(c));
-        } else {
-          // a lane's offset differs from chunk to chunk here (lanes past the row's end fall back to its start), which as
-          // a 64-bit address per row and chunk cost R x NCH register pairs and spilled (d = 384: 30 registers, d = 1000:
-          // 164; 0.62 / 0.42 of the HBM peak where full widths reach 0.82): the row's start is wave-uniform -- a scalar
-          // base -- and the lane's part a 32-bit offset per chunk, computed once
-          // (through readfirstlane: otherwise the optimiser derives the next row's addresses from this row's, per lane)
-          const uint64_t rbi = (uint64_t)(a.rows + ((int64_t)t * 64 + r) * a.ld);
-          const float *rb = reinterpret_cast<const float *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rbi >> 32)) << 32) |
-                                                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rbi));
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) v[buf][j][c] = ld16<NT>(rb + loff[c]);
-        }
-      }
-    };
-
-    float val = 0.f;
-    // The previous tile's key / gmin stores share vmcnt with the loads, and stores may retire out of order with
-    // loads: while one MIGHT be pending the compiler must wait for vmcnt(0) instead of counting.  Retire them here.
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    load_group(0);
-    // One 8-row batch.  The LAST batch is a separate instance without the trailing load instead of an `if` inside
-    // the loop: behind a branch the compiler's s_waitcnt insertion no longer knows which loads are in flight
-    // and waits for vmcnt(0) -- the group just issued included -- before every group's arithmetic.
-    auto batch = [&](int b, auto LAST) {
-      float acc[8];
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        if (!(decltype(LAST)::value && k == G - 1)) load_group((k + 1) & 1);
-        TSH_FENCE();
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-          float s = 0.f;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-            if (has(c)) s = accum4<METRIC>(s, q[c], v[k & 1][j][c]);  // (!FULL: lanes past the row's end sit the chunk out)
-          // tie the finished sum to the fence: pure math would otherwise be
-          // sunk below the next group's loads, keeping every buffer live
-          asm volatile("" : "+v"(s)::"memory");
-          acc[k * R + j] = s;
-        }
-        TSH_FENCE();
-      }
-      // octet partial of row (lane&7) of this batch, then across the 8 octets
-      float o = treduce8<0>(acc, lane);
-      o += __shfl_xor(o, 8);
-      o += __shfl_xor(o, 16);
-      o += __shfl_xor(o, 32);
-      if ((lane >> 3) == b) val = o;  // slot b*8 + (lane&7) == lane
-    };
-#pragma nounroll
-    for (int b = 0; b < nb - 1; ++b) batch(b, std::false_type{});
-    batch(nb - 1, std::true_type{});
-    // dense: val = key sum of row t*64+lane; masked: of the lane-th live row
-
-    bool alive;
-    if (MASKED) {
-      // expand compact slots back to row positions
-      uint64_t below = bits & ((1ull << lane) - 1ull);
-      int rank = __popcll(below);
-      val = __shfl(val, rank);
-      alive = (bits >> lane) & 1ull;
-    } else {
-      alive = (int64_t)t * 64 + lane < a.n;
-    }
+#define TSH_SCAN_TILE_SUM
+#include "tsh_scan_tile.inc.h"
     if (METRIC == METRIC_L2) {
       // nothing
     } else if (METRIC == METRIC_IP) {
@@ -329,158 +238,31 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_kernel(ScanArgsQ aq) {
 
 // ---------------------------------------------------------------------------
 // K1 over the fp16 copy of the rows (big shards' tile scans, dense or MASKED): half the HBM bytes per query.
-// scan_kernel's structure -- one wave per 64-row tile, two register buffers with the next group in flight, the
-// same fences and butterfly -- with 8-byte loads per lane: a lane holds the same four ELEMENTS of a chunk as in the
-// f32 kernel (chunk = 256 elements = 512 contiguous bytes per wave instruction), so NCH, FULL, the query registers
-// and the tail handling are the f32 kernel's.  The buffers hold the raw halves (two VGPRs per load); they are widened
-// where they are consumed, behind the fence, so a load never waits for its own conversion.
+// The skeleton over RowsF16: a lane holds the same four ELEMENTS of a chunk as in the f32 kernel (chunk = 256 elements =
+// 512 contiguous bytes per wave instruction), so NCH, FULL, the query registers and the tail handling are the f32
+// kernel's; the buffers hold the raw halves (two VGPRs per load).
 // All metrics are dot products here: acc = sum q_j * float(h_ij), h = fp16(S * v), in f32 FMAs; then
 //   L2      key = |v_i|^2 - 2 acc / S     (the common |q|^2 is left out: it orders nothing)
 //   IP      key = -acc / S
 //   cosine  key = -(acc / S) / |v_i|
 // and what is STORED is the upper side key + w_i of the band |key - exact| <= w_i = w_alpha |v_i| + w_beta that the
 // host proved for this query (tsh_scan_f16_band.h).  select_body then runs on upper sides.
-// MASKED is scan_kernel's: a tile's word is live & caller mask, only its live rows are loaded (in 8-row batches over
-// the compacted slots), dead lanes store KEY_DEAD and a dead tile only its gmin.  The band is per row and the norm
+// MASKED: dead lanes store KEY_DEAD and a dead tile only its gmin.  The band is per row and the norm
 // bounds cover every row ever ingested, so nothing of the error model depends on which rows are live; |row|^2 and
 // 1/|row| are read for live rows only (a quarantined row's are not finite, an absent row's were never written).
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float scan_f16_w(float alpha, float beta, float sqnorm) {
   return __builtin_fmaf(alpha, __builtin_sqrtf(sqnorm), beta);
 }
 
 template <int NCH, int METRIC, bool FULL, bool MASKED, int R, int WAVES, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) scan_f16_kernel(ScanArgsQ aq) {
-  static_assert(R == 2 || R == 4, "R must give an even number of groups per 8-row batch");
-  const ScanArgs &a = aq.a;
-  const float *qsrc = a.query;
-  if (!qsrc) {
-    typedef const char __attribute__((address_space(4))) * karg_ptr;
-    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
-  }
-  constexpr int G = 8 / R;
-  const _Float16 *rows16 = reinterpret_cast<const _Float16 *>(a.rows16);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wpb = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
-  const int stride = gridDim.x * wpb;
-  uint32_t vmask = 0;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) vmask |= (FULL || c * 64 + lane < a.d4) ? (1u << c) : 0u;
-  auto has = [&](int c) { return FULL || ((vmask >> c) & 1u) != 0u; };
-  auto off = [&](int c) { return has(c) ? c * 256 : -4 * lane; };
-  uint32_t loff[NCH];  // !FULL: this lane's element offset into a row, per chunk (lanes past the row's end: its start)
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) loff[c] = has(c) ? (uint32_t)(4 * lane + c * 256) : 0u;
-
-  f32x4 q[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    q[c] = *reinterpret_cast<const f32x4 *>(qsrc + 4 * lane + off(c));
-    if (!has(c)) q[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  if (a.query_out && blockIdx.x == 0 && wave == 0) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (has(c))
-        *reinterpret_cast<f32x4 *>(a.query_out + 4 * lane + c * 256) = q[c];
-  }
-
-  // (masked scans hand consecutive tiles to different workgroups: see scan_kernel)
+  typedef RowsF16 Store;
+#define TSH_SCAN_TILE_SETUP
+#include "tsh_scan_tile.inc.h"
   for (int t = MASKED ? wave * (int)gridDim.x + (int)blockIdx.x : (int)blockIdx.x * wpb + wave; t < a.n_tiles;
        t += stride) {
-    const _Float16 *tbase = rows16 + (int64_t)t * 64 * a.ld + 4 * lane;
-    uint64_t bits = ~0ull;
-    int cnt = 64;
-    if (MASKED) {
-      uint64_t w = a.live[t];
-      if (a.mask) w &= a.mask[t];
-      uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)w);
-      uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(w >> 32));
-      bits = ((uint64_t)hi << 32) | lo;
-      cnt = __popcll(bits);
-      if (cnt == 0) {
-        if (lane == 0) a.gmin[t] = KEY_DEAD;  // (keys[] of a dead tile stay stale: every reader checks gmin first)
-        continue;
-      }
-    }
-    const int nb = MASKED ? (cnt + 7) >> 3 : 8;  // 8-row batches, wave-uniform
-    f16x4 v[2][R][NCH];
-    uint64_t rem = bits;
-    int last = 0, next_dense = 0;
-    auto load_group = [&](int buf) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        int r;
-        if (MASKED) {  // next live row (a short last batch repeats the final row)
-          if (rem) {
-            last = __builtin_ctzll(rem);
-            rem &= rem - 1;
-          }
-          r = last;
-        } else {
-          r = next_dense++;
-        }
-        if (FULL) {
-          const _Float16 *rp = tbase + (int64_t)r * a.ld;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4 *>(rp + off(c)));
-        } else {
-          // (a scalar row base + one 32-bit lane offset per chunk: see scan_kernel)
-          const uint64_t rbi = (uint64_t)(rows16 + ((int64_t)t * 64 + r) * a.ld);
-          const _Float16 *rb = reinterpret_cast<const _Float16 *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rbi >> 32)) << 32) |
-                                                                  (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rbi));
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4 *>(rb + loff[c]));
-        }
-      }
-    };
-
-    float val = 0.f;
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the previous tile's stores (see scan_kernel)
-    load_group(0);
-    auto batch = [&](int b, auto LAST) {
-      float acc[8];
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        if (!(decltype(LAST)::value && k == G - 1)) load_group((k + 1) & 1);
-        TSH_FENCE();
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-          float s = 0.f;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-            if (has(c)) s = accum4<METRIC_IP>(s, q[c], __builtin_convertvector(v[k & 1][j][c], f32x4));
-          asm volatile("" : "+v"(s)::"memory");
-          acc[k * R + j] = s;
-        }
-        TSH_FENCE();
-      }
-      float o = treduce8<0>(acc, lane);
-      o += __shfl_xor(o, 8);
-      o += __shfl_xor(o, 16);
-      o += __shfl_xor(o, 32);
-      if ((lane >> 3) == b) val = o;
-    };
-#pragma nounroll
-    for (int b = 0; b < nb - 1; ++b) batch(b, std::false_type{});
-    batch(nb - 1, std::true_type{});
-    // dense: val = dot product of row t*64+lane; masked: of the lane-th live row
-
-    const int64_t row = (int64_t)t * 64 + lane;
-    bool alive;
-    if (MASKED) {
-      // expand compact slots back to row positions
-      uint64_t below = bits & ((1ull << lane) - 1ull);
-      int rank = __popcll(below);
-      val = __shfl(val, rank);
-      alive = (bits >> lane) & 1ull;
-    } else {
-      alive = row < a.n;
-    }
+#define TSH_SCAN_TILE_SUM
+#include "tsh_scan_tile.inc.h"
     const float dot = val * a.inv_scale;
     float x, w;
     if (METRIC == METRIC_COS) {
@@ -523,11 +305,10 @@ static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqn
 // K1 over the int8 copy of the rows (big shards' dense, all-live tile scans): a quarter of the f32 scan's HBM bytes.
 // A COARSE first pass: its keys only have to name a set of rows that provably holds the top k -- the survivors go
 // through the exact path (tsh_scan_i8.hip.h, tsh_exact.hip.h), so no second band and no re-rank follow it.
-// scan_f16_kernel's dense structure with 4-byte loads per lane: a lane holds the same four ELEMENTS of a chunk (chunk =
-// 256 elements = 256 contiguous bytes per wave instruction), so NCH, FULL, the query registers and the inline query are
-// the f32 kernel's.  A load is a quarter of the f32 kernel's bytes, so a register buffer holds R = 8 rows (a whole batch
-// of the butterfly) and two of them keep as many bytes in flight per wave as the fp16 kernel's two buffers of four rows.
-// The buffers hold the raw words; the bytes are widened where they are consumed, behind the fence.
+// The skeleton, dense, over RowsI8: a lane holds the same four ELEMENTS of a chunk (chunk = 256 elements = 256 contiguous
+// bytes per wave instruction).  A load is a quarter of the f32 kernel's bytes, so a register buffer holds R = 8 rows (a
+// whole batch of the butterfly) and two of them keep as many bytes in flight per wave as the fp16 kernel's two buffers
+// of four rows.
 // All metrics are dot products: acc = sum q_j * float(b_ij) over the biased bytes b = code + 128, in f32 FMAs; then with
 // t = acc - qbias (qbias = fl(128 sum q_j), from the host) and dot = scale8_i * t
 //   L2      key = |v_i|^2 - 2 dot        IP      key = -dot        cosine  key = -dot / |v_i|
@@ -536,104 +317,14 @@ static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqn
 // gmin, so every row of the top k has a lower side <= tau, and the threshold step needs no band arithmetic.
 template <int NCH, int METRIC, bool FULL, int WAVES, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) scan_i8_kernel(ScanArgsQ aq) {
-  const ScanArgs &a = aq.a;
-  const float *qsrc = a.query;
-  if (!qsrc) {
-    typedef const char __attribute__((address_space(4))) * karg_ptr;
-    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
-  }
+  typedef RowsI8 Store;
+  constexpr bool MASKED = false;
   constexpr int R = 8;
-  const uint8_t *rows8 = reinterpret_cast<const uint8_t *>(a.rows16);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wpb = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);
-  const int stride = gridDim.x * wpb;
-  uint32_t vmask = 0;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) vmask |= (FULL || c * 64 + lane < a.d4) ? (1u << c) : 0u;
-  auto has = [&](int c) { return FULL || ((vmask >> c) & 1u) != 0u; };
-  auto off = [&](int c) { return has(c) ? c * 256 : -4 * lane; };
-  uint32_t loff[NCH];  // !FULL: this lane's byte offset into a row, per chunk (lanes past the row's end: its start)
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) loff[c] = has(c) ? (uint32_t)(4 * lane + c * 256) : 0u;
-
-  f32x4 q[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    q[c] = *reinterpret_cast<const f32x4 *>(qsrc + 4 * lane + off(c));
-    if (!has(c)) q[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  if (a.query_out && blockIdx.x == 0 && wave == 0) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (has(c))
-        *reinterpret_cast<f32x4 *>(a.query_out + 4 * lane + c * 256) = q[c];
-  }
-
+#define TSH_SCAN_TILE_SETUP
+#include "tsh_scan_tile.inc.h"
   for (int t = (int)blockIdx.x * wpb + wave; t < a.n_tiles; t += stride) {
-    const uint8_t *tbase = rows8 + (int64_t)t * 64 * a.ld + 4 * lane;
-    uint32_t v[2][R][NCH];
-    int next_row = 0;
-    auto load_group = [&](int buf) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        const int r = next_row++;
-        if (FULL) {
-          const uint8_t *rp = tbase + (int64_t)r * a.ld;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(rp + off(c)));
-        } else {
-          // (a scalar row base + one 32-bit lane offset per chunk: see scan_kernel)
-          const uint64_t rbi = (uint64_t)(rows8 + ((int64_t)t * 64 + r) * a.ld);
-          const uint8_t *rb = reinterpret_cast<const uint8_t *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rbi >> 32)) << 32) |
-                                                                (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rbi));
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-            v[buf][j][c] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(rb + loff[c]));
-        }
-      }
-    };
-    float val = 0.f;
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the previous tile's stores (see scan_kernel)
-    load_group(0);
-    // eight rows: the other buffer's loads go out first, then this one's words are widened and consumed
-    auto group = [&](int b, auto BUF, auto LAST) {
-      constexpr int buf = decltype(BUF)::value;
-      if (!decltype(LAST)::value) load_group(buf ^ 1);
-      TSH_FENCE();
-      float acc[8];
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-          if (has(c)) {
-            const uint32_t x = v[buf][j][c];
-            const f32x4 f = f32x4{(float)(x & 255u), (float)((x >> 8) & 255u), (float)((x >> 16) & 255u), (float)(x >> 24)};
-            s = accum4<METRIC_IP>(s, q[c], f);
-          }
-        asm volatile("" : "+v"(s)::"memory");
-        acc[j] = s;
-      }
-      TSH_FENCE();
-      float o = treduce8<0>(acc, lane);
-      o += __shfl_xor(o, 8);
-      o += __shfl_xor(o, 16);
-      o += __shfl_xor(o, 32);
-      if ((lane >> 3) == b) val = o;
-    };
-#pragma nounroll
-    for (int b = 0; b < 6; b += 2) {
-      group(b, std::integral_constant<int, 0>{}, std::false_type{});
-      group(b + 1, std::integral_constant<int, 1>{}, std::false_type{});
-    }
-    group(6, std::integral_constant<int, 0>{}, std::false_type{});
-    group(7, std::integral_constant<int, 1>{}, std::true_type{});
-    // val = sum q_j b_ij of row t*64+lane
-
-    const int64_t row = (int64_t)t * 64 + lane;
-    const bool alive = row < a.n;
+#define TSH_SCAN_TILE_SUM
+#include "tsh_scan_tile.inc.h"
     const float sc = alive ? a.scale8[row] : 0.f;
     const float dot = sc * (val - a.inv_scale);
     float x, w;
@@ -714,11 +405,7 @@ __global__ void __launch_bounds__(512, 2) scan_list_kernel(ScanArgsQ aq) {
   static_assert(R == 2 || R == 4, "R must give an even number of groups per 8-row batch");
   static_assert(2 * R * NCH * 4 + NCH * 4 <= 200, "two register buffers + the query within 256 VGPRs");
   const ScanArgs &a = aq.a;
-  const float *qsrc = a.query;
-  if (!qsrc) {
-    typedef const char __attribute__((address_space(4))) * karg_ptr;
-    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
-  }
+  const float *qsrc = scan_query_ptr(a.query);
   constexpr int G = 8 / R;
   __shared__ uint32_t s_min[8];
   const int lane = threadIdx.x & 63;
@@ -818,11 +505,7 @@ __global__ void __launch_bounds__(256, 4) scan_packed_kernel(ScanArgsQ aq) {
   constexpr int LPR = 64 >> SPLIT;           // lanes per real row
   constexpr int NB = 8 >> SPLIT;             // batches of 8 virtual rows per 64-row tile
   const ScanArgs &a = aq.a;
-  const float *qsrc = a.query;
-  if (!qsrc) {
-    typedef const char __attribute__((address_space(4))) * karg_ptr;
-    qsrc = (const float *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(ScanArgsQ, q));
-  }
+  const float *qsrc = scan_query_ptr(a.query);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wpb = __builtin_amdgcn_readfirstlane((int)blockDim.x >> 6);

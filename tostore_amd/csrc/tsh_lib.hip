@@ -341,6 +341,22 @@ struct DeviceStreams {
 DeviceStreams *device_streams(int device);  // defined after set_err / HIPCHK users below
 void device_streams_release(int device);
 
+// What a shard keeps per reduced-precision scan route (the fp16 copy's, the int8 copy's).  A scan of the route whose
+// list overflowed is redone through the f32 scan (redo_overflowed_scan); two such scans in a row and the shard's next
+// SCAN_ROUTE_DENIED_SCANS eligible scans skip the route.
+constexpr int SCAN_ROUTE_DENIED_SCANS = 256;
+struct ScanRouteState {
+  std::atomic<int64_t> scans{0}, redone{0};
+  std::atomic<int> strikes{0};  // scans in a row whose list overflowed
+  std::atomic<int> denied{0};   // eligible scans left that skip the route
+  // an eligible scan uses up a denial, if any are left, whatever its band
+  bool take_denial() {
+    if (denied.load() <= 0) return false;
+    denied.fetch_sub(1);
+    return true;
+  }
+};
+
 struct Shard {
   int device = 0;
   int dim = 0, metric = 0, nch = 0;
@@ -474,9 +490,8 @@ struct Shard {
   int scan_f16 = 1;  // TSH_OPT_SCAN_F16: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible dense scan
   int scan_f16_masked = 1;  // TSH_OPT_SCAN_F16_MASKED: the same three for tile scans behind a mask, tombstones, quarantined
                             // rows or gaps (none of them while scan_f16 == 0)
-  std::atomic<int64_t> c_f16_scans{0}, c_f16_redone{0}, c_f16_converted{0};
-  std::atomic<int> scan_f16_strikes{0};  // fp16 scans in a row whose candidate list overflowed
-  std::atomic<int> scan_f16_denied{0};   // eligible scans left that go straight to f32 (two overflows in a row: 256)
+  std::atomic<int64_t> c_f16_converted{0};
+  ScanRouteState route_f16;  // (overflow: of the candidate list)
   // The int8 copy of the rows that big shards' dense, all-live single-query scans read as a coarse first pass
   // (scan_i8_kernel): row-major, ld biased bytes per row, and behind them (same allocation) a scale per row.  Kept
   // current exactly like the fp16 copy (rows8_ensure / rows16_ensure share row_copy_ensure, and rows16_mu guards both).
@@ -488,9 +503,8 @@ struct Shard {
 #define TSH_SCAN_I8_DEFAULT 1  // (A/B builds: -DTSH_SCAN_I8_DEFAULT=0, a variant library of its own -- tostore_amd/build.py)
 #endif
   int scan_i8 = TSH_SCAN_I8_DEFAULT;  // TSH_OPT_SCAN_I8: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible scan
-  std::atomic<int64_t> c_i8_scans{0}, c_i8_redone{0}, c_i8_converted{0};
-  std::atomic<int> scan_i8_strikes{0};  // int8 scans in a row whose survivor list overflowed
-  std::atomic<int> scan_i8_denied{0};   // eligible scans left that skip the route (two overflows in a row: 256)
+  std::atomic<int64_t> c_i8_converted{0};
+  ScanRouteState route_i8;  // (overflow: of the survivor list)
 
   bool safe_mode() const {
     if (nonfinite_rows) return true;
@@ -1039,6 +1053,8 @@ struct ShardMask {
   bool listed() const { return list.ids || list.d_ids; }
 };
 
+enum class RowStore { F32, F16, I8 };  // which copy of the rows a tile scan reads
+
 // One query in flight on one context.  Its three kernels (scan, select,
 // rerank) are enqueued back to back on the shard's single in-order pipeline
 // stream with NO copy and NO cross-stream dependency between them: the query
@@ -1063,11 +1079,11 @@ struct Job {
                                 // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
                                 // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
                                 // redoing the group with larger blocks, not ahead
-  bool i8 = false;         // scanned over the int8 copy, survivors through the exact path (q_f16 / tag: the redo's)
-  bool f16 = false;        // scanned over the fp16 copy (scan_f16_kernel): a list overflow is redone through the f32 scan,
-  std::vector<float> q_f16;  // from this copy of the query, with this tag
+  RowStore store = RowStore::F32;  // the copy of the rows its tile scan read (I8: survivors through the exact path).
+                                   // A list overflow of an F16 / I8 scan is redone through the f32 scan,
+  std::vector<float> redo_q;  // from this copy of the query, with this tag
   uint32_t tag = 0;
-  ShardMask mask_f16;      // ... behind the same mask: a handle's part, or the context's own copy of a pointer mask's words
+  ShardMask redo_mask;     // ... behind the same mask: a handle's part, or the context's own copy of a pointer mask's words
                            // (job_enqueue: the caller's slice may be gone when a ticket is waited for)
   hipStream_t last_stream = nullptr;  // where the job's last kernel was enqueued (ev_done rides on it)
   uint64_t enq_seq = 0;               // ... and its place in the device's enqueue order (DeviceStreams::enq_counter)
@@ -1264,7 +1280,6 @@ void launch_exact_scan(const ExactArgsQ &xa, int metric, hipStream_t st, const L
 inline bool alloc_fault(int64_t bytes);      // tsh_host_batch.inl.h
 inline bool device_has_room(int64_t bytes);
 constexpr int64_t SCAN_F16_MIN_BYTES = 256ll << 20;  // the Infinity Cache: a row store below it is not HBM-bound
-constexpr int SCAN_F16_DENIED_SCANS = 256;
 
 // Could a tile scan of this shard read the fp16 copy?  masked: behind a caller's mask, tombstones, quarantined rows or
 // gaps -- TSH_OPT_SCAN_F16_MASKED decides for those, TSH_OPT_SCAN_F16 for dense scans and, at 0, for both.  (The shard's
@@ -1352,7 +1367,6 @@ bool rows8_ensure(Shard *s, hipStream_t st) {
 
 // Could a scan of this shard take the coarse int8 route?  Dense and all-live only (the callers know about masks); the
 // exact path behind it needs a block of at least k entries.  (The shard's side of the decision: caller holds s->mu)
-constexpr int SCAN_I8_DENIED_SCANS = 256;
 bool scan_i8_applies(const Shard *s, int32_t k, int32_t entries) {
   if (s->scan_i8 == 0 || s->rows8_denied || s->safe_mode() || !s->all_live || !s->quar_ids.empty()) return false;
   if (!scan_i8_supported(s->nch) || k > entries || k > I8_LIST_CAP || s->rows <= 0) return false;
@@ -1561,8 +1575,8 @@ void fill_job_args(const Shard *s, Job *j, const JobReq &rq, const float *q, Job
   se.metric = s->metric;
   se.row_base = s->row_base;
   se.shard_rows = s->rows;
-  if (j->f16) fill_scan_f16_args(s, r.fb, &ka->sa, &se);
-  if (j->i8) {
+  if (j->store == RowStore::F16) fill_scan_f16_args(s, r.fb, &ka->sa, &se);
+  if (j->store == RowStore::I8) {
     // the coarse scan, then E1 + E2 / E2' over the survivor list: I8_LIST_CAP entries, the padding dead.  E1 reads the
     // query's device copy (the scan's workgroup 0 leaves it, or it was uploaded in front of the scan)
     fill_scan_i8_args(s, r.ib, &ka->sa);
@@ -1655,9 +1669,11 @@ int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipSt
   else if (j->route.use_list) launch_scan_list(ka.sa, s->nch, s->metric, ps, ev);
   else {
     const bool ml = j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows);
-    if (j->i8) launch_scan_i8(ka.sa, s->nch, s->metric, ps, ev);
-    else if (j->f16) launch_scan_f16(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
-    else launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml);
+    switch (j->store) {
+      case RowStore::I8: launch_scan_i8(ka.sa, s->nch, s->metric, ps, ev); break;
+      case RowStore::F16: launch_scan_f16(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml); break;
+      case RowStore::F32: launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml); break;
+    }
   }
   return TSH_OK;
 }
@@ -1672,7 +1688,8 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
   Ctx *c = j->c;
   const bool quar = !j->quar_sel.empty();
   const hipEvent_t none = nullptr, done = quar ? none : c->ev_done;
-  if (j->i8) {
+  const bool i8 = j->store == RowStore::I8;
+  if (i8) {
     // threshold, survivors' ballot words, their count and ascending list (capped and padded by M2), E1 over the list
     const int32_t n_tiles = ka.sa.a.n_tiles, n_blocks = (n_tiles + MASK_BLOCK_WORDS - 1) / MASK_BLOCK_WORDS;
     if (n_tiles <= SEL_VPT * SEL_THREADS) i8_tau_kernel<true><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
@@ -1686,7 +1703,7 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
   if (j->route.picked) {  // E2': one workgroup per 256 entries, a bound from E1's wave minima, no ranking below it
     const ExactPickArgs xp = exact_pick_args(j->xsel, c);
     TSH_LAUNCH_EV(exact_pick_kernel, (unsigned)((xp.n_entries + 255) / 256), 256, ts, none, done, xp);
-  } else if (j->route.exact || j->i8) {
+  } else if (j->route.exact || i8) {
     TSH_LAUNCH_EV(exact_select_kernel, 1, 1024, ts, none, done, j->xsel);
   } else {
     launch_select(ka.se, ka.se.n_tiles, ts);
@@ -1708,31 +1725,29 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   float *q;
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
-  // (an eligible scan uses up a denial of the int8 route, if any are left, whatever its band; a scan that takes the
+  // (an eligible scan uses up a denial of its route, if any are left, whatever its band; a scan that takes the int8
   // route neither asks for the fp16 copy nor touches the fp16 route's denials)
-  const bool denied8 = r.i8_eligible && s->scan_i8_denied.load() > 0;
-  if (denied8) s->scan_i8_denied.fetch_sub(1);
-  j->i8 = r.i8_eligible && !denied8 && r.ib.ok && rows8_ensure(s, s->scan_stream);
-  if (j->i8 && ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c, (s->rows + 63) / 64)))) return rc;
-  if (!j->i8 && !r.exact) j->route.picked = false;
-  // (an eligible scan uses up a denial, if any are left, whatever its band)
-  const bool denied = !j->i8 && r.f16_eligible && s->scan_f16_denied.load() > 0;
-  if (denied) s->scan_f16_denied.fetch_sub(1);
-  j->f16 = !j->i8 && r.f16_eligible && !denied && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp);
-  if (j->i8) {
-    j->q_f16.assign(rq.query, rq.query + s->dim);
-    j->tag = rq.tag;
+  j->store = RowStore::F32;
+  if (r.i8_eligible && !s->route_i8.take_denial() && r.ib.ok && rows8_ensure(s, s->scan_stream)) {
+    j->store = RowStore::I8;
+    if ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c, (s->rows + 63) / 64))) return rc;
+  } else {
+    if (!r.exact) j->route.picked = false;
+    if (r.f16_eligible && !s->route_f16.take_denial() && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp)) j->store = RowStore::F16;
   }
-  if (j->f16) {
-    j->q_f16.assign(rq.query, rq.query + s->dim);
+  if (j->store != RowStore::F32) {  // what a redo needs (redo_overflowed_scan)
+    j->redo_q.assign(rq.query, rq.query + s->dim);
     j->tag = rq.tag;
-    // (no list: an fp16 scan walks tiles, and so does its redo.  A pointer mask's words were staged in c->h_mask under
-    // rq.mask.epoch -- by this job or an earlier one of the call -- and stay there while the job holds the context)
-    j->mask_f16 = ShardMask();
-    j->mask_f16.words = rq.mask.part ? rq.mask.words : (rq.mask.words ? c->h_mask : nullptr);
-    j->mask_f16.epoch = rq.mask.epoch;
-    j->mask_f16.rows_est = rq.mask.rows_est;
-    j->mask_f16.part = rq.mask.part;
+    // (no list: such a scan walks tiles, and so does its redo.  A pointer mask's words were staged in c->h_mask under
+    // rq.mask.epoch -- by this job or an earlier one of the call -- and stay there while the job holds the context.
+    // An int8 scan has no mask)
+    j->redo_mask = ShardMask();
+    if (j->store == RowStore::F16) {
+      j->redo_mask.words = rq.mask.part ? rq.mask.words : (rq.mask.words ? c->h_mask : nullptr);
+      j->redo_mask.epoch = rq.mask.epoch;
+      j->redo_mask.rows_est = rq.mask.rows_est;
+      j->redo_mask.part = rq.mask.part;
+    }
   }
   fill_job_args(s, j, rq, q, &ka);
   // with other queries already in flight -- or the caller about to submit more (the first query of a multi-query
@@ -1765,8 +1780,8 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   s->c_scans++;
   if (r.use_list) s->c_list_scans++;
   if (r.exact) s->c_exact_scans++;
-  if (j->f16) s->c_f16_scans++;
-  if (j->i8) s->c_i8_scans++;
+  if (j->store == RowStore::F16) s->route_f16.scans++;
+  if (j->store == RowStore::I8) s->route_i8.scans++;
   return TSH_OK;
 }
 
@@ -1879,6 +1894,44 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
   return TSH_OK;
 }
 
+// A finished fp16 or int8 scan (j->store) whose list overflowed -- the fp16 scan's candidate list (crowded neighbours:
+// ties, near-duplicates), the int8 scan's survivor list (the same, or fewer live tiles than k in a big shard) -- is NOT
+// widened over its reduced keys: the query is redone through the f32 scan, from the job's saved query, tag and mask, and
+// the f32 scan's own overflow handling follows in job_finish as ever.  Books the route's strike or denial.
+int redo_overflowed_scan(Shard *s, Job *j) {
+  Ctx *c = j->c;
+  const bool i8 = j->store == RowStore::I8;
+  ScanRouteState &rt = i8 ? s->route_i8 : s->route_f16;
+  const BlockHeader *h = reinterpret_cast<const BlockHeader *>(c->h_block);
+  if (!(h->flags & (i8 ? FLAG_I8_OVERFLOW : FLAG_LIST_OVERFLOW))) {
+    rt.strikes.store(0);
+    return TSH_OK;
+  }
+  if (j->leave_overflow && j->dev_target) return TSH_OK;  // (left as it is: see Job::leave_overflow)
+  rt.redone++;
+  if (rt.strikes.fetch_add(1) + 1 >= 2) {
+    rt.strikes.store(0);
+    rt.denied.store(SCAN_ROUTE_DENIED_SCANS);
+  }
+  const std::vector<float> q(j->redo_q);
+  JobReq rq(q.data(), j->k, j->entries);
+  rq.mask = j->redo_mask;  // the WHERE clause holds for the redo too
+  rq.dev_target = j->dev_target;
+  rq.last_of_call = true;
+  rq.tag = j->tag;
+  rq.no_f16 = true;
+  rq.no_i8 = i8;
+  int rc = job_enqueue(s, j, rq);
+  if (j->counted) {
+    s->inflight.fetch_sub(1);
+    j->counted = false;
+  }
+  if (rc) return rc;
+  HIPCHK(hipEventSynchronize(c->ev_done));
+  HIPCHK(hipGetLastError());
+  return TSH_OK;
+}
+
 // Waits for a job; afterwards c->h_block / c->d_block hold the final block
 // (and *spill every candidate when they did not fit); *extra gets the quarantined rows' entries.
 int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<BlockEntry> *extra) {
@@ -1890,66 +1943,9 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipEventSynchronize(c->ev_done));
   HIPCHK(hipGetLastError());
-  if (j->i8) {
-    // An int8 scan whose survivors did not fit their list (crowded neighbours; fewer live tiles than k in a big shard): the
-    // query is redone through the f32 scan, as an fp16 overflow is.  Two in a row and the shard's next
-    // SCAN_I8_DENIED_SCANS eligible scans skip the route.
-    const BlockHeader *h8 = reinterpret_cast<const BlockHeader *>(c->h_block);
-    const bool over = (h8->flags & FLAG_I8_OVERFLOW) != 0;
-    if (!over) {
-      s->scan_i8_strikes.store(0);
-    } else if (!(j->leave_overflow && j->dev_target)) {  // (left as it is: see Job::leave_overflow)
-      s->c_i8_redone++;
-      if (s->scan_i8_strikes.fetch_add(1) + 1 >= 2) {
-        s->scan_i8_strikes.store(0);
-        s->scan_i8_denied.store(SCAN_I8_DENIED_SCANS);
-      }
-      const std::vector<float> q(j->q_f16);
-      JobReq rq(q.data(), j->k, j->entries);
-      rq.dev_target = j->dev_target;
-      rq.last_of_call = true;
-      rq.tag = j->tag;
-      rq.no_f16 = rq.no_i8 = true;
-      int rc = job_enqueue(s, j, rq);
-      if (j->counted) {
-        s->inflight.fetch_sub(1);
-        j->counted = false;
-      }
-      if (rc) return rc;
-      HIPCHK(hipEventSynchronize(c->ev_done));
-      HIPCHK(hipGetLastError());
-    }
-  }
-  if (j->f16) {
-    // An fp16 scan whose candidate list overflowed (crowded neighbours: ties, near-duplicates) is NOT widened over its
-    // fp16 keys: the query is redone through the f32 scan, whose own overflow handling follows below as ever.  Two
-    // such queries in a row and the shard's next SCAN_F16_DENIED_SCANS eligible scans go straight to f32.
-    const BlockHeader *h16 = reinterpret_cast<const BlockHeader *>(c->h_block);
-    const bool over = (h16->flags & FLAG_LIST_OVERFLOW) != 0;
-    if (!over) {
-      s->scan_f16_strikes.store(0);
-    } else if (!(j->leave_overflow && j->dev_target)) {  // (left as it is: see Job::leave_overflow)
-      s->c_f16_redone++;
-      if (s->scan_f16_strikes.fetch_add(1) + 1 >= 2) {
-        s->scan_f16_strikes.store(0);
-        s->scan_f16_denied.store(SCAN_F16_DENIED_SCANS);
-      }
-      const std::vector<float> q(j->q_f16);
-      JobReq rq(q.data(), j->k, j->entries);
-      rq.mask = j->mask_f16;  // the WHERE clause holds for the redo too
-      rq.dev_target = j->dev_target;
-      rq.last_of_call = true;
-      rq.tag = j->tag;
-      rq.no_f16 = true;
-      int rc = job_enqueue(s, j, rq);
-      if (j->counted) {
-        s->inflight.fetch_sub(1);
-        j->counted = false;
-      }
-      if (rc) return rc;
-      HIPCHK(hipEventSynchronize(c->ev_done));
-      HIPCHK(hipGetLastError());
-    }
+  if (j->store != RowStore::F32) {
+    int rc = redo_overflowed_scan(s, j);
+    if (rc) return rc;
   }
   if (j->timed) {
     float ms = 0.f;
@@ -1968,7 +1964,7 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
 #endif
   if ((h->flags & FLAG_LIST_OVERFLOW) && j->leave_overflow && j->dev_target) {
     s->c_cands += std::min(h->count, h->entries);  // (the block stays as it is: see Job::leave_overflow)
-  } else if ((h->flags & FLAG_LIST_OVERFLOW) && (j->route.exact || j->i8)) {
+  } else if ((h->flags & FLAG_LIST_OVERFLOW) && (j->route.exact || j->store == RowStore::I8)) {
     // The wide pick emits every row up to its cut bin: ties by the hundred, or a k-th neighbour outside the histogram's
     // window, and the bin holds more rows than the block.  The keys and sums of all entries are still in the context:
     // exact_select_kernel ranks them and writes exactly min(k, live rows) entries -- into a block exact_applies sized for
@@ -3558,8 +3554,8 @@ int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out) {
   for (auto &sp : idx->shards) {
     Shard *s = sp.get();
     std::shared_lock<RwLock> sl = share(idx, s);
-    out[0] += s->c_f16_scans.load();
-    out[1] += s->c_f16_redone.load();
+    out[0] += s->route_f16.scans.load();
+    out[1] += s->route_f16.redone.load();
     out[2] += s->c_f16_converted.load();
     std::lock_guard<std::mutex> lk(s->rows16_mu);
     out[3] += s->rows16_bytes;
@@ -3573,8 +3569,8 @@ int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out) {
   for (auto &sp : idx->shards) {
     Shard *s = sp.get();
     std::shared_lock<RwLock> sl = share(idx, s);
-    out[0] += s->c_i8_scans.load();
-    out[1] += s->c_i8_redone.load();
+    out[0] += s->route_i8.scans.load();
+    out[1] += s->route_i8.redone.load();
     out[2] += s->c_i8_converted.load();
     std::lock_guard<std::mutex> lk(s->rows16_mu);
     out[3] += s->rows8_bytes;

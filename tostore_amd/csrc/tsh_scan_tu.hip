@@ -11,13 +11,6 @@
 namespace tsh {
 namespace {
 
-// (rows per group, min waves per SIMD) per row width: two register buffers of
-// R*NCH*4 VGPRs plus NCH*4 for the query must fit 512/MINW registers.
-template <int NCH, bool MASKED> struct ScanTune {
-  static constexpr int R = (NCH <= 2) ? 4 : (NCH == 3 ? (MASKED ? 2 : 4) : 2);
-  static constexpr int MINW =
-      (NCH <= 2) ? 4 : (NCH == 3 ? (MASKED ? 4 : 3) : (NCH == 4 ? 4 : (NCH <= 6 ? 3 : (NCH <= 8 ? 2 : 1))));
-};
 #define TSH_LAUNCH(KERN, GRID, BLOCK, LDS, ST, EV, ARG)                                                  \
   do {                                                                                                  \
     if ((EV).start || (EV).stop)                                                                        \
@@ -44,35 +37,111 @@ template <int NCH> struct ScanShape {
   static constexpr int LDS = NCH == 1 ? 0 : (NCH == 2 ? 32768 : 65536);  // 160 KB per CU: 4 resp. 2 workgroups
 };
 
-template <int NCH, int METRIC, bool FULL, bool MASKED>
-void launch_scan_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev, bool mostly_live) {
-  using T = ScanTune<NCH, MASKED>;
-  // grid > 0: a big shard -- dense scans in the shape of ScanShape, masked ones in 4-wave workgroups;
-  // grid < 0: -grid one-wave workgroups (small shards)
-  using S = ScanShape<NCH>;
-  if (grid > 0 && (!MASKED || mostly_live))
-    TSH_LAUNCH((scan_kernel<NCH, METRIC, FULL, MASKED, T::R, true, 4, T::MINW>), (a.a.n_tiles + S::WPB - 1) / S::WPB,
-               64 * S::WPB, S::LDS, s, ev, a);
-  else if (grid > 0) TSH_LAUNCH((scan_kernel<NCH, METRIC, FULL, MASKED, T::R, true, 4, T::MINW>), grid, 256, 0, s, ev, a);
-  else TSH_LAUNCH((scan_kernel<NCH, METRIC, FULL, MASKED, T::R, true, 4, T::MINW>), -grid, 64, 0, s, ev, a);
-}
-template <int NCH, int METRIC>
-void launch_scan_m(const ScanArgsQ &a, bool masked, int grid, hipStream_t s, const LaunchEv &ev, bool ml) {
-  bool full = a.a.d4 == NCH * 64;
-  if (full) {
-    if (masked) launch_scan_t<NCH, METRIC, true, true>(a, grid, s, ev, ml);
-    else launch_scan_t<NCH, METRIC, true, false>(a, grid, s, ev, ml);
-  } else {
-    if (masked) launch_scan_t<NCH, METRIC, false, true>(a, grid, s, ev, ml);
-    else launch_scan_t<NCH, METRIC, false, false>(a, grid, s, ev, ml);
+// A family of tile-scan kernels, as the launcher below sees it: the kernel for (NCH, METRIC, FULL, MASKED) with its
+// (rows per group R, min waves per SIMD) per row width, the ScanShape it is launched in, whether masked instantiations
+// exist, and the widest NCH (widths: 1-8, 10, 12, 14, 16 up to MAX_NCH).
+struct ScanF32 {
+  // two register buffers of R*NCH*4 VGPRs plus NCH*4 for the query must fit 512/MINW registers.
+  template <int NCH, bool MASKED> struct Tune {
+    static constexpr int R = (NCH <= 2) ? 4 : (NCH == 3 ? (MASKED ? 2 : 4) : 2);
+    static constexpr int MINW =
+        (NCH <= 2) ? 4 : (NCH == 3 ? (MASKED ? 4 : 3) : (NCH == 4 ? 4 : (NCH <= 6 ? 3 : (NCH <= 8 ? 2 : 1))));
+  };
+  template <int NCH> using Shape = ScanShape<NCH>;
+  static constexpr bool HAS_MASKED = true;
+  static constexpr int MAX_NCH = 16;
+  template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
+    using T = Tune<NCH, MASKED>;
+    return &scan_kernel<NCH, METRIC, FULL, MASKED, T::R, true, 4, T::MINW>;
   }
+};
+// The fp16 scan: a row is half the bytes, so two register buffers of R rows are R*NCH*2 VGPRs each, and the launch shape
+// is ScanShape's for a row of half as many 1 KiB chunks (d = 768: 1.5 KiB rows, eight waves per CU; d = 1536: four).
+// MASKED: the same (R, MINW) at every width -- the masked instantiations fit the dense ones' register budgets without
+// scratch (the compiler's resource-usage remarks: profiles/scan_f16_masked_resources.txt).
+struct ScanF16 {
+  template <int NCH, bool MASKED> struct Tune {
+    static constexpr int R = NCH <= 6 ? 4 : 2;
+    static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 8 ? 3 : 2);
+  };
+  template <int NCH> using Shape = ScanShape<(NCH + 1) / 2>;
+  static constexpr bool HAS_MASKED = true;
+  static constexpr int MAX_NCH = 14;  // (wider rows that end inside a chunk would spill: they stay on f32)
+  template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
+    using T = Tune<NCH, MASKED>;
+    return &scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>;
+  }
+};
+// The int8 scan: a row is a quarter of the bytes, two register buffers of eight rows are 16 * NCH VGPRs, and the launch
+// shape is the fp16 scan's (ScanShape of half as many chunks: as many bytes in flight per CU as there).  Rows of up to
+// eight chunks (d <= 2048): beyond that the two buffers and the query leave the register budget.  Dense only.
+struct ScanI8 {
+  template <int NCH> struct Tune {
+    static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 6 ? 3 : 2);
+  };
+  template <int NCH> using Shape = ScanShape<(NCH + 1) / 2>;
+  static constexpr bool HAS_MASKED = false;
+  static constexpr int MAX_NCH = 8;
+  template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
+    return &scan_i8_kernel<NCH, METRIC, FULL, 4, Tune<NCH>::MINW>;
+  }
+};
+
+// grid > 0: a big shard -- dense and mostly-live scans in the shape of ScanShape, scattered masked ones in `grid` 4-wave
+// workgroups; grid < 0: -grid one-wave workgroups (small shards)
+// (the middle branch is never taken by a dense instantiation)
+template <class F, int NCH, int METRIC, bool FULL, bool MASKED>
+void launch_tile_scan_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev, bool mostly_live) {
+  using S = typename F::template Shape<NCH>;
+  constexpr auto kern = F::template kernel<NCH, METRIC, FULL, MASKED>();
+  if (grid > 0 && (!MASKED || mostly_live))
+    TSH_LAUNCH(kern, (a.a.n_tiles + S::WPB - 1) / S::WPB, 64 * S::WPB, S::LDS, s, ev, a);
+  else if (grid > 0) TSH_LAUNCH(kern, grid, 256, 0, s, ev, a);
+  else TSH_LAUNCH(kern, -grid, 64, 0, s, ev, a);
 }
-template <int NCH>
-void launch_scan_n(const ScanArgsQ &a, int metric, bool masked, int grid, hipStream_t s, const LaunchEv &ev, bool ml) {
-  if (metric == TSH_METRIC_L2) launch_scan_m<NCH, METRIC_L2>(a, masked, grid, s, ev, ml);
-  else if (metric == TSH_METRIC_IP) launch_scan_m<NCH, METRIC_IP>(a, masked, grid, s, ev, ml);
-  else launch_scan_m<NCH, METRIC_COS>(a, masked, grid, s, ev, ml);
+template <class F, int NCH, int METRIC>
+void launch_tile_scan_m(const ScanArgsQ &a, bool masked, int grid, hipStream_t s, const LaunchEv &ev, bool ml) {
+  const bool full = a.a.d4 == NCH * 64;
+  if constexpr (F::HAS_MASKED) {
+    if (masked) {
+      if (full) launch_tile_scan_t<F, NCH, METRIC, true, true>(a, grid, s, ev, ml);
+      else launch_tile_scan_t<F, NCH, METRIC, false, true>(a, grid, s, ev, ml);
+      return;
+    }
+  }
+  if (full) launch_tile_scan_t<F, NCH, METRIC, true, false>(a, grid, s, ev, ml);
+  else launch_tile_scan_t<F, NCH, METRIC, false, false>(a, grid, s, ev, ml);
 }
+// grid: launch_tile_scan_t's, for a shard of SMALL_SHARD_TILES tiles or more (smaller ones: one-wave workgroups --
+// fewer than ~6 four-wave workgroups per CU and tile counts per CU differ by tens of percent; one tile per workgroup
+// lets the dispatcher even them out)
+template <class F>
+void launch_tile_scan(const ScanArgsQ &a, int nch, int metric, bool masked, int grid, hipStream_t s, const LaunchEv &ev, bool ml) {
+  if (a.a.n_tiles < SMALL_SHARD_TILES) grid = -std::max(1, (int)a.a.n_tiles);
+#define TSH_NCH_DO(N)                                                                                  \
+  do {                                                                                                 \
+    if (metric == TSH_METRIC_L2) launch_tile_scan_m<F, N, METRIC_L2>(a, masked, grid, s, ev, ml);      \
+    else if (metric == TSH_METRIC_IP) launch_tile_scan_m<F, N, METRIC_IP>(a, masked, grid, s, ev, ml); \
+    else launch_tile_scan_m<F, N, METRIC_COS>(a, masked, grid, s, ev, ml);                             \
+  } while (0)
+// (a width the family does not have falls through to its widest: the cases below must stay in ascending order, a new
+// width goes in its place in the list)
+#define TSH_NCH(N)                  \
+  case N:                           \
+    if constexpr (N < F::MAX_NCH) { \
+      TSH_NCH_DO(N);                \
+      break;                        \
+    }                               \
+    [[fallthrough]];
+  switch (nch) {
+    TSH_NCH(1) TSH_NCH(2) TSH_NCH(3) TSH_NCH(4) TSH_NCH(5) TSH_NCH(6) TSH_NCH(7) TSH_NCH(8)
+    TSH_NCH(10) TSH_NCH(12) TSH_NCH(14)
+    default: TSH_NCH_DO(F::MAX_NCH);
+  }
+#undef TSH_NCH
+#undef TSH_NCH_DO
+}
+
 template <int SPLIT>
 void launch_packed(const ScanArgsQ &a, int metric, bool masked, int grid, int threads, hipStream_t s,
                    const LaunchEv &ev) {
@@ -92,113 +161,20 @@ void launch_scan_list_n(const ScanArgsQ &a, int metric, hipStream_t s, const Lau
   else TSH_LAUNCH((scan_list_kernel<NCH, METRIC_COS, R, true>), grid, 512, 0, s, ev, a);
 }
 
-// The fp16 scan: a row is half the bytes, so two register buffers of R rows are R*NCH*2 VGPRs each, and the launch shape
-// is ScanShape's for a row of half as many 1 KiB chunks (d = 768: 1.5 KiB rows, eight waves per CU; d = 1536: four).
-// MASKED: the same (R, MINW) at every width -- the masked instantiations fit the dense ones' register budgets without
-// scratch (the compiler's resource-usage remarks: profiles/scan_f16_masked_resources.txt) -- and launch_scan_t's three shapes.
-template <int NCH, bool MASKED> struct ScanF16Tune {
-  static constexpr int R = NCH <= 6 ? 4 : 2;
-  static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 8 ? 3 : 2);
-};
-template <int NCH, int METRIC, bool FULL, bool MASKED>
-void launch_scan_f16_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev, bool mostly_live) {
-  using T = ScanF16Tune<NCH, MASKED>;
-  using S = ScanShape<(NCH + 1) / 2>;
-  // grid > 0: a big shard -- dense and mostly-live scans in the shape of ScanShape, scattered ones in 4-wave workgroups;
-  // grid < 0: -grid one-wave workgroups (small shards)
-  if (grid > 0 && (!MASKED || mostly_live))
-    TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>), (a.a.n_tiles + S::WPB - 1) / S::WPB, 64 * S::WPB, S::LDS, s, ev, a);
-  else if (grid > 0) TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>), grid, 256, 0, s, ev, a);
-  else TSH_LAUNCH((scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>), -grid, 64, 0, s, ev, a);
-}
-template <int NCH>
-void launch_scan_f16_n(const ScanArgsQ &a, int metric, bool masked, int grid, hipStream_t s, const LaunchEv &ev, bool ml) {
-  const bool full = a.a.d4 == NCH * 64;
-#define TSH_F16(M)                                                            \
-  do {                                                                        \
-    if (full) {                                                               \
-      if (masked) launch_scan_f16_t<NCH, M, true, true>(a, grid, s, ev, ml);  \
-      else launch_scan_f16_t<NCH, M, true, false>(a, grid, s, ev, ml);        \
-    } else {                                                                  \
-      if (masked) launch_scan_f16_t<NCH, M, false, true>(a, grid, s, ev, ml); \
-      else launch_scan_f16_t<NCH, M, false, false>(a, grid, s, ev, ml);       \
-    }                                                                         \
-  } while (0)
-  if (metric == TSH_METRIC_L2) TSH_F16(METRIC_L2);
-  else if (metric == TSH_METRIC_IP) TSH_F16(METRIC_IP);
-  else TSH_F16(METRIC_COS);
-#undef TSH_F16
-}
-
 }  // namespace
 
-// (rows of more than 14 chunks that end inside a chunk would spill: they stay on f32)
-bool scan_f16_supported(int nch, int dim) { return dim >= 256 && dim % 8 == 0 && nch >= 1 && nch <= 14; }
+bool scan_f16_supported(int nch, int dim) { return dim >= 256 && dim % 8 == 0 && nch >= 1 && nch <= ScanF16::MAX_NCH; }
 
 void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev, bool ml) {
   if (a.a.n_tiles <= 0) return;
-  // (> 0: the big shards' shapes -- one workgroup per ScanShape::WPB tiles, or this many 4-wave workgroups for a
-  // scattered masked scan)
-  int grid = std::max(1, (a.a.n_tiles + 3) / 4);
-  if (a.a.n_tiles < SMALL_SHARD_TILES) grid = -std::max(1, (int)a.a.n_tiles);
-  switch (nch) {
-    case 1: launch_scan_f16_n<1>(a, metric, masked, grid, s, ev, ml); break;
-    case 2: launch_scan_f16_n<2>(a, metric, masked, grid, s, ev, ml); break;
-    case 3: launch_scan_f16_n<3>(a, metric, masked, grid, s, ev, ml); break;
-    case 4: launch_scan_f16_n<4>(a, metric, masked, grid, s, ev, ml); break;
-    case 5: launch_scan_f16_n<5>(a, metric, masked, grid, s, ev, ml); break;
-    case 6: launch_scan_f16_n<6>(a, metric, masked, grid, s, ev, ml); break;
-    case 7: launch_scan_f16_n<7>(a, metric, masked, grid, s, ev, ml); break;
-    case 8: launch_scan_f16_n<8>(a, metric, masked, grid, s, ev, ml); break;
-    case 10: launch_scan_f16_n<10>(a, metric, masked, grid, s, ev, ml); break;
-    case 12: launch_scan_f16_n<12>(a, metric, masked, grid, s, ev, ml); break;
-    default: launch_scan_f16_n<14>(a, metric, masked, grid, s, ev, ml); break;
-  }
+  launch_tile_scan<ScanF16>(a, nch, metric, masked, std::max(1, (a.a.n_tiles + 3) / 4), s, ev, ml);
 }
 
-// The int8 scan: a row is a quarter of the bytes, two register buffers of eight rows are 16 * NCH VGPRs, and the launch
-// shape is the fp16 scan's (ScanShape of half as many chunks: as many bytes in flight per CU as there).  Rows of up to
-// eight chunks (d <= 2048): beyond that the two buffers and the query leave the register budget.
-template <int NCH> struct ScanI8Tune {
-  static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 6 ? 3 : 2);
-};
-template <int NCH, int METRIC, bool FULL>
-void launch_scan_i8_t(const ScanArgsQ &a, int grid, hipStream_t s, const LaunchEv &ev) {
-  using S = ScanShape<(NCH + 1) / 2>;
-  constexpr int MINW = ScanI8Tune<NCH>::MINW;
-  if (grid > 0) TSH_LAUNCH((scan_i8_kernel<NCH, METRIC, FULL, 4, MINW>), (a.a.n_tiles + S::WPB - 1) / S::WPB, 64 * S::WPB, S::LDS, s, ev, a);
-  else TSH_LAUNCH((scan_i8_kernel<NCH, METRIC, FULL, 4, MINW>), -grid, 64, 0, s, ev, a);
-}
-template <int NCH>
-void launch_scan_i8_n(const ScanArgsQ &a, int metric, int grid, hipStream_t s, const LaunchEv &ev) {
-  const bool full = a.a.d4 == NCH * 64;
-#define TSH_I8(M)                                                  \
-  do {                                                             \
-    if (full) launch_scan_i8_t<NCH, M, true>(a, grid, s, ev);      \
-    else launch_scan_i8_t<NCH, M, false>(a, grid, s, ev);          \
-  } while (0)
-  if (metric == TSH_METRIC_L2) TSH_I8(METRIC_L2);
-  else if (metric == TSH_METRIC_IP) TSH_I8(METRIC_IP);
-  else TSH_I8(METRIC_COS);
-#undef TSH_I8
-}
-
-bool scan_i8_supported(int nch) { return nch >= 1 && nch <= 8; }
+bool scan_i8_supported(int nch) { return nch >= 1 && nch <= ScanI8::MAX_NCH; }
 
 void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev) {
   if (a.a.n_tiles <= 0) return;
-  int grid = 1;  // (> 0: the big shards' shape; < 0: one-wave workgroups)
-  if (a.a.n_tiles < SMALL_SHARD_TILES) grid = -std::max(1, (int)a.a.n_tiles);
-  switch (nch) {
-    case 1: launch_scan_i8_n<1>(a, metric, grid, s, ev); break;
-    case 2: launch_scan_i8_n<2>(a, metric, grid, s, ev); break;
-    case 3: launch_scan_i8_n<3>(a, metric, grid, s, ev); break;
-    case 4: launch_scan_i8_n<4>(a, metric, grid, s, ev); break;
-    case 5: launch_scan_i8_n<5>(a, metric, grid, s, ev); break;
-    case 6: launch_scan_i8_n<6>(a, metric, grid, s, ev); break;
-    case 7: launch_scan_i8_n<7>(a, metric, grid, s, ev); break;
-    default: launch_scan_i8_n<8>(a, metric, grid, s, ev); break;
-  }
+  launch_tile_scan<ScanI8>(a, nch, metric, false, 1, s, ev, false);
 }
 
 bool scan_list_supported(int nch, int64_t ld) { return nch >= 1 && nch <= 8 && ld != 128 && ld != 64 && ld != 32; }
@@ -232,23 +208,7 @@ void launch_scan(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream
     else launch_packed<3>(a, metric, masked, grid, threads, s, ev);
     return;
   }
-  // fewer than ~6 four-wave workgroups per CU: tile counts per CU differ by tens of
-  // percent; one tile per workgroup lets the dispatcher even them out
-  if (a.a.n_tiles < SMALL_SHARD_TILES) grid = -std::max(1, (int)a.a.n_tiles);
-  switch (nch) {
-    case 1: launch_scan_n<1>(a, metric, masked, grid, s, ev, ml); break;
-    case 2: launch_scan_n<2>(a, metric, masked, grid, s, ev, ml); break;
-    case 3: launch_scan_n<3>(a, metric, masked, grid, s, ev, ml); break;
-    case 4: launch_scan_n<4>(a, metric, masked, grid, s, ev, ml); break;
-    case 5: launch_scan_n<5>(a, metric, masked, grid, s, ev, ml); break;
-    case 6: launch_scan_n<6>(a, metric, masked, grid, s, ev, ml); break;
-    case 7: launch_scan_n<7>(a, metric, masked, grid, s, ev, ml); break;
-    case 8: launch_scan_n<8>(a, metric, masked, grid, s, ev, ml); break;
-    case 10: launch_scan_n<10>(a, metric, masked, grid, s, ev, ml); break;
-    case 12: launch_scan_n<12>(a, metric, masked, grid, s, ev, ml); break;
-    case 14: launch_scan_n<14>(a, metric, masked, grid, s, ev, ml); break;
-    default: launch_scan_n<16>(a, metric, masked, grid, s, ev, ml); break;
-  }
+  launch_tile_scan<ScanF32>(a, nch, metric, masked, grid, s, ev, ml);
 }
 
 }  // namespace tsh
