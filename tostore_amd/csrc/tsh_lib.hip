@@ -357,6 +357,38 @@ struct ScanRouteState {
   }
 };
 
+enum class RowStore { F32, F16, I8 };  // which copy of the rows a tile scan reads
+
+// One lazily kept reduced-precision copy of the row store (the fp16 copy, the int8 copy): row-major, one allocation.  Kept
+// current where a scan is enqueued (row_copy_ensure): rows [0, valid) are converted; appends past the watermark are
+// converted in front of the next scan; an overwrite of a stored row, a reallocation of the row store or (fp16) another
+// scale reset it to 0.  Tombstones do not touch it.  Guarded by Shard::row_copies_mu under a shared s->mu; appends change
+// it under the exclusive lock.
+struct RowCopy {
+  explicit RowCopy(int mode_) : mode(mode_) {}
+  void *d = nullptr;
+  int64_t cap = 0, valid = 0, bytes = 0;
+  bool denied = false;  // the copy did not fit on the device: its route is off until the row store is reallocated
+  std::atomic<int64_t> converted{0};
+  ScanRouteState route;  // (overflow: of the fp16 scan's candidate list, the int8 scan's survivor list)
+  int mode;  // TSH_OPT_SCAN_F16 / TSH_OPT_SCAN_I8: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible scan
+  void release(struct Shard *s);  // the buffer goes, with its bytes, its watermark and its denial
+  void overwritten(int64_t first) {  // rows from `first` on were written: a stored row among them and the copy is rebuilt
+    if (first < valid) valid = 0;
+  }
+};
+// The fp16 copy: ld halves per row, elements scaled by 2^exp
+struct RowCopyF16 : RowCopy {
+  using RowCopy::RowCopy;
+  int exp = 0;
+  int mode_masked = 1;  // TSH_OPT_SCAN_F16_MASKED: the same three for tile scans behind a mask, tombstones, quarantined
+                        // rows or gaps (none of them while mode == 0)
+};
+// The int8 copy: ld biased bytes per row and behind the rows, in the same allocation, a scale per row
+inline float *rows8_scales(const RowCopy &c, int64_t ld) {
+  return c.d ? reinterpret_cast<float *>(static_cast<uint8_t *>(c.d) + c.cap * ld) : nullptr;
+}
+
 struct Shard {
   int device = 0;
   int dim = 0, metric = 0, nch = 0;
@@ -477,34 +509,15 @@ struct Shard {
   int hub_n = 0, hub_exp = 0, hub_chunks = 0;
   int64_t hub_bytes = 0;
 
-  // The fp16 copy of the rows that big shards' dense single-query scans read (scan_f16_kernel): row-major, ld halves per
-  // row, elements scaled by 2^rows16_exp.  Kept current LAZILY by rows16_ensure, where a scan is enqueued: rows
-  // [0, rows16_valid) are converted; appends past the watermark are converted in front of the next scan; an overwrite of
-  // a stored row, a reallocation of the row store or another scale reset it to 0.  Tombstones do not touch it (a
-  // tombstoned shard scans f32).  Guarded by rows16_mu under a shared s->mu; appends change it under the exclusive lock.
-  void *d_rows16 = nullptr;
-  int64_t rows16_cap = 0, rows16_valid = 0, rows16_bytes = 0;
-  int rows16_exp = 0;
-  bool rows16_denied = false;  // the copy did not fit on the device: f32 scans until the row store is reallocated
-  std::mutex rows16_mu;
-  int scan_f16 = 1;  // TSH_OPT_SCAN_F16: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible dense scan
-  int scan_f16_masked = 1;  // TSH_OPT_SCAN_F16_MASKED: the same three for tile scans behind a mask, tombstones, quarantined
-                            // rows or gaps (none of them while scan_f16 == 0)
-  std::atomic<int64_t> c_f16_converted{0};
-  ScanRouteState route_f16;  // (overflow: of the candidate list)
-  // The int8 copy of the rows that big shards' dense, all-live single-query scans read as a coarse first pass
-  // (scan_i8_kernel): row-major, ld biased bytes per row, and behind them (same allocation) a scale per row.  Kept
-  // current exactly like the fp16 copy (rows8_ensure / rows16_ensure share row_copy_ensure, and rows16_mu guards both).
-  void *d_rows8 = nullptr;
-  float *d_scale8 = nullptr;
-  int64_t rows8_cap = 0, rows8_valid = 0, rows8_bytes = 0;
-  bool rows8_denied = false;  // the copy did not fit on the device: no int8 scans until the row store is reallocated
+  // The fp16 copy of the rows that big shards' tile scans, dense or masked, read (scan_f16_kernel), and the int8 copy
+  // that their dense, all-live scans read as a coarse first pass (scan_i8_kernel).  One mutex guards both.
 #ifndef TSH_SCAN_I8_DEFAULT
 #define TSH_SCAN_I8_DEFAULT 1  // (A/B builds: -DTSH_SCAN_I8_DEFAULT=0, a variant library of its own -- tostore_amd/build.py)
 #endif
-  int scan_i8 = TSH_SCAN_I8_DEFAULT;  // TSH_OPT_SCAN_I8: 0 never, 1 shards larger than the Infinity Cache, 2 every eligible scan
-  std::atomic<int64_t> c_i8_converted{0};
-  ScanRouteState route_i8;  // (overflow: of the survivor list)
+  RowCopyF16 rows16{1};
+  RowCopy rows8{TSH_SCAN_I8_DEFAULT};
+  std::mutex row_copies_mu;
+  RowCopy *row_copy(RowStore st) { return st == RowStore::F16 ? &rows16 : st == RowStore::I8 ? &rows8 : nullptr; }
 
   bool safe_mode() const {
     if (nonfinite_rows) return true;
@@ -513,6 +526,18 @@ struct Shard {
     return false;
   }
 };
+
+// (the copy follows the row store's capacity: built again by the next eligible scan)
+void RowCopy::release(Shard *s) {
+  if (d) {
+    hipFree(d);
+    d = nullptr;
+    s->bytes -= bytes;
+    bytes = 0;
+  }
+  cap = valid = 0;
+  denied = false;
+}
 
 // The stream sets live as long as the process -- except the CU-masked streams: left to the runtime's own teardown
 // they crash a python host at exit under rocprofv3 (tools/exitcheck.sh: SIGSEGV in __cxa_finalize after the tool
@@ -685,23 +710,8 @@ int shard_reserve(Shard *s, int64_t want_rows) {
   if (s->d_inv_norm) hipFree(s->d_inv_norm);
   if (s->d_sqnorm) hipFree(s->d_sqnorm);
   if (s->d_live) hipFree(s->d_live);
-  if (s->d_rows16) {  // the copy follows the row store's capacity: built again by the next eligible scan
-    hipFree(s->d_rows16);
-    s->d_rows16 = nullptr;
-    s->bytes -= s->rows16_bytes;
-    s->rows16_bytes = 0;
-  }
-  s->rows16_cap = s->rows16_valid = 0;
-  s->rows16_denied = false;
-  if (s->d_rows8) {
-    hipFree(s->d_rows8);
-    s->d_rows8 = nullptr;
-    s->d_scale8 = nullptr;
-    s->bytes -= s->rows8_bytes;
-    s->rows8_bytes = 0;
-  }
-  s->rows8_cap = s->rows8_valid = 0;
-  s->rows8_denied = false;
+  s->rows16.release(s);
+  s->rows8.release(s);
   s->d_rows = nrows;
   s->d_inv_norm = ninv;
   s->d_sqnorm = nsq;
@@ -798,8 +808,8 @@ int shard_append(Shard *s, int64_t first, int64_t n, const float *src, bool src_
   if (first > s->rows) s->all_live = false;  // gap of absent rows
   if (first + n > s->rows) s->rows = first + n;
   s->split_valid = std::min(s->split_valid, first);  // overwritten / new rows need re-splitting
-  if (first < s->rows16_valid) s->rows16_valid = 0;  // a stored row overwritten: the fp16 copy is rebuilt
-  if (first < s->rows8_valid) s->rows8_valid = 0;    // ... and the int8 copy
+  s->rows16.overwritten(first);
+  s->rows8.overwritten(first);
   if (first < s->hub_rows_built) s->hub_rows_built = -1;  // (an overwritten row may be a hub row: its copy is stale)
   return TSH_OK;
 }
@@ -1053,8 +1063,6 @@ struct ShardMask {
   bool listed() const { return list.ids || list.d_ids; }
 };
 
-enum class RowStore { F32, F16, I8 };  // which copy of the rows a tile scan reads
-
 // One query in flight on one context.  Its three kernels (scan, select,
 // rerank) are enqueued back to back on the shard's single in-order pipeline
 // stream with NO copy and NO cross-stream dependency between them: the query
@@ -1285,37 +1293,25 @@ constexpr int64_t SCAN_F16_MIN_BYTES = 256ll << 20;  // the Infinity Cache: a ro
 // gaps -- TSH_OPT_SCAN_F16_MASKED decides for those, TSH_OPT_SCAN_F16 for dense scans and, at 0, for both.  (The shard's
 // side of the decision: caller holds s->mu)
 bool scan_f16_applies(const Shard *s, bool masked, int *v_exp) {
-  const int mode = masked ? s->scan_f16_masked : s->scan_f16;
-  if (s->scan_f16 == 0 || mode == 0 || s->rows16_denied || s->safe_mode()) return false;
+  const int mode = masked ? s->rows16.mode_masked : s->rows16.mode;
+  if (s->rows16.mode == 0 || mode == 0 || s->rows16.denied || s->safe_mode()) return false;
   if (!scan_f16_supported(s->nch, s->dim)) return false;
   if (mode == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
   if (s->metric == TSH_METRIC_COSINE && !(s->min_norm > 0.f)) return false;  // (a zero row: no uniform cosine band)
   return scan_f16_exp(s->max_abs, v_exp);
 }
 
-// One lazily kept copy of the rows (the fp16 copy, the int8 copy): its device buffer and watermark, as fields of the shard
-struct RowCopyRef {
-  void *&d;
-  int64_t &cap, &valid, &bytes;
-  bool &denied;
-};
 // Brings a copy up to the shard's rows: allocation on first use (`bytes` for the row store's capacity), conversion of the
 // rows past the watermark (all of them after a reset, or with `rebuild`) by convert(r0, r1) on `st`, waited for -- a scan
 // on any stream may follow.  false: the copy does not fit on the device; the shard stays off it from now on (denied)
-// instead of asking again with every query.  Caller holds rows16_mu.
+// instead of asking again with every query.  Caller holds row_copies_mu.
 template <class Convert>
-bool row_copy_ensure(Shard *s, RowCopyRef c, int64_t bytes, bool rebuild, hipStream_t st, std::atomic<int64_t> *converted, Convert convert) {
+bool row_copy_ensure(Shard *s, RowCopy &c, int64_t bytes, bool rebuild, hipStream_t st, Convert convert) {
   if (c.denied) return false;
   if (c.d && c.cap == s->cap && !rebuild && c.valid == s->rows) return true;
   if (hipSetDevice(s->device) != hipSuccess) return false;
   if (!c.d || c.cap != s->cap) {
-    if (c.d) {
-      hipFree(c.d);
-      c.d = nullptr;
-      s->bytes -= c.bytes;
-      c.bytes = 0;
-    }
-    c.cap = c.valid = 0;
+    c.release(s);
     if (alloc_fault(bytes) || !device_has_room(bytes) || hipMalloc(&c.d, (size_t)bytes) != hipSuccess) {
       (void)hipGetLastError();
       c.d = nullptr;
@@ -1334,51 +1330,46 @@ bool row_copy_ensure(Shard *s, RowCopyRef c, int64_t bytes, bool rebuild, hipStr
     c.valid = 0;
     return false;
   }
-  *converted += s->rows - r0;
+  c.converted += s->rows - r0;
   c.valid = s->rows;
   return true;
 }
 
 // The fp16 copy, of scale 2^v_exp (another scale: every row again)
 bool rows16_ensure(Shard *s, hipStream_t st, int v_exp) {
-  std::lock_guard<std::mutex> lk(s->rows16_mu);
-  const bool rescale = s->rows16_exp != v_exp;
-  s->rows16_exp = v_exp;
-  return row_copy_ensure(s, RowCopyRef{s->d_rows16, s->rows16_cap, s->rows16_valid, s->rows16_bytes, s->rows16_denied},
-                         s->cap * s->ld * 2, rescale, st, &s->c_f16_converted, [&](int64_t r0, int64_t r1) {
-                           const int64_t groups = (r1 - r0) * s->ld / 4;
-                           const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 8192));
-                           rows16_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->d_rows16, s->ld, r0, r1, std::ldexp(1.0f, v_exp));
-                         });
+  std::lock_guard<std::mutex> lk(s->row_copies_mu);
+  const bool rescale = s->rows16.exp != v_exp;
+  s->rows16.exp = v_exp;
+  return row_copy_ensure(s, s->rows16, s->cap * s->ld * 2, rescale, st, [&](int64_t r0, int64_t r1) {
+    const int64_t groups = (r1 - r0) * s->ld / 4;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + 255) / 256, 8192));
+    rows16_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->rows16.d, s->ld, r0, r1, std::ldexp(1.0f, v_exp));
+  });
 }
 
 // The int8 copy and, behind its rows, their scales
 bool rows8_ensure(Shard *s, hipStream_t st) {
-  std::lock_guard<std::mutex> lk(s->rows16_mu);
-  const bool ok = row_copy_ensure(s, RowCopyRef{s->d_rows8, s->rows8_cap, s->rows8_valid, s->rows8_bytes, s->rows8_denied},
-                                  s->cap * s->ld + s->cap * 4, false, st, &s->c_i8_converted, [&](int64_t r0, int64_t r1) {
-                                    float *scale8 = reinterpret_cast<float *>(static_cast<uint8_t *>(s->d_rows8) + s->cap * s->ld);
-                                    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((r1 - r0 + 3) / 4, 16384));
-                                    rows8_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->d_rows8, scale8, s->ld, r0, r1);
-                                  });
-  s->d_scale8 = ok ? reinterpret_cast<float *>(static_cast<uint8_t *>(s->d_rows8) + s->cap * s->ld) : nullptr;
-  return ok;
+  std::lock_guard<std::mutex> lk(s->row_copies_mu);
+  return row_copy_ensure(s, s->rows8, s->cap * s->ld + s->cap * 4, false, st, [&](int64_t r0, int64_t r1) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((r1 - r0 + 3) / 4, 16384));
+    rows8_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, s->rows8.d, rows8_scales(s->rows8, s->ld), s->ld, r0, r1);
+  });
 }
 
 // Could a scan of this shard take the coarse int8 route?  Dense and all-live only (the callers know about masks); the
 // exact path behind it needs a block of at least k entries.  (The shard's side of the decision: caller holds s->mu)
 bool scan_i8_applies(const Shard *s, int32_t k, int32_t entries) {
-  if (s->scan_i8 == 0 || s->rows8_denied || s->safe_mode() || !s->all_live || !s->quar_ids.empty()) return false;
+  if (s->rows8.mode == 0 || s->rows8.denied || s->safe_mode() || !s->all_live || !s->quar_ids.empty()) return false;
   if (!scan_i8_supported(s->nch) || k > entries || k > I8_LIST_CAP || s->rows <= 0) return false;
-  if (s->scan_i8 == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
+  if (s->rows8.mode == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
   if (s->metric == TSH_METRIC_COSINE && !(s->min_norm > 0.f)) return false;
   return true;
 }
 
 // the int8 scan's arguments on top of the f32 scan's (fill_scan_args)
 void fill_scan_i8_args(const Shard *s, const ScanI8Band &ib, ScanArgsQ *aq) {
-  aq->a.rows16 = s->d_rows8;
-  aq->a.scale8 = s->d_scale8;
+  aq->a.rows16 = s->rows8.d;
+  aq->a.scale8 = rows8_scales(s->rows8, s->ld);
   aq->a.sqnorm = s->d_sqnorm;
   aq->a.inv_scale = ib.qbias;
   aq->a.w_s = ib.a_s;
@@ -1411,9 +1402,9 @@ inline uint64_t *i8_words(const Ctx *c) {
 
 // the fp16 scan's arguments on top of the f32 scan's (fill_scan_args) and the select's
 void fill_scan_f16_args(const Shard *s, const ScanF16Band &fb, ScanArgsQ *aq, SelectArgs *se) {
-  aq->a.rows16 = s->d_rows16;
+  aq->a.rows16 = s->rows16.d;
   aq->a.sqnorm = s->d_sqnorm;
-  aq->a.inv_scale = std::ldexp(1.0f, -s->rows16_exp);
+  aq->a.inv_scale = std::ldexp(1.0f, -s->rows16.exp);
   aq->a.w_alpha = fb.alpha;
   aq->a.w_beta = fb.beta;
   if (se) {
@@ -1439,7 +1430,7 @@ Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, i
   r.exact = exact_applies(s, r.n_exam, k, entries);
   // the coarse int8 route: dense, all-live tile scans inside the error model (TSH_OPT_SCAN_I8 = 2, the tests' setting,
   // takes it for shards the exact path would answer whole, too)
-  if (!no_i8 && !masked && !r.use_list && (!r.exact || s->scan_i8 == 2) && scan_i8_applies(s, k, entries) && !compute_band(s, q).force_all) {
+  if (!no_i8 && !masked && !r.use_list && (!r.exact || s->rows8.mode == 2) && scan_i8_applies(s, k, entries) && !compute_band(s, q).force_all) {
     r.ib = scan_i8_band(s->metric, s->dim, s->nch, q, s->max_norm, s->min_norm, s->max_abs);
     r.i8_eligible = true;
     if (r.exact && r.ib.ok) r.exact = false;  // (mode 2; a denial or a full device below leaves such a shard to its f32 scan)
@@ -1652,6 +1643,20 @@ int pick_tail_stream(Shard *s, const Route &r, bool overlap, int which, hipStrea
 }
 
 // ---- which kernels run for a job ------------------------------------------------------------------------------------
+// The first-pass kernel of a route, for searches and for the measurement hook alike: E1 over xa, or over sa the list
+// scan or the tile scan of `store`.  masked: a mask or dead rows; rows_est: the mask's (ShardMask), 0 = none
+void launch_route_scan(const Shard *s, const Route &r, RowStore store, bool masked, int64_t rows_est, const ScanArgsQ &sa,
+                       const ExactArgsQ &xa, hipStream_t st, const LaunchEv &ev) {
+  if (r.exact) return launch_exact_scan(xa, s->metric, st, ev);
+  if (r.use_list) return launch_scan_list(sa, s->nch, s->metric, st, ev);
+  const bool ml = masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows);
+  switch (store) {
+    case RowStore::I8: launch_scan_i8(sa, s->nch, s->metric, st, ev); break;
+    case RowStore::F16: launch_scan_f16(sa, s->nch, s->metric, masked, st, ev, ml); break;
+    case RowStore::F32: launch_scan(sa, s->nch, s->metric, masked, st, ev, ml); break;
+  }
+}
+
 // The copies of what is new to the context, then the route's scan, all on ps
 // (short scans as ONE dispatch -- every workgroup scans its tiles, the one drawing the last ticket selects and
 // re-ranks -- were built in round 2 and measured slower than these three launches: C1 45 vs 37 us per call,
@@ -1664,17 +1669,7 @@ int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipSt
     HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, (size_t)rq.mask.list.padded * sizeof(uint32_t), hipMemcpyHostToDevice, ps));
   if (s->ld > SCAN_Q_INLINE)
     HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, ps));
-  const int64_t rows_est = rq.mask.rows_est;
-  if (j->route.exact) launch_exact_scan(ka.xa, s->metric, ps, ev);
-  else if (j->route.use_list) launch_scan_list(ka.sa, s->nch, s->metric, ps, ev);
-  else {
-    const bool ml = j->masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows);
-    switch (j->store) {
-      case RowStore::I8: launch_scan_i8(ka.sa, s->nch, s->metric, ps, ev); break;
-      case RowStore::F16: launch_scan_f16(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml); break;
-      case RowStore::F32: launch_scan(ka.sa, s->nch, s->metric, j->masked, ps, ev, ml); break;
-    }
-  }
+  launch_route_scan(s, j->route, j->store, j->masked, rq.mask.rows_est, ka.sa, ka.xa, ps, ev);
   return TSH_OK;
 }
 
@@ -1728,12 +1723,12 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   // (an eligible scan uses up a denial of its route, if any are left, whatever its band; a scan that takes the int8
   // route neither asks for the fp16 copy nor touches the fp16 route's denials)
   j->store = RowStore::F32;
-  if (r.i8_eligible && !s->route_i8.take_denial() && r.ib.ok && rows8_ensure(s, s->scan_stream)) {
+  if (r.i8_eligible && !s->rows8.route.take_denial() && r.ib.ok && rows8_ensure(s, s->scan_stream)) {
     j->store = RowStore::I8;
     if ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c, (s->rows + 63) / 64))) return rc;
   } else {
     if (!r.exact) j->route.picked = false;
-    if (r.f16_eligible && !s->route_f16.take_denial() && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp)) j->store = RowStore::F16;
+    if (r.f16_eligible && !s->rows16.route.take_denial() && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp)) j->store = RowStore::F16;
   }
   if (j->store != RowStore::F32) {  // what a redo needs (redo_overflowed_scan)
     j->redo_q.assign(rq.query, rq.query + s->dim);
@@ -1780,8 +1775,7 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   s->c_scans++;
   if (r.use_list) s->c_list_scans++;
   if (r.exact) s->c_exact_scans++;
-  if (j->store == RowStore::F16) s->route_f16.scans++;
-  if (j->store == RowStore::I8) s->route_i8.scans++;
+  if (RowCopy *copy = s->row_copy(j->store)) copy->route.scans++;
   return TSH_OK;
 }
 
@@ -1901,7 +1895,7 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
 int redo_overflowed_scan(Shard *s, Job *j) {
   Ctx *c = j->c;
   const bool i8 = j->store == RowStore::I8;
-  ScanRouteState &rt = i8 ? s->route_i8 : s->route_f16;
+  ScanRouteState &rt = s->row_copy(j->store)->route;
   const BlockHeader *h = reinterpret_cast<const BlockHeader *>(c->h_block);
   if (!(h->flags & (i8 ? FLAG_I8_OVERFLOW : FLAG_LIST_OVERFLOW))) {
     rt.strikes.store(0);
@@ -2224,8 +2218,8 @@ void shard_destroy(Shard *s) {
   hipFree(s->d_sqnorm);
   hipFree(s->d_live);
   hipFree(s->d_split);
-  hipFree(s->d_rows16);
-  hipFree(s->d_rows8);
+  s->rows16.release(s);
+  s->rows8.release(s);
   hipFree(s->d_perm);
   hipFree(s->d_psq);
   hipFree(s->d_hub);
@@ -3330,26 +3324,59 @@ int32_t tsh_get_counters(tsh_index *idx, tsh_counters *out) {
   return TSH_OK;
 }
 
-struct CtxHold {  // a measurement / probe entry's context, given back when it returns
-  Shard *s;
-  Ctx *c;
-  ~CtxHold() { ctx_release(s, c); }
+// A measurement / probe entry's scaffold: the handle's one shard under its shared lock, a context prepared for the default
+// block of k = 100 and given back when the entry returns, the query zero-padded in c->h_query and on its way to c->d_query
+// on the aux stream (st)
+struct ScanHook {
+  Shard *s = nullptr;
+  Ctx *c = nullptr;
+  hipStream_t st = nullptr;
+  std::shared_lock<RwLock> sl;
+  ~ScanHook() {
+    if (!c) return;
+    if (st) (void)hipStreamSynchronize(st);  // (an entry that gave up: c->h_query is read until the upload is through)
+    ctx_release(s, c);
+  }
 };
+// args_ok: the entry's own arguments; need_mask: room for a caller's mask words in the context
+int scan_hook_begin(ScanHook *h, tsh_index *idx, const float *query, bool args_ok, bool need_mask = false) {
+  if (!idx || idx->shards.size() != 1 || !query || !args_ok) return set_err(TSH_E_BAD_ARG, "bad arguments");
+  Shard *s = h->s = idx->shards[0].get();
+  h->sl = share(idx, s);
+  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
+  Ctx *c = h->c = ctx_acquire(s, true);
+  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), need_mask);
+  if (rc) return rc;
+  h->st = s->aux_stream;
+  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
+  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
+  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, h->st));
+  return TSH_OK;
+}
+// What the hook's scan left in c->d_keys, waited for: every row's key as a float, NaN where the key is dead
+int scan_hook_keys(const ScanHook &h, float *out_keys) {
+  std::vector<uint32_t> keys((size_t)h.s->rows);
+  HIPCHK(hipMemcpyAsync(keys.data(), h.c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, h.st));
+  HIPCHK(hipStreamSynchronize(h.st));
+  HIPCHK(hipGetLastError());
+  for (size_t i = 0; i < keys.size(); ++i) out_keys[i] = keys[i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[i]);
+  return TSH_OK;
+}
 
 int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const uint8_t *row_mask,
                        double *out_avg_us) {
-  if (!idx || idx->shards.size() != 1 || !query || iters <= 0 || !out_avg_us)
-    return set_err(TSH_E_BAD_ARG, "bad arguments");
-  Shard *s = idx->shards[0].get();
-  std::shared_lock<RwLock> sl = share(idx, s);
-  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
-  Ctx *c = ctx_acquire(s, true);
-  CtxHold rel{s, c};
-  // the kernel a search with this mask would run: a search's mask resolution and route, for k = 100 and its default block
-  const int32_t k = 100, entries = tsh_default_block_entries(k);
-  int rc = ctx_prepare(s, c, entries, row_mask != nullptr);
+  ScanHook h;
+  int rc = scan_hook_begin(&h, idx, query, iters > 0 && out_avg_us, row_mask != nullptr);
   if (rc) return rc;
-  hipStream_t st = s->aux_stream;
+  Shard *s = h.s;
+  Ctx *c = h.c;
+  hipStream_t st = h.st;
+  // A search's mask resolution, route (choose_route) and first-pass kernel (launch_route_scan), for k = 100 and its
+  // default block -- EXCEPT the int8 route, which the hook never takes: where a search would scan the int8 copy, the hook
+  // times the fp16 or f32 tile scan such a search falls back to (a denial, a full device).  Under TSH_OPT_SCAN_I8 = 2 that
+  // is a tile scan even of a shard small enough for the exact path, which no search of it runs.  No denial is read or
+  // used up, no route counter touched.
+  const int32_t k = 100, entries = tsh_default_block_entries(k);
   std::vector<uint64_t> words;
   std::vector<uint32_t> list_ids;
   const ShardMask m = resolve_mask(s, MaskSrc(row_mask), k, entries, &words, &list_ids);
@@ -3360,9 +3387,6 @@ int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const 
     HIPCHK(hipMemcpyAsync(c->d_mask, c->h_mask, (size_t)n_tiles * 8, hipMemcpyHostToDevice, st));
     c->mask_epoch = 0;
   }
-  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
-  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
-  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
   const Route r = choose_route(s, m, masked, k, entries, c->h_query, false);
   if (r.use_list) {
     if ((rc = ctx_reserve_list(c, m.list.padded))) return rc;
@@ -3370,26 +3394,21 @@ int32_t tsh_bench_scan(tsh_index *idx, const float *query, int32_t iters, const 
     c->list_epoch = 0;
     HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, (size_t)m.list.padded * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
-  const bool ml = masked && scan_mostly_live(m.rows_est > 0 ? m.rows_est : s->rows - s->deleted, s->rows);
   const uint32_t *d_list = r.use_list ? c->d_list : nullptr;
   static thread_local ScanArgsQ sa;
   static thread_local ExactArgsQ xa;
-  bool f16 = false;
+  RowStore store = RowStore::F32;
   if (r.exact) {  // (no wave minima: the scan alone is timed, nothing picks behind it)
     if ((rc = ctx_reserve_exact(c, r.n_exam))) return rc;
     fill_exact_args(s, c, m.words && !r.use_list ? c->d_mask : nullptr, d_list, r.n_exam, c->h_query, &xa);
   } else {
     fill_scan_args(s, c, m.words ? c->d_mask : nullptr, d_list, m.list.padded, &sa);
-    // (the denial counter is a search's business: the hook neither reads nor consumes it)
-    f16 = r.f16_eligible && r.fb.ok && rows16_ensure(s, st, r.v_exp);
-    if (f16) fill_scan_f16_args(s, r.fb, &sa, nullptr);
+    if (r.f16_eligible && r.fb.ok && rows16_ensure(s, st, r.v_exp)) {
+      store = RowStore::F16;
+      fill_scan_f16_args(s, r.fb, &sa, nullptr);
+    }
   }
-  auto launch = [&]() {
-    if (r.exact) launch_exact_scan(xa, s->metric, st, LaunchEv());
-    else if (r.use_list) launch_scan_list(sa, s->nch, s->metric, st);
-    else if (f16) launch_scan_f16(sa, s->nch, s->metric, masked, st, LaunchEv(), ml);
-    else launch_scan(sa, s->nch, s->metric, masked, st, LaunchEv(), ml);
-  };
+  auto launch = [&]() { launch_route_scan(s, r, store, masked, m.rows_est, sa, xa, st, LaunchEv()); };
   launch();  // warm
   HIPCHK(hipEventRecord(c->ev0, st));
   for (int32_t i = 0; i < iters; ++i) launch();
@@ -3419,67 +3438,34 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
     idx->batch_min_nq = (int32_t)value;
     return TSH_OK;
   }
-  if (option == TSH_OPT_EXACT_SCAN_ROWS) {
-    if (value < 0 || value > EX_MAX_ROWS) return set_err(TSH_E_BAD_ARG, "exact scan rows: 0 .. %d", EX_MAX_ROWS);
+  // the per-shard options: id, lowest and highest value, what a value outside is told (%d: the highest), the store
+  struct ShardOption {
+    int32_t id;
+    int64_t lo, hi;
+    const char *msg;
+    void (*set)(Shard *, int64_t);
+  };
+  static const ShardOption options[] = {
+      {TSH_OPT_EXACT_SCAN_ROWS, 0, EX_MAX_ROWS, "exact scan rows: 0 .. %d", [](Shard *sh, int64_t v) { sh->exact_rows = (int)v; }},
+      {TSH_OPT_BATCH_GROUP, 0, 1, "batch group: 0 or 1", [](Shard *sh, int64_t v) { sh->batch_group = v != 0; }},
+      {TSH_OPT_BATCH_HUB, 0, 1, "batch hub: 0 or 1", [](Shard *sh, int64_t v) { sh->batch_hub = v != 0; }},
+      {TSH_OPT_EXACT_SELECT, 0, 1, "exact select: 0 (one workgroup ranks k rows) or 1 (wide pick)",
+       [](Shard *sh, int64_t v) { sh->exact_pick = v != 0; }},
+      {TSH_OPT_SCAN_F16, 0, 2, "scan f16 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible dense scan)",
+       [](Shard *sh, int64_t v) { sh->rows16.mode = (int)v; }},
+      {TSH_OPT_SCAN_F16_MASKED, 0, 2, "scan f16 masked must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible masked scan)",
+       [](Shard *sh, int64_t v) { sh->rows16.mode_masked = (int)v; }},
+      {TSH_OPT_SCAN_I8, 0, 2, "scan i8 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible scan)",
+       [](Shard *sh, int64_t v) { sh->rows8.mode = (int)v; }},
+      {TSH_OPT_BATCH_KERNEL, 0, 3, "batch kernel must be 0 (f32 MFMA), 1 (bf16x3), 2 (f16) or 3 (auto)",
+       [](Shard *sh, int64_t v) { sh->batch_kernel = (int)v; }},
+  };
+  for (const ShardOption &o : options) {
+    if (o.id != option) continue;
+    if (value < o.lo || value > o.hi) return set_err(TSH_E_BAD_ARG, o.msg, (int)o.hi);
     for (auto &sh : idx->shards) {
       std::unique_lock<RwLock> xl(sh->mu);
-      sh->exact_rows = (int)value;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_BATCH_GROUP) {
-    if (value != 0 && value != 1) return set_err(TSH_E_BAD_ARG, "batch group: 0 or 1");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->batch_group = value != 0;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_BATCH_HUB) {
-    if (value != 0 && value != 1) return set_err(TSH_E_BAD_ARG, "batch hub: 0 or 1");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->batch_hub = value != 0;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_EXACT_SELECT) {
-    if (value != 0 && value != 1) return set_err(TSH_E_BAD_ARG, "exact select: 0 (one workgroup ranks k rows) or 1 (wide pick)");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->exact_pick = value != 0;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_SCAN_F16) {
-    if (value < 0 || value > 2) return set_err(TSH_E_BAD_ARG, "scan f16 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible dense scan)");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->scan_f16 = (int)value;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_SCAN_F16_MASKED) {
-    if (value < 0 || value > 2) return set_err(TSH_E_BAD_ARG, "scan f16 masked must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible masked scan)");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->scan_f16_masked = (int)value;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_SCAN_I8) {
-    if (value < 0 || value > 2) return set_err(TSH_E_BAD_ARG, "scan i8 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible scan)");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->scan_i8 = (int)value;
-    }
-    return TSH_OK;
-  }
-  if (option == TSH_OPT_BATCH_KERNEL) {
-    if (value < 0 || value > 3) return set_err(TSH_E_BAD_ARG, "batch kernel must be 0 (f32 MFMA), 1 (bf16x3), 2 (f16) or 3 (auto)");
-    for (auto &sh : idx->shards) {
-      std::unique_lock<RwLock> xl(sh->mu);
-      sh->batch_kernel = (int)value;
+      o.set(sh.get(), value);
     }
     return TSH_OK;
   }
@@ -3519,119 +3505,78 @@ int32_t tsh_bench_batch(tsh_index *idx, const float *queries, int32_t nq, int32_
 // ---- probes of the pre-filter keys (tests/test_gpu_bands.py): what the kernels actually computed, next to the
 // error bound the host claimed for it
 int32_t tsh_probe_scan_keys(tsh_index *idx, const float *query, float *out_keys, float *out_eps_rel, float *out_delta_abs) {
-  if (!idx || idx->shards.size() != 1 || !query || !out_keys || !out_eps_rel || !out_delta_abs)
-    return set_err(TSH_E_BAD_ARG, "bad arguments");
-  Shard *s = idx->shards[0].get();
-  std::shared_lock<RwLock> sl = share(idx, s);
-  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
-  Ctx *c = ctx_acquire(s, true);
-  CtxHold rel{s, c};
-  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
+  ScanHook h;
+  int rc = scan_hook_begin(&h, idx, query, out_keys && out_eps_rel && out_delta_abs);
   if (rc) return rc;
-  hipStream_t st = s->aux_stream;
-  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
-  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
-  const Band band = compute_band(s, c->h_query);
+  Shard *s = h.s;
+  const Band band = compute_band(s, h.c->h_query);
   if (band.force_all) return set_err(TSH_E_BAD_ARG, "the query / index is outside the error model (no band)");
-  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
   static thread_local ScanArgsQ sa;
-  const bool masked = !s->all_live;
-  fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
-  launch_scan(sa, s->nch, s->metric, masked, st);
-  std::vector<uint32_t> keys((size_t)s->rows);
-  HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
-  for (int64_t i = 0; i < s->rows; ++i) out_keys[i] = keys[(size_t)i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[(size_t)i]);
+  fill_scan_args(s, h.c, nullptr, nullptr, 0, &sa);
+  launch_scan(sa, s->nch, s->metric, /*masked*/ !s->all_live, h.st);
+  if ((rc = scan_hook_keys(h, out_keys))) return rc;
   *out_eps_rel = band.eps_rel;
   *out_delta_abs = band.delta_abs;
   return TSH_OK;
 }
 
-int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out) {
+// scans, queries redone through the f32 scan, rows converted, bytes of the copy: of one of the two copies, over the shards
+int32_t row_copy_stats(tsh_index *idx, RowStore store, int64_t *out) {
   if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
   out[0] = out[1] = out[2] = out[3] = 0;
   for (auto &sp : idx->shards) {
     Shard *s = sp.get();
     std::shared_lock<RwLock> sl = share(idx, s);
-    out[0] += s->route_f16.scans.load();
-    out[1] += s->route_f16.redone.load();
-    out[2] += s->c_f16_converted.load();
-    std::lock_guard<std::mutex> lk(s->rows16_mu);
-    out[3] += s->rows16_bytes;
+    const RowCopy &c = *s->row_copy(store);
+    out[0] += c.route.scans.load();
+    out[1] += c.route.redone.load();
+    out[2] += c.converted.load();
+    std::lock_guard<std::mutex> lk(s->row_copies_mu);
+    out[3] += c.bytes;
   }
   return TSH_OK;
 }
-
-int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out) {
-  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
-  out[0] = out[1] = out[2] = out[3] = 0;
-  for (auto &sp : idx->shards) {
-    Shard *s = sp.get();
-    std::shared_lock<RwLock> sl = share(idx, s);
-    out[0] += s->route_i8.scans.load();
-    out[1] += s->route_i8.redone.load();
-    out[2] += s->c_i8_converted.load();
-    std::lock_guard<std::mutex> lk(s->rows16_mu);
-    out[3] += s->rows8_bytes;
-  }
-  return TSH_OK;
-}
+int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out) { return row_copy_stats(idx, RowStore::F16, out); }
+int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out) { return row_copy_stats(idx, RowStore::I8, out); }
 
 int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper) {
-  if (!idx || idx->shards.size() != 1 || !query || !out_lower || !out_upper) return set_err(TSH_E_BAD_ARG, "bad arguments");
-  Shard *s = idx->shards[0].get();
-  std::shared_lock<RwLock> sl = share(idx, s);
-  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
-  Ctx *c = ctx_acquire(s, true);
-  CtxHold rel{s, c};
-  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
+  ScanHook h;
+  int rc = scan_hook_begin(&h, idx, query, out_lower && out_upper);
   if (rc) return rc;
-  hipStream_t st = s->aux_stream;
-  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
-  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
+  Shard *s = h.s;
+  Ctx *c = h.c;
+  hipStream_t st = h.st;
   if (!scan_i8_applies(s, 1, 1) || compute_band(s, c->h_query).force_all)
     return set_err(TSH_E_BAD_ARG, "no int8 scan for this index / query (TSH_OPT_SCAN_I8, dead rows, row width, error model)");
   const ScanI8Band ib = scan_i8_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, s->max_abs);
   if (!ib.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the int8 scan's error model");
   if (!rows8_ensure(s, st)) return set_err(TSH_E_OOM, "no room on the device for the int8 copy of the rows");
-  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
   static thread_local ScanArgsQ sa;
   fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
   fill_scan_i8_args(s, ib, &sa);
   launch_scan_i8(sa, s->nch, s->metric, st);
-  std::vector<uint32_t> keys((size_t)s->rows);
-  std::vector<float> w((size_t)s->rows);
-  HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
+  if ((rc = scan_hook_keys(h, out_lower))) return rc;
   // (the rows' bands, by the arithmetic the kernel forms them with -- into the keys buffer, free again once copied)
+  std::vector<float> w((size_t)s->rows);
   float *d_w = reinterpret_cast<float *>(c->d_keys);
   scan_i8_w_kernel<<<(unsigned)((s->rows + 255) / 256), 256, 0, st>>>(s->d_sqnorm, s->metric == TSH_METRIC_COSINE ? s->d_inv_norm : nullptr,
-                                                                     s->d_scale8, s->rows, ib.a_s, ib.a_v, ib.beta, d_w);
+                                                                     sa.a.scale8, s->rows, ib.a_s, ib.a_v, ib.beta, d_w);
   HIPCHK(hipMemcpyAsync(w.data(), d_w, (size_t)s->rows * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   // the upper side as the kernel forms it: (lower + w) + w would round twice -- the key itself is lower + w up to one
   // rounding, which the band's own slack (1.001) covers on either side
-  for (int64_t i = 0; i < s->rows; ++i) {
-    const float lo = keys[(size_t)i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[(size_t)i]);
-    out_lower[i] = lo;
-    out_upper[i] = lo + 2.0f * w[(size_t)i];
-  }
+  for (int64_t i = 0; i < s->rows; ++i) out_upper[i] = out_lower[i] + 2.0f * w[(size_t)i];
   return TSH_OK;
 }
 
 int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_keys, float *out_w) {
-  if (!idx || idx->shards.size() != 1 || !query || !out_keys || !out_w) return set_err(TSH_E_BAD_ARG, "bad arguments");
-  Shard *s = idx->shards[0].get();
-  std::shared_lock<RwLock> sl = share(idx, s);
-  if (s->rows == 0) return set_err(TSH_E_BAD_ARG, "empty index");
-  Ctx *c = ctx_acquire(s, true);
-  CtxHold rel{s, c};
-  int rc = ctx_prepare(s, c, tsh_default_block_entries(100), false);
+  ScanHook h;
+  int rc = scan_hook_begin(&h, idx, query, out_keys && out_w);
   if (rc) return rc;
-  hipStream_t st = s->aux_stream;
-  memcpy(c->h_query, query, (size_t)s->dim * sizeof(float));
-  for (int64_t j = s->dim; j < s->ld; ++j) c->h_query[j] = 0.f;
+  Shard *s = h.s;
+  Ctx *c = h.c;
+  hipStream_t st = h.st;
   int v_exp = 0;
   const bool masked = !s->all_live;  // (dead rows: the keys of TSH_OPT_SCAN_F16_MASKED's route, NaN where a row is not live)
   if (!scan_f16_applies(s, masked, &v_exp) || compute_band(s, c->h_query).force_all)
@@ -3639,24 +3584,20 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
   const ScanF16Band fb = scan_f16_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, v_exp);
   if (!fb.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the fp16 scan's error model");
   if (!rows16_ensure(s, st, v_exp)) return set_err(TSH_E_OOM, "no room on the device for the fp16 copy of the rows");
-  HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
   static thread_local ScanArgsQ sa;
   fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
   fill_scan_f16_args(s, fb, &sa, nullptr);
   // (a dead tile's keys stay as they were: the probe reads them all, so they start out dead)
   if (masked) HIPCHK(hipMemsetAsync(c->d_keys, 0xFF, (size_t)((s->rows + 63) / 64) * 64 * 4, st));
   launch_scan_f16(sa, s->nch, s->metric, masked, st);
-  std::vector<uint32_t> keys((size_t)s->rows);
-  HIPCHK(hipMemcpyAsync(keys.data(), c->d_keys, keys.size() * 4, hipMemcpyDeviceToHost, st));
-  // (the rows' bands, by the function the kernel adds them with -- into gmin's neighbour: the keys buffer is free again
-  // once copied, in stream order)
+  if ((rc = scan_hook_keys(h, out_keys))) return rc;
+  // (the rows' bands, by the function the kernel adds them with -- into the keys buffer, free again once copied)
   float *d_w = reinterpret_cast<float *>(c->d_keys);
   scan_f16_w_kernel<<<(unsigned)((s->rows + 255) / 256), 256, 0, st>>>(s->metric == TSH_METRIC_COSINE ? nullptr : s->d_sqnorm, s->rows,
                                                                       fb.alpha, fb.beta, d_w);
   HIPCHK(hipMemcpyAsync(out_w, d_w, (size_t)s->rows * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
-  for (int64_t i = 0; i < s->rows; ++i) out_keys[i] = keys[(size_t)i] >= KEY_NAN ? std::nanf("") : h_key2f(keys[(size_t)i]);
   return TSH_OK;
 }
 
