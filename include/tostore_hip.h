@@ -47,7 +47,7 @@ extern "C" {
  *    tsh_ngh_info grew (row_base, row_end); tsh_comm_timeline's sampled fields are scaled by exchanges / timed
  *    exchanges instead of a constant.
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
- *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys. */
+ *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS. */
 
 /* status codes */
 #define TSH_OK 0
@@ -87,7 +87,9 @@ typedef struct tsh_counters {
                                 (see quarantined_rows); every search re-ranks all rows in f64 (exact, slow) */
   int32_t device_id;
   /* scan-kernel device time sampled with HIP events on the stream the kernel runs
-   * on, inside real searches (every 4th query): sum of microseconds / samples */
+   * on, inside real searches (every 4th query): sum of microseconds / samples.  The launch's own
+   * duration: where consecutive scans alternate between two streams (TSH_OPT_SCAN_STREAMS) a scan runs
+   * beside its neighbour and this is about twice its share of the HBM time */
   double scan_us_sum;
   int64_t scan_us_samples;
   int32_t batch_kernel_last; /* TSH_OPT_BATCH_KERNEL variant the last batched search ran (0/1/2; -1 none yet) */
@@ -629,6 +631,16 @@ int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
  * the f32 scan; two in a row keep the shard's next 256 eligible scans off the route.  Results are identical either way;
  * the scans count in tsh_scan_i8_stats. */
 #define TSH_OPT_SCAN_I8 10
+/* TSH_OPT_SCAN_STREAMS (default 0): on how many streams the single-query scans of overlapping queries (a multi-query
+ * call, several tickets out) run.  On one in-order stream the compute units empty at the end of every scan and nothing
+ * refills them until the next one starts: half a wave's life per scan, a share  tile bytes x waves per CU x CUs / 2 /
+ * bytes the scan moves  of it.  0 = by that share: two streams for every scan of fewer than 6144 tiles (as ever) and for
+ * bigger scans whose share is at least 4.5 % -- a big shard's scans over its int8 or fp16 copy; the f32 scan of 1 M x 768
+ * rows (3 %) keeps one.  1 = always one stream; 2 = two streams whenever queries overlap (tests, A/B runs).  On two
+ * streams consecutive scans run side by side: tsh_counters.scan_us_sum stays the sampled launch's OWN duration, which is
+ * then about twice its share of the HBM time -- it is not rescaled.  Results are identical either way.
+ * (Number 11 is not assigned: the suite pins it as an unknown id.) */
+#define TSH_OPT_SCAN_STREAMS 12
 /* TSH_OPT_TEST_HOOKS (process-wide; idx is ignored and may be NULL): value TSH_TEST_HOOKS_MAGIC switches the
  * library's TEST hooks on, 0 off.  Only then does it read the environment variables that change what it loads or make
  * it fail on purpose -- TSH_RCCL_LIB (a stand-in for librccl: tests/fake_rccl), TSH_TEST_FAIL_ALLOC_OVER (device

@@ -322,6 +322,13 @@ class HipVectorIndex:
         than 256 MiB), 2 every eligible scan whatever the size.  Results are identical."""
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_I8, int(mode)))
 
+    def set_scan_streams(self, mode: int) -> None:
+        """On how many streams the scans of overlapping single queries run: 0 by the scan's drain share (default: two for
+        scans of fewer than 6144 tiles and for a big shard's scans over its int8 or fp16 copy), 1 always one, 2 two
+        whenever queries overlap.  On two streams a sampled scan's own duration (counters()["scan_us_sum"]) is about
+        twice its share of the HBM time.  Results are identical."""
+        _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_STREAMS, int(mode)))
+
     def scan_i8_stats(self) -> dict:
         """The int8 scan's counters: scans launched, queries redone through the f32 scan, rows converted, copy bytes."""
         out = (ctypes.c_int64 * 4)()

@@ -5,10 +5,9 @@
 
 #include "tsh_batch.hip.h"
 #include "tsh_kernels.hip.h"
+#include "tsh_scan_overlap.h"  // SMALL_SHARD_TILES, RowStore, the dense scans' launch shape
 
 namespace tsh {
-
-constexpr int SMALL_SHARD_TILES = 6 * 4 * 256;  // below this: one-wave workgroups, two scan streams
 
 // Events that ride on the scan's own dispatch packet (hipExtLaunchKernel): a separate
 // hipEventRecord is a barrier packet of its own, and two or three of those between

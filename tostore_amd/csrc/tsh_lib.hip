@@ -313,6 +313,7 @@ struct Ctx {
 // Streams are a finite resource (CU-masked ones especially: about 85 open indexes with their own
 // five streams plus context streams crashed the runtime), and everything on one GPU shares its HBM and
 // CUs anyway -- so all shards of a device share ONE set, created on first use and never destroyed.
+constexpr int TAIL_CUS = 16;  // of a split device: two CUs of every XCD for the tails (make_scan_streams), the rest scan
 struct DeviceStreams {
   hipStream_t ingest = nullptr;
   hipStream_t scan = nullptr, scan2 = nullptr;  // pipeline streams (240-CU mask when cu_split)
@@ -356,8 +357,6 @@ struct ScanRouteState {
     return true;
   }
 };
-
-enum class RowStore { F32, F16, I8 };  // which copy of the rows a tile scan reads
 
 // One lazily kept reduced-precision copy of the row store (the fp16 copy, the int8 copy): row-major, one allocation.  Kept
 // current where a scan is enqueued (row_copy_ensure): rows [0, valid) are converted; appends past the watermark are
@@ -427,9 +426,10 @@ struct Shard {
   // (Running a query's tail beside the next query's scan was measured 10-25x
   // slower per tail: each dependent load queues behind the scan's loads.)
   hipStream_t scan_stream = nullptr;
-  // small shards alternate their scans between two streams (see job_enqueue)
+  // small shards, and big ones' scans over the int8 / fp16 copy, alternate between two streams (pick_scan_stream)
   hipStream_t scan_stream2 = nullptr;
   uint64_t scan_seq = 0;  // guarded by scan_mu
+  int scan_streams = 0;   // TSH_OPT_SCAN_STREAMS: 0 the rule (scan_two_streams), 1 one stream, 2 two whenever queries overlap
   // When several queries are in flight, a query's select + rerank run here, on
   // CUs the scan stream's CU mask leaves free (2 per XCD), so they overlap the
   // next query's scan without queueing behind its loads on the same CU.
@@ -1580,22 +1580,24 @@ void fill_job_args(const Shard *s, Job *j, const JobReq &rq, const float *q, Job
 }
 
 // ---- on which streams a job's kernels run (all of it under the device's scan_mu) ------------------------------------
-// The scan's stream; *which >= 0: one of the two scan streams of a small shard, booked in DeviceStreams::scan_out once
-// the scan is enqueued
-hipStream_t pick_scan_stream(Shard *s, bool overlap, int64_t rows_est, int *which) {
+// The scan's stream; *which >= 0: one of the two scan streams, for a scan that alternates between them (small shards,
+// big shards' scans with a large drain share), booked in DeviceStreams::scan_out once the scan is enqueued
+hipStream_t pick_scan_stream(Shard *s, RowStore store, bool overlap, int64_t rows_est, int *which) {
   *which = -1;
-  // Between two scans on one in-order stream the GPU idles for about 13 us (drain, write-back,
-  // ramp-up).  That is 3 % of a 1 M-row scan but 20 % of a 125 k-row one (a shard of an 8-GPU
-  // index), so small shards alternate between two streams and the next scan's workgroups fill
-  // in as the previous one drains (+12 % queries/s at 125 k and 250 k rows).  The two scans
-  // then run side by side, so each one's own duration roughly doubles; large shards keep one
-  // stream, where a scan's duration is its HBM time.  TSH_SCAN_STREAMS=1 / 2 forces either.
-  static const int forced = probe_env("TSH_SCAN_STREAMS") ? atoi(probe_env("TSH_SCAN_STREAMS")) : 0;
+  // Between two scans on one in-order stream the slots of the finished launch empty over one wave life and nothing
+  // refills them: half a wave life per scan, a share
+  //   tile_bytes x waves_per_CU x CUs / 2 / bytes_the_scan_moves
+  // of the scan (tsh_scan_overlap.h).  Where that share is large -- every small shard, and a big shard's scans over the
+  // int8 or fp16 copy, which read as few bytes as a quarter or half as many f32 rows -- consecutive scans alternate between
+  // two streams and the next scan's workgroups fill in as the previous one drains.  The two scans then run side by side,
+  // so each one's own duration roughly doubles; elsewhere one stream, where a scan's duration is its HBM time.
+  // TSH_OPT_SCAN_STREAMS = 1 / 2 forces either.
   // (a selective row mask makes a big shard's scan just as short: count the rows it keeps)
   const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
   const int64_t tiles_read = rows_est > 0 ? std::min<int64_t>(n_tiles, (rows_est + 63) / 64) : n_tiles;
-  static const int min_tiles = probe_env("TSH_TWO_STREAM_MIN_TILES") ? atoi(probe_env("TSH_TWO_STREAM_MIN_TILES")) : 0;
-  const bool two = forced == 2 || (forced != 1 && tiles_read < SMALL_SHARD_TILES && tiles_read >= min_tiles);
+  // (two scan streams exist on a split device only: the scans' CUs are those the tails' mask leaves)
+  const bool two = s->scan_streams == 2 ||
+                   (s->scan_streams == 0 && scan_two_streams(store, s->nch, s->ld, tiles_read, s->cus - TAIL_CUS));
   if (!(overlap && two && s->scan_stream2)) return s->scan_stream;
   DeviceStreams *ds = s->dstreams;
   for (size_t i = 0; i < ds->scan_out.size();) {  // scans that have finished since the last look
@@ -1753,7 +1755,9 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   {
     std::lock_guard<std::mutex> lk(*s->scan_mu);
     int which;
-    hipStream_t ps = pick_scan_stream(s, overlap, rq.mask.rows_est, &which), ts;
+    // (a first scan on the second stream needs no wait for the copy it reads: rows8_ensure / rows16_ensure above
+    // converted on scan_stream and synchronised on the host before they returned -- row_copy_ensure)
+    hipStream_t ps = pick_scan_stream(s, j->store, overlap, rq.mask.rows_est, &which), ts;
     j->timed = (s->c_scans.load() & 3) == 0;  // sample every 4th scan with timing events
     LaunchEv ev;  // start / stop ride on the scan's own packet: no barrier packets between scans
     if (j->timed) {
@@ -3457,6 +3461,8 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
        [](Shard *sh, int64_t v) { sh->rows16.mode_masked = (int)v; }},
       {TSH_OPT_SCAN_I8, 0, 2, "scan i8 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible scan)",
        [](Shard *sh, int64_t v) { sh->rows8.mode = (int)v; }},
+      {TSH_OPT_SCAN_STREAMS, 0, 2, "scan streams must be 0 (by the scan's drain share), 1 (one stream) or 2 (two whenever queries overlap)",
+       [](Shard *sh, int64_t v) { sh->scan_streams = (int)v; }},
       {TSH_OPT_BATCH_KERNEL, 0, 3, "batch kernel must be 0 (f32 MFMA), 1 (bf16x3), 2 (f16) or 3 (auto)",
        [](Shard *sh, int64_t v) { sh->batch_kernel = (int)v; }},
   };

@@ -32,9 +32,10 @@ namespace {
 // waves (keep 50 %: +2 % at eight waves, keep 10 %: -8 %): theirs stays.  One
 // tile per wave and a workgroup per two tiles stays: a grid of 480 / 960 / 1920 workgroups striding over the tiles
 // takes 560 / 500 / 457 us against 439-445.
+// (the figures live in tsh_scan_overlap.h, where the two-stream rule reads them too)
 template <int NCH> struct ScanShape {
-  static constexpr int WPB = NCH == 1 ? 4 : 2;                          // waves per workgroup
-  static constexpr int LDS = NCH == 1 ? 0 : (NCH == 2 ? 32768 : 65536);  // 160 KB per CU: 4 resp. 2 workgroups
+  static constexpr int WPB = scan_shape_wpb(NCH);  // waves per workgroup
+  static constexpr int LDS = scan_shape_lds(NCH);  // 160 KB per CU: 4 resp. 2 workgroups
 };
 
 // A family of tile-scan kernels, as the launcher below sees it: the kernel for (NCH, METRIC, FULL, MASKED) with its
@@ -47,7 +48,7 @@ struct ScanF32 {
     static constexpr int MINW =
         (NCH <= 2) ? 4 : (NCH == 3 ? (MASKED ? 4 : 3) : (NCH == 4 ? 4 : (NCH <= 6 ? 3 : (NCH <= 8 ? 2 : 1))));
   };
-  template <int NCH> using Shape = ScanShape<NCH>;
+  template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::F32, NCH)>;
   static constexpr bool HAS_MASKED = true;
   static constexpr int MAX_NCH = 16;
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
@@ -64,7 +65,7 @@ struct ScanF16 {
     static constexpr int R = NCH <= 6 ? 4 : 2;
     static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 8 ? 3 : 2);
   };
-  template <int NCH> using Shape = ScanShape<(NCH + 1) / 2>;
+  template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::F16, NCH)>;
   static constexpr bool HAS_MASKED = true;
   static constexpr int MAX_NCH = 14;  // (wider rows that end inside a chunk would spill: they stay on f32)
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
@@ -79,7 +80,7 @@ struct ScanI8 {
   template <int NCH> struct Tune {
     static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 6 ? 3 : 2);
   };
-  template <int NCH> using Shape = ScanShape<(NCH + 1) / 2>;
+  template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::I8, NCH)>;
   static constexpr bool HAS_MASKED = false;
   static constexpr int MAX_NCH = 8;
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
