@@ -47,7 +47,8 @@ extern "C" {
  *    tsh_ngh_info grew (row_base, row_end); tsh_comm_timeline's sampled fields are scaled by exchanges / timed
  *    exchanges instead of a constant.
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
- *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS. */
+ *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS;
+ *    TSH_OPT_SCAN_I8_MASKED. */
 
 /* status codes */
 #define TSH_OK 0
@@ -537,11 +538,12 @@ int32_t tsh_probe_scan_f16_keys(tsh_index *idx, const float *query, float *out_k
  * out[2] = rows converted into the copy so far, out[3] = bytes of the copy resident now (part of bytes_resident). */
 int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out);
 /* tsh_probe_scan_i8_keys: the int8 scan's (TSH_OPT_SCAN_I8, which must allow the scan) two sides of every row's
- * ranking key, out_lower[i] <= exact key of row i <= out_upper[i] being what its band claims (single-shard indexes
- * without dead rows; rows floats each).  For the band test. */
+ * ranking key, out_lower[i] <= exact key of row i <= out_upper[i] being what its band claims (single-shard indexes;
+ * rows floats each).  On an index with dead rows (tombstones, quarantined rows, gaps: TSH_OPT_SCAN_I8_MASKED must allow
+ * the scan) both are NaN for every row that is not live.  For the band test. */
 int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper);
-/* tsh_scan_i8_stats: out[0] scans over the int8 copy, out[1] queries redone through the f32 scan (survivor list
- * overflow), out[2] rows converted into the copy, out[3] device bytes the copy holds. */
+/* tsh_scan_i8_stats: out[0] scans over the int8 copy (dense and masked ones alike), out[1] queries redone through
+ * another scan (survivor list overflow), out[2] rows converted into the copy, out[3] device bytes the copy holds. */
 int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
 
 /* Tuning knobs (no reference counterpart).  TSH_OPT_BATCH_MIN_NQ: when tsh_search /
@@ -641,6 +643,19 @@ int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
  * then about twice its share of the HBM time -- it is not rescaled.  Results are identical either way.
  * (Number 11 is not assigned: the suite pins it as an unknown id.) */
 #define TSH_OPT_SCAN_STREAMS 12
+/* TSH_OPT_SCAN_I8_MASKED (default 1; additive since ABI 5): the int8 coarse pass of TSH_OPT_SCAN_I8 for single-query tile
+ * scans that are NOT dense -- behind a caller's row mask (pointer or handle; masks selective enough for the list scan or
+ * the exact path keep those), tombstones, quarantined rows or gaps of absent ids: only the live rows' bytes are read,
+ * dead tiles never count towards the threshold, and fewer live rows than k come back as exactly those.  0 = never; 1 =
+ * auto: shards whose row store is larger than 256 MiB, unless the fp16 masked route was forced (TSH_OPT_SCAN_F16_MASKED =
+ * 2: a forced value beats an automatic one); 2 = every eligible masked scan whatever the size (tests, A/B runs).
+ * TSH_OPT_SCAN_I8 = 0 switches both int8 routes off; its value 2 does not force this one.  A survivor list that
+ * overflows is redone behind the same mask through the fp16 masked scan where that applies, the f32 scan otherwise; two
+ * in a row keep the shard's next 256 eligible scans off the int8 routes.  Results are identical either way; the scans
+ * count in tsh_scan_i8_stats.  Measured on one MI355X, 1 M x 768, 64-query calls (profiles/scan_i8_masked_ab.json): one
+ * tombstone 228.3 -> 123.7 us per query, a keep-50 % mask 123.9 -> 66.9 (pointer) and 123.2 -> 66.3 (handle) against the
+ * fp16 masked scans, spread at most 2.5 %: hence 1 by default. */
+#define TSH_OPT_SCAN_I8_MASKED 13
 /* TSH_OPT_TEST_HOOKS (process-wide; idx is ignored and may be NULL): value TSH_TEST_HOOKS_MAGIC switches the
  * library's TEST hooks on, 0 off.  Only then does it read the environment variables that change what it loads or make
  * it fail on purpose -- TSH_RCCL_LIB (a stand-in for librccl: tests/fake_rccl), TSH_TEST_FAIL_ALLOC_OVER (device

@@ -177,6 +177,7 @@ TSH_OPT_SCAN_F16 = 8
 TSH_OPT_SCAN_F16_MASKED = 9
 TSH_OPT_SCAN_I8 = 10
 TSH_OPT_SCAN_STREAMS = 12
+TSH_OPT_SCAN_I8_MASKED = 13
 TSH_OPT_TEST_HOOKS = 1000
 TSH_TEST_HOOKS_MAGIC = 0x7465737468
 

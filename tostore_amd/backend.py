@@ -322,6 +322,13 @@ class HipVectorIndex:
         than 256 MiB), 2 every eligible scan whatever the size.  Results are identical."""
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_I8, int(mode)))
 
+    def set_scan_i8_masked(self, mode: int) -> None:
+        """The same coarse int8 pass for tile scans behind a row mask, tombstones, quarantined rows or gaps of absent ids:
+        0 never, 1 auto (default: shards whose row store is larger than 256 MiB, unless set_scan_f16_masked(2) forced the
+        fp16 masked route), 2 every eligible masked scan whatever the size.  set_scan_i8(0) switches both off;
+        set_scan_i8(2) does not force this one.  Results are identical."""
+        _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_I8_MASKED, int(mode)))
+
     def set_scan_streams(self, mode: int) -> None:
         """On how many streams the scans of overlapping single queries run: 0 by the scan's drain share (default: two for
         scans of fewer than 6144 tiles and for a big shard's scans over its int8 or fp16 copy), 1 always one, 2 two
@@ -330,7 +337,8 @@ class HipVectorIndex:
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_STREAMS, int(mode)))
 
     def scan_i8_stats(self) -> dict:
-        """The int8 scan's counters: scans launched, queries redone through the f32 scan, rows converted, copy bytes."""
+        """The int8 scan's counters: scans launched (dense and masked), queries redone through another scan, rows converted,
+        copy bytes."""
         out = (ctypes.c_int64 * 4)()
         _ffi.check(_ffi.lib().tsh_scan_i8_stats(self._h, out))
         return {"scans": out[0], "redone": out[1], "rows_converted": out[2], "copy_bytes": out[3]}

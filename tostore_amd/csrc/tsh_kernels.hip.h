@@ -302,7 +302,7 @@ static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqn
 }
 
 // ---------------------------------------------------------------------------
-// K1 over the int8 copy of the rows (big shards' dense, all-live tile scans): a quarter of the f32 scan's HBM bytes.
+// K1 over the int8 copy of the rows (big shards' tile scans, dense or MASKED): a quarter of the f32 scan's HBM bytes.
 // A COARSE first pass: its keys only have to name a set of rows that provably holds the top k -- the survivors go
 // through the exact path (tsh_scan_i8.hip.h, tsh_exact.hip.h), so no second band and no re-rank follow it.
 // The skeleton, dense, over RowsI8: a lane holds the same four ELEMENTS of a chunk (chunk = 256 elements = 256 contiguous
@@ -315,14 +315,18 @@ static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqn
 // and the band |key - exact| <= w_i of tsh_scan_i8_band.h.  keys[row] = the LOWER side key - w_i; gmin[tile] = the minimum
 // of the UPPER sides key + w_i: k distinct tiles hold a row whose exact key is at or below tau = the k-th smallest
 // gmin, so every row of the top k has a lower side <= tau, and the threshold step needs no band arithmetic.
-template <int NCH, int METRIC, bool FULL, int WAVES, int MINW>
+// MASKED (tombstones, gaps, quarantined rows, a caller's dense mask): R = 4, two groups per batch -- a masked tile's batch
+// count may be odd, which the one-group-per-batch pipeline does not take -- so a wave has half the dense kernel's bytes in
+// flight.  Dead lanes store KEY_DEAD and add KEY_DEAD to the tile's minimum, a dead tile stores only gmin = KEY_DEAD (its
+// keys[] stay stale: i8_survivor_kernel drops the tile by its gmin).  scale8, |row|^2 and 1/|row| are read for live rows
+// only: an absent row's scale was never written, a quarantined row's norm is not finite.
+template <int NCH, int METRIC, bool FULL, bool MASKED, int R, int WAVES, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) scan_i8_kernel(ScanArgsQ aq) {
   typedef RowsI8 Store;
-  constexpr bool MASKED = false;
-  constexpr int R = 8;
 #define TSH_SCAN_TILE_SETUP
 #include "tsh_scan_tile.inc.h"
-  for (int t = (int)blockIdx.x * wpb + wave; t < a.n_tiles; t += stride) {
+  for (int t = MASKED ? wave * (int)gridDim.x + (int)blockIdx.x : (int)blockIdx.x * wpb + wave; t < a.n_tiles;
+       t += stride) {
 #define TSH_SCAN_TILE_SUM
 #include "tsh_scan_tile.inc.h"
     const float sc = alive ? a.scale8[row] : 0.f;

@@ -37,10 +37,12 @@ bool scan_f16_supported(int nch, int dim);
 void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev = LaunchEv(),
                      bool mostly_live = false);
 
-// K1 over the int8 copy of the rows (a.a.rows16 = the copy, a.a.scale8 and the band fields of ScanArgs set): dense,
-// all-live tile scans of rows of up to eight chunks (scan_i8_supported).  tsh_scan_tu.hip
+// K1 over the int8 copy of the rows (a.a.rows16 = the copy, a.a.scale8 and the band fields of ScanArgs set): tile
+// scans, dense or masked, of rows of up to eight chunks (scan_i8_supported).  masked / mostly_live: launch_scan's.
+// tsh_scan_tu.hip
 bool scan_i8_supported(int nch);
-void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev = LaunchEv());
+void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev = LaunchEv(),
+                    bool mostly_live = false);
 
 // batched key pass (f32 MFMA / bf16x3 / f16 by a.Vs and a.dot_scale).  cus: compute units of the device the stream
 // belongs to (the persistent f16 kernels run one workgroup per CU).  tsh_batch_tu.hip

@@ -384,6 +384,14 @@ struct RowCopyF16 : RowCopy {
                         // rows or gaps (none of them while mode == 0)
 };
 // The int8 copy: ld biased bytes per row and behind the rows, in the same allocation, a scale per row
+struct RowCopyI8 : RowCopy {
+  using RowCopy::RowCopy;
+#ifndef TSH_SCAN_I8_MASKED_DEFAULT
+#define TSH_SCAN_I8_MASKED_DEFAULT 1  // (A/B builds: -DTSH_SCAN_I8_MASKED_DEFAULT=0, like TSH_SCAN_I8_DEFAULT)
+#endif
+  int mode_masked = TSH_SCAN_I8_MASKED_DEFAULT;  // TSH_OPT_SCAN_I8_MASKED: the same three for tile scans behind a mask, tombstones,
+                                                 // quarantined rows or gaps (none of them while mode == 0)
+};
 inline float *rows8_scales(const RowCopy &c, int64_t ld) {
   return c.d ? reinterpret_cast<float *>(static_cast<uint8_t *>(c.d) + c.cap * ld) : nullptr;
 }
@@ -510,14 +518,17 @@ struct Shard {
   int64_t hub_bytes = 0;
 
   // The fp16 copy of the rows that big shards' tile scans, dense or masked, read (scan_f16_kernel), and the int8 copy
-  // that their dense, all-live scans read as a coarse first pass (scan_i8_kernel).  One mutex guards both.
+  // that their scans, dense or masked, read as a coarse first pass (scan_i8_kernel).  One mutex guards both.
 #ifndef TSH_SCAN_I8_DEFAULT
 #define TSH_SCAN_I8_DEFAULT 1  // (A/B builds: -DTSH_SCAN_I8_DEFAULT=0, a variant library of its own -- tostore_amd/build.py)
 #endif
   RowCopyF16 rows16{1};
-  RowCopy rows8{TSH_SCAN_I8_DEFAULT};
+  RowCopyI8 rows8{TSH_SCAN_I8_DEFAULT};
   std::mutex row_copies_mu;
-  RowCopy *row_copy(RowStore st) { return st == RowStore::F16 ? &rows16 : st == RowStore::I8 ? &rows8 : nullptr; }
+  RowCopy *row_copy(RowStore st) {
+    if (st == RowStore::F16) return &rows16;
+    return st == RowStore::I8 ? &rows8 : nullptr;
+  }
 
   bool safe_mode() const {
     if (nonfinite_rows) return true;
@@ -1087,8 +1098,9 @@ struct Job {
                                 // overflowed is then NOT rewritten by the wide-band pass (a peer could gather a new
                                 // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
                                 // redoing the group with larger blocks, not ahead
+  bool no_i8 = false;  // enqueued as the redo of an int8 scan (JobReq::no_i8): a further redo stays off that route
   RowStore store = RowStore::F32;  // the copy of the rows its tile scan read (I8: survivors through the exact path).
-                                   // A list overflow of an F16 / I8 scan is redone through the f32 scan,
+                                   // A list overflow of an F16 / I8 scan is redone through another scan (redo_overflowed_scan),
   std::vector<float> redo_q;  // from this copy of the query, with this tag
   uint32_t tag = 0;
   ShardMask redo_mask;     // ... behind the same mask: a handle's part, or the context's own copy of a pointer mask's words
@@ -1356,12 +1368,17 @@ bool rows8_ensure(Shard *s, hipStream_t st) {
   });
 }
 
-// Could a scan of this shard take the coarse int8 route?  Dense and all-live only (the callers know about masks); the
-// exact path behind it needs a block of at least k entries.  (The shard's side of the decision: caller holds s->mu)
-bool scan_i8_applies(const Shard *s, int32_t k, int32_t entries) {
-  if (s->rows8.mode == 0 || s->rows8.denied || s->safe_mode() || !s->all_live || !s->quar_ids.empty()) return false;
+// Could a tile scan of this shard take the coarse int8 route?  masked: behind a caller's mask, tombstones, quarantined
+// rows or gaps -- TSH_OPT_SCAN_I8_MASKED decides for those, TSH_OPT_SCAN_I8 for dense scans and, at 0, for both; an
+// automatic masked route gives way to an fp16 masked route that was forced (TSH_OPT_SCAN_F16_MASKED = 2).  The exact path
+// behind the scan needs a block of at least k entries.  (The shard's side of the decision: caller holds s->mu)
+bool scan_i8_applies(const Shard *s, bool masked, int32_t k, int32_t entries) {
+  const int mode = masked ? s->rows8.mode_masked : s->rows8.mode;
+  if (s->rows8.mode == 0 || mode == 0 || s->rows8.denied || s->safe_mode()) return false;
+  if (!masked && (!s->all_live || !s->quar_ids.empty())) return false;
+  if (masked && mode == 1 && s->rows16.mode != 0 && s->rows16.mode_masked == 2) return false;
   if (!scan_i8_supported(s->nch) || k > entries || k > I8_LIST_CAP || s->rows <= 0) return false;
-  if (s->rows8.mode == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
+  if (mode == 1 && s->rows * s->ld * 4 <= SCAN_F16_MIN_BYTES) return false;
   if (s->metric == TSH_METRIC_COSINE && !(s->min_norm > 0.f)) return false;
   return true;
 }
@@ -1428,15 +1445,18 @@ Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, i
   // (tsh_exact.hip.h).  The block must have room for the k rows it will hold.
   r.n_exam = r.use_list ? (int64_t)m.list.padded : s->rows;
   r.exact = exact_applies(s, r.n_exam, k, entries);
-  // the coarse int8 route: dense, all-live tile scans inside the error model (TSH_OPT_SCAN_I8 = 2, the tests' setting,
-  // takes it for shards the exact path would answer whole, too)
-  if (!no_i8 && !masked && !r.use_list && (!r.exact || s->rows8.mode == 2) && scan_i8_applies(s, k, entries) && !compute_band(s, q).force_all) {
+  // the coarse int8 route: tile scans, dense or masked, inside the error model (TSH_OPT_SCAN_I8 = 2 resp.
+  // TSH_OPT_SCAN_I8_MASKED = 2, the tests' settings, take it for shards the exact path would answer whole, too)
+  if (!no_i8 && !r.use_list && (!r.exact || (masked ? s->rows8.mode_masked : s->rows8.mode) == 2) && scan_i8_applies(s, masked, k, entries) &&
+      !compute_band(s, q).force_all) {
     r.ib = scan_i8_band(s->metric, s->dim, s->nch, q, s->max_norm, s->min_norm, s->max_abs);
     r.i8_eligible = true;
     if (r.exact && r.ib.ok) r.exact = false;  // (mode 2; a denial or a full device below leaves such a shard to its f32 scan)
     // E2' needs as many live waves as k; the survivors -- at least k rows, at the front of the list -- guarantee
-    // ceil(k / EX_R) of them, and the host knows no more: the wide pick where that is enough, E2 otherwise
-    r.picked = s->exact_pick && (k + EX_R - 1) / EX_R >= k;
+    // ceil(k / EX_R) of them, and the host knows no more: the wide pick where that is enough, E2 otherwise.  Behind a
+    // mask not even k rows need be alive (a tombstoned index of five rows, or of none): always E2, which writes
+    // min(k, live rows) entries
+    r.picked = !masked && s->exact_pick && (k + EX_R - 1) / EX_R >= k;
   }
   if (r.exact) {
     // E2' (the wide pick) bounds the k-th key by the k-th smallest wave minimum: it needs clearly more waves than k
@@ -1653,7 +1673,7 @@ void launch_route_scan(const Shard *s, const Route &r, RowStore store, bool mask
   if (r.use_list) return launch_scan_list(sa, s->nch, s->metric, st, ev);
   const bool ml = masked && scan_mostly_live(rows_est > 0 ? rows_est : s->rows - s->deleted, s->rows);
   switch (store) {
-    case RowStore::I8: launch_scan_i8(sa, s->nch, s->metric, st, ev); break;
+    case RowStore::I8: launch_scan_i8(sa, s->nch, s->metric, masked, st, ev, ml); break;
     case RowStore::F16: launch_scan_f16(sa, s->nch, s->metric, masked, st, ev, ml); break;
     case RowStore::F32: launch_scan(sa, s->nch, s->metric, masked, st, ev, ml); break;
   }
@@ -1691,7 +1711,8 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     const int32_t n_tiles = ka.sa.a.n_tiles, n_blocks = (n_tiles + MASK_BLOCK_WORDS - 1) / MASK_BLOCK_WORDS;
     if (n_tiles <= SEL_VPT * SEL_THREADS) i8_tau_kernel<true><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
     else i8_tau_kernel<false><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
-    i8_survivor_kernel<<<(unsigned)((n_tiles + 4 * I8_SURV_TILES - 1) / (4 * I8_SURV_TILES)), 256, 0, ts>>>(c->d_keys, c->d_i8, n_tiles, i8_words(c));
+    i8_survivor_kernel<<<(unsigned)((n_tiles + 4 * I8_SURV_TILES - 1) / (4 * I8_SURV_TILES)), 256, 0, ts>>>(c->d_keys, j->masked ? c->d_gmin : nullptr, c->d_i8, n_tiles,
+                                                                                                            i8_words(c));
     mask_block_count_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, ts>>>(i8_words(c), n_tiles, i8_bsum(c));
     mask_compact_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, ts>>>(i8_words(c), n_tiles, i8_bsum(c), c->d_i8_list, c->d_i8 + 1,
                                                               (uint32_t)I8_LIST_CAP, (uint32_t)I8_LIST_CAP);
@@ -1718,6 +1739,7 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   static thread_local JobArgs ka;  // ScanArgsQ, ExactArgsQ: 4 KiB each: keep them off the stack of deep callers
   j->user_mask = rq.mask.words != nullptr;
   j->masked = j->user_mask || !s->all_live;
+  j->no_i8 = rq.no_i8;
   const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8);
   float *q;
   int rc = job_stage(s, j, rq, &ka, &q);
@@ -1736,15 +1758,12 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
     j->redo_q.assign(rq.query, rq.query + s->dim);
     j->tag = rq.tag;
     // (no list: such a scan walks tiles, and so does its redo.  A pointer mask's words were staged in c->h_mask under
-    // rq.mask.epoch -- by this job or an earlier one of the call -- and stay there while the job holds the context.
-    // An int8 scan has no mask)
+    // rq.mask.epoch -- by this job or an earlier one of the call -- and stay there while the job holds the context)
     j->redo_mask = ShardMask();
-    if (j->store == RowStore::F16) {
-      j->redo_mask.words = rq.mask.part ? rq.mask.words : (rq.mask.words ? c->h_mask : nullptr);
-      j->redo_mask.epoch = rq.mask.epoch;
-      j->redo_mask.rows_est = rq.mask.rows_est;
-      j->redo_mask.part = rq.mask.part;
-    }
+    j->redo_mask.words = rq.mask.part ? rq.mask.words : (rq.mask.words ? c->h_mask : nullptr);
+    j->redo_mask.epoch = rq.mask.epoch;
+    j->redo_mask.rows_est = rq.mask.rows_est;
+    j->redo_mask.part = rq.mask.part;
   }
   fill_job_args(s, j, rq, q, &ka);
   // with other queries already in flight -- or the caller about to submit more (the first query of a multi-query
@@ -1917,8 +1936,10 @@ int redo_overflowed_scan(Shard *s, Job *j) {
   rq.dev_target = j->dev_target;
   rq.last_of_call = true;
   rq.tag = j->tag;
-  rq.no_f16 = true;
-  rq.no_i8 = i8;
+  // (a masked int8 scan is redone through the fp16 masked scan where that applies; should THAT list overflow too, the f32
+  // scan follows below.  A dense one goes straight to f32, as ever)
+  rq.no_f16 = !(i8 && j->masked);
+  rq.no_i8 = i8 || j->no_i8;
   int rc = job_enqueue(s, j, rq);
   if (j->counted) {
     s->inflight.fetch_sub(1);
@@ -1927,6 +1948,7 @@ int redo_overflowed_scan(Shard *s, Job *j) {
   if (rc) return rc;
   HIPCHK(hipEventSynchronize(c->ev_done));
   HIPCHK(hipGetLastError());
+  if (i8 && j->store == RowStore::F16) return redo_overflowed_scan(s, j);
   return TSH_OK;
 }
 
@@ -3461,6 +3483,8 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
        [](Shard *sh, int64_t v) { sh->rows16.mode_masked = (int)v; }},
       {TSH_OPT_SCAN_I8, 0, 2, "scan i8 must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible scan)",
        [](Shard *sh, int64_t v) { sh->rows8.mode = (int)v; }},
+      {TSH_OPT_SCAN_I8_MASKED, 0, 2, "scan i8 masked must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible masked scan)",
+       [](Shard *sh, int64_t v) { sh->rows8.mode_masked = (int)v; }},
       {TSH_OPT_SCAN_STREAMS, 0, 2, "scan streams must be 0 (by the scan's drain share), 1 (one stream) or 2 (two whenever queries overlap)",
        [](Shard *sh, int64_t v) { sh->scan_streams = (int)v; }},
       {TSH_OPT_BATCH_KERNEL, 0, 3, "batch kernel must be 0 (f32 MFMA), 1 (bf16x3), 2 (f16) or 3 (auto)",
@@ -3552,7 +3576,8 @@ int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lo
   Shard *s = h.s;
   Ctx *c = h.c;
   hipStream_t st = h.st;
-  if (!scan_i8_applies(s, 1, 1) || compute_band(s, c->h_query).force_all)
+  const bool masked = !s->all_live || !s->quar_ids.empty();  // (dead rows: the keys of TSH_OPT_SCAN_I8_MASKED's route, NaN where a row is not live)
+  if (!scan_i8_applies(s, masked, 1, 1) || compute_band(s, c->h_query).force_all)
     return set_err(TSH_E_BAD_ARG, "no int8 scan for this index / query (TSH_OPT_SCAN_I8, dead rows, row width, error model)");
   const ScanI8Band ib = scan_i8_band(s->metric, s->dim, s->nch, c->h_query, s->max_norm, s->min_norm, s->max_abs);
   if (!ib.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the int8 scan's error model");
@@ -3560,7 +3585,9 @@ int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lo
   static thread_local ScanArgsQ sa;
   fill_scan_args(s, c, nullptr, nullptr, 0, &sa);
   fill_scan_i8_args(s, ib, &sa);
-  launch_scan_i8(sa, s->nch, s->metric, st);
+  // (a dead tile's keys stay as they were: the probe reads them all, so they start out dead)
+  if (masked) HIPCHK(hipMemsetAsync(c->d_keys, 0xFF, (size_t)((s->rows + 63) / 64) * 64 * 4, st));
+  launch_scan_i8(sa, s->nch, s->metric, masked, st);
   if ((rc = scan_hook_keys(h, out_lower))) return rc;
   // (the rows' bands, by the arithmetic the kernel forms them with -- into the keys buffer, free again once copied)
   std::vector<float> w((size_t)s->rows);

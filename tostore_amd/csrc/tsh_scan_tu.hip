@@ -75,16 +75,20 @@ struct ScanF16 {
 };
 // The int8 scan: a row is a quarter of the bytes, two register buffers of eight rows are 16 * NCH VGPRs, and the launch
 // shape is the fp16 scan's (ScanShape of half as many chunks: as many bytes in flight per CU as there).  Rows of up to
-// eight chunks (d <= 2048): beyond that the two buffers and the query leave the register budget.  Dense only.
+// eight chunks (d <= 2048): beyond that the two buffers and the query leave the register budget.
+// MASKED: buffers of four rows (two groups per batch, so a tile's odd batch count needs no tail of its own) within the
+// dense instantiations' MINW -- no scratch, at least their occupancy (profiles/scan_i8_masked_resources.txt).
 struct ScanI8 {
-  template <int NCH> struct Tune {
+  template <int NCH, bool MASKED> struct Tune {
+    static constexpr int R = MASKED ? 4 : 8;
     static constexpr int MINW = NCH <= 4 ? 4 : (NCH <= 6 ? 3 : 2);
   };
   template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::I8, NCH)>;
-  static constexpr bool HAS_MASKED = false;
+  static constexpr bool HAS_MASKED = true;
   static constexpr int MAX_NCH = 8;
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
-    return &scan_i8_kernel<NCH, METRIC, FULL, 4, Tune<NCH>::MINW>;
+    using T = Tune<NCH, MASKED>;
+    return &scan_i8_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>;
   }
 };
 
@@ -173,9 +177,9 @@ void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipSt
 
 bool scan_i8_supported(int nch) { return nch >= 1 && nch <= ScanI8::MAX_NCH; }
 
-void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev) {
+void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev, bool ml) {
   if (a.a.n_tiles <= 0) return;
-  launch_tile_scan<ScanI8>(a, nch, metric, false, 1, s, ev, false);
+  launch_tile_scan<ScanI8>(a, nch, metric, masked, std::max(1, (a.a.n_tiles + 3) / 4), s, ev, ml);
 }
 
 bool scan_list_supported(int nch, int64_t ld) { return nch >= 1 && nch <= 8 && ld != 128 && ld != 64 && ld != 32; }

@@ -817,9 +817,14 @@ final class HipVectorBackend {
 
   /// tsh_index_set_option: 1 = TSH_OPT_BATCH_MIN_NQ, 2 = TSH_OPT_BATCH_KERNEL, 4 = TSH_OPT_EXACT_SCAN_ROWS,
   /// 5 = TSH_OPT_EXACT_SELECT, 6 = TSH_OPT_BATCH_HUB, 7 = TSH_OPT_BATCH_GROUP, 8 = TSH_OPT_SCAN_F16,
-  /// 9 = TSH_OPT_SCAN_F16_MASKED, 10 = TSH_OPT_SCAN_I8, 12 = TSH_OPT_SCAN_STREAMS (tuning only: results never depend
-  /// on them).
+  /// 9 = TSH_OPT_SCAN_F16_MASKED, 10 = TSH_OPT_SCAN_I8, 12 = TSH_OPT_SCAN_STREAMS, 13 = TSH_OPT_SCAN_I8_MASKED (tuning
+  /// only: results never depend on them).
   bool setOption(int option, int value) => _setOption(_handle, option, value) == 0;
+
+  /// TSH_OPT_SCAN_I8_MASKED: the int8 coarse pass behind row masks, tombstones, quarantined rows and gaps -- 0 never,
+  /// 1 auto (shards above 256 MiB; gives way to a forced fp16 masked route), 2 every eligible masked scan.
+  static const int optScanI8Masked = 13;
+  bool setScanI8Masked(int mode) => setOption(optScanI8Masked, mode);
 
   /// The fp16 scan's counters (TSH_OPT_SCAN_F16): scans over the fp16 copy of the rows, queries redone through the
   /// f32 scan, rows converted, bytes of the copy resident.
