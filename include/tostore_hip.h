@@ -48,7 +48,7 @@ extern "C" {
  *    exchanges instead of a constant.
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
  *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS;
- *    TSH_OPT_SCAN_I8_MASKED. */
+ *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats. */
 
 /* status codes */
 #define TSH_OK 0
@@ -353,6 +353,36 @@ int32_t tsh_search_submit(tsh_index *idx, const float *query, int32_t k, const u
 int32_t tsh_search_ready(tsh_index *idx, int32_t ticket);
 int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double distance_threshold, int64_t *out_ids,
                         double *out_dist, int32_t *out_count);
+
+/* ---- search after a cursor: the next k rows past (distance, id) (additive since ABI 5) ----------------------
+ * Let L be the list tsh_search would return for the query with k = infinity, under the same mask, tombstones and
+ * threshold: ordered by Dart double.compareTo on the distance (-0.0 before 0.0, NaN last), ties by row id
+ * (ngh_graph_engine.dart:122-134).  tsh_search_after returns the first k entries of L that are strictly greater than
+ * (after_dist[q], after_id[q]) in that order; the cursor need not name an existing row.  after_dist = -inf with any id
+ * is "from the start" and equals tsh_search bit for bit.  The concatenation of successive pages, each started from the
+ * last entry of the page before, is exactly L; a page shorter than k is the last one.  Each page costs one scan,
+ * however deep it is: a pass over the scan's keys takes the rows at or before the cursor out of the select's sight,
+ * and the few rows whose f32 key cannot tell are decided by their exact distances (tostore_amd/csrc/tsh_after.hip.h,
+ * tsh_after_band.h).  "Everything within distance_threshold" is a loop of pages that ends at the first short page.
+ * row_mask / mask: at most one of the two forms of a WHERE row set, or neither.  after_dist / after_id: nq each.
+ * Works on whole-index handles, handles over several devices and shard handles (global ids).  Several queries per
+ * call run as the pipeline of single-query scans, never on the batched path.  TSH_E_BAD_ARG: both masks, a NULL
+ * cursor array, a mask handle made for another index.  tsh_search_submit_after is the asynchronous form; its ticket is
+ * waited for with tsh_search_wait.
+ * tsh_search_after_stats, summed over the shards (a search counts once per shard, as tsh_counters.searches does; that
+ * struct keeps its layout and counts cursor searches in searches and scan_launches like any other): out[0] = cursor
+ * searches, out[1] = rows their floor passes could not decide and sent to the side list, out[2] = searches redone
+ * because the side list overflowed (more than 1024 rows tied with the cursor), out[3] = searches answered without a
+ * floor on the device (safe mode, where the finaliser filters; a +inf or NaN cursor, which only quarantined rows can
+ * follow: no scan runs).
+ * Not covered: the sharded entries (tsh_search_shard*, tsh_search_sharded) -- a sharded caller pages per shard and
+ * merges. */
+int32_t tsh_search_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double distance_threshold,
+                         const uint8_t *row_mask, tsh_mask *mask, const double *after_dist, const int64_t *after_id,
+                         int64_t *out_ids, double *out_dist, int32_t *out_count);
+int32_t tsh_search_submit_after(tsh_index *idx, const float *query, int32_t k, const uint8_t *row_mask, tsh_mask *mask,
+                                double after_dist, int64_t after_id, int32_t *out_ticket);
+int32_t tsh_search_after_stats(tsh_index *idx, int64_t *out);
 
 /* ---- row-sharded deployments (one process per GPU) ----------------------
  * Each rank scans its shard and emits, per query, one fixed-size candidate

@@ -253,12 +253,58 @@ class HipVectorIndex:
                                          cnt.ctypes.data_as(_ffi.p_i32)))
         return ids[:, :kk], dist[:, :kk], cnt
 
+    def search_after(self, queries, k: int, after, distance_threshold: Optional[float] = None, row_mask=None):
+        """The next k rows past a cursor: (ids[nq,k], dist[nq,k], count[nq]) like search(), holding for every query the
+        first k entries, in the reference's order (distance by double.compareTo, ties by id), that are strictly greater
+        than its cursor.  after: one (distance, id) pair for all queries, or (distances[nq], ids[nq]); the last entry of
+        the page before continues a list, (-inf, anything) starts one.  A page shorter than k is the last one.
+        row_mask: None, a byte mask or a HipMask."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be nq x {self.dim}")
+        nq, kk = q.shape[0], max(int(k), 0)
+        a_dist = np.ascontiguousarray(np.broadcast_to(np.asarray(after[0], dtype=np.float64).reshape(-1), (nq,)))
+        a_id = np.ascontiguousarray(np.broadcast_to(np.asarray(after[1], dtype=np.int64).reshape(-1), (nq,)))
+        ids = np.empty((nq, max(kk, 1)), dtype=np.int64)
+        dist = np.empty((nq, max(kk, 1)), dtype=np.float64)
+        cnt = np.zeros(nq, dtype=np.int32)
+        thr = math.nan if distance_threshold is None else float(distance_threshold)
+        handle, mp = None, None
+        if isinstance(row_mask, HipMask):
+            handle = row_mask.handle()
+        else:
+            row_mask, mp = self.mask_arg(row_mask)
+        _ffi.check(_ffi.lib().tsh_search_after(self._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp, handle,
+                                               a_dist.ctypes.data_as(_ffi.p_f64), a_id.ctypes.data_as(_ffi.p_i64),
+                                               ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                               cnt.ctypes.data_as(_ffi.p_i32)))
+        return ids[:, :kk], dist[:, :kk], cnt
+
+    def search_after_stats(self) -> dict:
+        """The cursor searches' counters, per shard search: all of them, rows sent to the side list, searches redone with a
+        larger side list, searches answered without a floor pass on the device."""
+        out = (ctypes.c_int64 * 4)()
+        _ffi.check(_ffi.lib().tsh_search_after_stats(self._h, out))
+        return {"searches": out[0], "side_rows": out[1], "redone": out[2], "no_floor": out[3]}
+
     # -- asynchronous single-query form (several queries in flight) -----------------
-    def submit(self, query, k: int, row_mask=None) -> tuple:
+    def submit(self, query, k: int, row_mask=None, after=None) -> tuple:
+        """after: a (distance, id) cursor -- the ticket answers search_after() instead of search()."""
         q = _f32c(query).reshape(-1)
         if q.shape[0] != self.dim:
             raise ValueError(f"query must have {self.dim} elements")
         t = ctypes.c_int32(-1)
+        if after is not None:
+            handle, mp = None, None
+            if isinstance(row_mask, HipMask):
+                handle = row_mask.handle()
+            else:
+                row_mask, mp = self.mask_arg(row_mask)
+            _ffi.check(_ffi.lib().tsh_search_submit_after(self._h, q.ctypes.data_as(_ffi.p_f32), int(k), mp, handle,
+                                                          float(after[0]), int(after[1]), ctypes.byref(t)))
+            return (t.value, int(k))
         if isinstance(row_mask, HipMask):
             _ffi.check(_ffi.lib().tsh_search_submit_masked(self._h, q.ctypes.data_as(_ffi.p_f32), int(k), row_mask.handle(),
                                                            ctypes.byref(t)))
@@ -442,7 +488,8 @@ class HipVectorBackend:
         self.medoidNodeId = medoidNodeId  # NghIndexMeta.medoidNodeId (-1 until the first insert picked one)
 
     def search(self, *, query, topK: int, efSearch: Optional[int] = None,
-               distanceThreshold: Optional[float] = None, rowMask=None) -> list:
+               distanceThreshold: Optional[float] = None, rowMask=None, after=None) -> list:
+        """after: a (distance, nodeId) cursor -- the answer is the next topK rows past it (HipVectorIndex.search_after)."""
         # ref: :78  `if (meta.totalVectors == 0 || meta.medoidNodeId < 0) return const []`
         if self.index.size == 0 or topK <= 0:
             return []
@@ -453,6 +500,9 @@ class HipVectorBackend:
             topK = min(topK, max(ef, 0))
             if topK <= 0:
                 return []
-        ids, dist, cnt = self.index.search(query, topK, distanceThreshold, rowMask)
+        if after is not None:
+            ids, dist, cnt = self.index.search_after(query, topK, after, distanceThreshold, rowMask)
+        else:
+            ids, dist, cnt = self.index.search(query, topK, distanceThreshold, rowMask)
         n = int(cnt[0])
         return [NghSearchResult(nodeId=int(ids[0, i]), distance=float(dist[0, i])) for i in range(n)]

@@ -1143,13 +1143,11 @@ struct RerankArgs {
 };
 constexpr int RR_CHUNK = 1024;
 
-static __global__ void __launch_bounds__(64) rerank_kernel(RerankArgs a) {
+// a workgroup's share of K4: candidates blockIdx.x, + gridDim.x, ... below count (t0 / t1: RR_CHUNK doubles of LDS each).
+// rerank_kernel's body, shared with the side re-rank of a cursor search (after_side_kernel, tsh_after.hip.h)
+__device__ __forceinline__ void rerank_rows(const RerankArgs &a, const uint32_t count, double *t0, double *t1) {
 #pragma clang fp contract(off)
-  __shared__ __attribute__((aligned(16))) double t0[RR_CHUNK];
-  __shared__ __attribute__((aligned(16))) double t1[RR_CHUNK];
   const int lane = threadIdx.x;
-  uint32_t count = *a.count_ptr;
-  if (count > (uint32_t)a.cap) count = (uint32_t)a.cap;
   const int chains = a.metric == METRIC_COS ? 2 : 1;  // lane 0: s0, lane 1: row norm
   for (uint32_t c = blockIdx.x; c < count; c += gridDim.x) {
     uint32_t row = a.cand_rows[c];
@@ -1191,6 +1189,14 @@ static __global__ void __launch_bounds__(64) rerank_kernel(RerankArgs a) {
       a.out[c].s1 = a.metric == METRIC_COS ? s1 : 0.0;
     }
   }
+}
+
+static __global__ void __launch_bounds__(64) rerank_kernel(RerankArgs a) {
+  __shared__ __attribute__((aligned(16))) double t0[RR_CHUNK];
+  __shared__ __attribute__((aligned(16))) double t1[RR_CHUNK];
+  uint32_t count = *a.count_ptr;
+  if (count > (uint32_t)a.cap) count = (uint32_t)a.cap;
+  rerank_rows(a, count, t0, t1);
 }
 
 // Exact sums (rerank_kernel's arithmetic: strictly sequential f64, element order) of a shard's QUARANTINED rows

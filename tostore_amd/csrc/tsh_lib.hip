@@ -31,6 +31,8 @@
 #include <unistd.h>
 
 #include "../../include/tostore_hip.h"
+#include "tsh_after.hip.h"
+#include "tsh_after_band.h"
 #include "tsh_batch.hip.h"
 #include "tsh_batch_f16.hip.h"
 #include "tsh_exact.hip.h"
@@ -90,17 +92,21 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 // double.compareTo as an integer order: key(a) < key(b)  <=>  dart_compare(a, b) < 0, equal keys <=> compareTo == 0
 // (every NaN maps to the one largest key; -0.0 sorts just below +0.0).  Sorting (key, id) pairs with integer
 // compares is what the finaliser does for every query.
-inline uint64_t dart_order_key(double d) {
-  if (d != d) return ~0ull;
-  uint64_t b;
-  memcpy(&b, &d, 8);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// (the function itself lives in tsh_after_band.h, host only, where tests/cpp/after_band_test.cpp holds it to the order)
+inline uint64_t dart_order_key(double d) { return after_order_key(d); }
 struct Hit {
   uint64_t key;  // dart_order_key(distance)
   int64_t id;
 };
 inline bool hit_less(const Hit &a, const Hit &b) { return a.key != b.key ? a.key < b.key : a.id < b.id; }
+// The cursor of a search-after (tsh_search_after): the last (distance, id) the caller saw.  A row follows it iff its
+// (order key, id) is strictly greater
+struct Cursor {
+  double dist = 0;
+  int64_t id = 0;
+  Hit hit() const { return Hit{dart_order_key(dist), id}; }
+  bool from_start() const { return dist == -INFINITY; }  // "-inf with any id": nothing is at or before it
+};
 // Ascending by (key, id).  A query's candidates are k plus a band's worth of rows whose distances share their
 // leading bits, and std::sort spends 3-4 us on 127 of them (two thirds of a query's finalisation, mostly
 // mispredicted branches): one counting pass over 512 buckets of the key RANGE (a shift, so the bucket is monotone in
@@ -208,10 +214,12 @@ double query_mag_a(const float *q, int dim) {
 
 // threshold + order + cut of ngh_graph_engine.dart:127,133-134 over candidate
 // entries from any number of blocks.  mag_a: query_mag_a(query) when the caller has it already (the batched path
-// computes it while it prepares the queries), else nullptr.
+// computes it while it prepares the queries), else nullptr.  after: a cursor search's cursor -- entries at or before it
+// are dropped first, wherever they came from -- else nullptr.
 typedef std::pair<const BlockEntry *, uint32_t> EntryList;
 int32_t finalize_query(int metric, int dim, const float *query, int32_t k, double thr, const EntryList *lists_p,
-                       size_t n_lists, int64_t *out_ids, double *out_dist, const double *mag_a_known = nullptr) {
+                       size_t n_lists, int64_t *out_ids, double *out_dist, const double *mag_a_known = nullptr,
+                       const Cursor *after = nullptr) {
   struct {
     const EntryList *b, *e;
     const EntryList *begin() const { return b; }
@@ -226,13 +234,17 @@ int32_t finalize_query(int metric, int dim, const float *query, int32_t k, doubl
   for (auto &l : lists) total += l.second;
   hits.reserve(total);
   const bool has_thr = !std::isnan(thr);
+  if (after && after->from_start()) after = nullptr;
+  const Hit cur = after ? after->hit() : Hit{0, 0};
   for (auto &l : lists) {
     if (dist.size() < l.second) dist.resize(l.second);
     final_distances(metric, l.first, l.second, sqrt_mag_a, dist.data());
     for (uint32_t i = 0; i < l.second; ++i) {
       const double d = dist[i];
+      const Hit h{dart_order_key(d), l.first[i].id};
+      if (after && !after_follows(cur.key, cur.id, h.key, h.id)) continue;
       if (has_thr && d > thr) continue;
-      hits.push_back({dart_order_key(d), l.first[i].id});
+      hits.push_back(h);
     }
   }
   size_t r = std::min<size_t>(hits.size(), (size_t)std::max(k, 0));
@@ -253,8 +265,9 @@ int32_t finalize_query(int metric, int dim, const float *query, int32_t k, doubl
   return (int32_t)r;
 }
 inline int32_t finalize_query(int metric, int dim, const float *query, int32_t k, double thr,
-                              const std::vector<EntryList> &lists, int64_t *out_ids, double *out_dist) {
-  return finalize_query(metric, dim, query, k, thr, lists.data(), lists.size(), out_ids, out_dist);
+                              const std::vector<EntryList> &lists, int64_t *out_ids, double *out_dist,
+                              const Cursor *after = nullptr) {
+  return finalize_query(metric, dim, query, k, thr, lists.data(), lists.size(), out_ids, out_dist, nullptr, after);
 }
 
 // ---- kernel dispatch ---------------------------------------------------------
@@ -307,6 +320,14 @@ struct Ctx {
   // the survivor list of I8_LIST_CAP ids
   uint32_t *d_i8 = nullptr, *d_i8_list = nullptr;
   int64_t i8_tiles = 0;
+  // cursor searches (tsh_after.hip.h): the side list of the rows the floor pass could not decide, its two count words
+  // (side_flip: the one the next cursor job counts in -- the job before it left it at zero) and, pinned + mapped, their
+  // count and entries: [0].id = count, [1 ..] the entries
+  uint32_t *d_side_rows = nullptr, *d_side_cnt = nullptr;
+  BlockEntry *h_side = nullptr, *h_side_dev = nullptr;
+  int64_t side_cap = 0;
+  int side_flip = 0;
+  bool side_dirty = false;  // a cursor job is out, or one failed on the way: the count words are cleared before the next
   int64_t bytes = 0;
 };
 
@@ -464,6 +485,9 @@ struct Shard {
   int exact_rows = EX_MAX_ROWS;  // TSH_OPT_EXACT_SCAN_ROWS: searches that look at no more rows than this take that path
   bool exact_pick = true;        // TSH_OPT_EXACT_SELECT: the wide pick (exact_pick_kernel) behind the exact scan
   std::atomic<int64_t> c_pick_redone{0};  // picks whose cut bin overflowed the block: finished by exact_select_kernel
+  // cursor searches (tsh_search_after_stats): all of them, rows their floor passes sent to the side list, searches redone
+  // with a larger side list, searches answered without a floor pass (safe mode, a +inf / NaN cursor)
+  std::atomic<int64_t> c_after{0}, c_after_side{0}, c_after_redone{0}, c_after_nofloor{0};
   int cus = 0;  // compute units of the shard's device (grid of the persistent key kernels)
   std::atomic<int> f16_strikes{0};      // batched calls in a row whose fp16 bands overflowed many candidate lists
   std::atomic<int> f16_denied_calls{0};  // auto key-kernel choice: bf16x3 instead of fp16 for this many more batched calls
@@ -851,6 +875,9 @@ void ctx_free_all(Ctx *c) {
   hipFree(c->d_xpick);
   hipFree(c->d_i8);
   hipFree(c->d_i8_list);
+  hipFree(c->d_side_rows);
+  hipFree(c->d_side_cnt);
+  hipHostFree(c->h_side);
 }
 
 int ctx_prepare(Shard *s, Ctx *c, int32_t entries, bool need_mask) {
@@ -1108,6 +1135,15 @@ struct Job {
   hipStream_t last_stream = nullptr;  // where the job's last kernel was enqueued (ev_done rides on it)
   uint64_t enq_seq = 0;               // ... and its place in the device's enqueue order (DeviceStreams::enq_counter)
   std::vector<uint32_t> quar_sel;  // entries of c->h_quar that belong to this query's candidates
+  // a cursor job (JobReq::after): its floor in the scan's key space (floored: the floor pass and the side re-rank run;
+  // not in safe mode, not "from the start"), or no scan at all (after_skip: a +inf / NaN cursor, which only quarantined
+  // rows can follow).  Redone once with a larger side list if that overflowed -- from redo_query / redo_mask
+  bool has_after = false, floored = false, after_skip = false, after_redone = false;
+  Cursor after;
+  AfterFloor floor;
+  int side_word = 0;  // which of the context's two count words this job counts in
+  const float *redo_query = nullptr;  // the caller's query (a ticket's own copy): valid until the job is finished
+  std::vector<uint64_t> redo_words;   // a ticket's copy of a pointer mask's words (JobReq::mask_dies), else empty
 };
 
 void launch_select(const SelectArgs &se, int32_t n_tiles, hipStream_t st) {
@@ -1172,6 +1208,27 @@ int ctx_reserve_list(Ctx *c, int64_t padded) {
   HIPCHK(hipHostMalloc(&c->h_list, (size_t)want * sizeof(uint32_t), hipHostMallocMapped));
   HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_list_dev), c->h_list, 0));
   c->list_cap = want;
+  c->bytes += want * 4;
+  return TSH_OK;
+}
+
+// the side list of a cursor job (tsh_after.hip.h): room for `want` undecided rows
+int ctx_reserve_side(Ctx *c, int64_t want) {
+  if (!c->d_side_cnt) {
+    HIPCHK(hipMalloc(&c->d_side_cnt, 2 * sizeof(uint32_t)));
+    c->side_dirty = true;
+  }
+  if (want <= c->side_cap) return TSH_OK;
+  hipFree(c->d_side_rows);
+  hipHostFree(c->h_side);
+  c->d_side_rows = nullptr;
+  c->h_side = c->h_side_dev = nullptr;
+  c->bytes -= c->side_cap * 4;
+  c->side_cap = 0;
+  HIPCHK(hipMalloc(&c->d_side_rows, (size_t)want * sizeof(uint32_t)));
+  HIPCHK(hipHostMalloc(&c->h_side, (size_t)(want + 1) * sizeof(BlockEntry), hipHostMallocMapped));
+  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_side_dev), c->h_side, 0));
+  c->side_cap = want;
   c->bytes += want * 4;
   return TSH_OK;
 }
@@ -1436,10 +1493,18 @@ void fill_scan_f16_args(const Shard *s, const ScanF16Band &fb, ScanArgsQ *aq, Se
 // The route of one query's scan on this shard, decided here for every caller and without side effects.  m: the search's
 // mask (resolve_mask); masked: a mask or tombstones; q: the query (dim floats are read: zero-padded or not); no_f16:
 // the redo of an fp16 scan.  Caller holds s->mu shared.
+// after: a cursor job -- the f32 tile scan or the list scan, never the exact path or a reduced copy (tsh_after.hip.h)
 Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, int32_t entries, const float *q, bool no_f16,
-                   bool no_i8 = false) {
+                   bool no_i8 = false, bool after = false) {
   Route r;
   r.use_list = m.listed();
+  if (after) {
+    // (a list made for the exact path alone may be of a width scan_list_kernel does not serve: tiles behind the mask then)
+    r.use_list = r.use_list && scan_list_supported(s->nch, s->ld);
+    r.n_exam = r.use_list ? (int64_t)m.list.padded : s->rows;
+    r.band = compute_band(s, q);
+    return r;
+  }
   // A search with only a few thousand rows to look at (a selective mask's list, a small index or shard) takes their
   // exact sums directly and selects among the exact distances: two dispatches instead of three, no f32 keys, no band
   // (tsh_exact.hip.h).  The block must have room for the k rows it will hold.
@@ -1481,6 +1546,9 @@ struct JobReq {
   uint32_t tag = 0;               // generation stamped into the block's header
   bool no_f16 = false;            // the redo of an fp16 scan whose list overflowed: f32 this time
   bool no_i8 = false;             // the redo of an int8 scan whose survivor list overflowed (with no_f16: f32)
+  const Cursor *after = nullptr;  // a cursor search: only rows past it are wanted
+  int64_t side_want = 0;          // ... redone after its side list overflowed: room for this many rows
+  bool mask_dies = false;         // ... enqueued for a ticket: a pointer mask's words and list are gone before the job is finished
 };
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
 struct JobArgs {
@@ -1724,13 +1792,52 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
   } else if (j->route.exact || i8) {
     TSH_LAUNCH_EV(exact_select_kernel, 1, 1024, ts, none, done, j->xsel);
   } else {
+    // a cursor job: the floor pass takes the rows at or before the cursor out of the select's sight (A1), and the rows
+    // it could not decide get their exact sums behind the re-rank (A2) -- tsh_after.hip.h
+    const uint32_t side_cap = (uint32_t)c->side_cap;
+    uint32_t *const side_count = j->floored ? c->d_side_cnt + j->side_word : nullptr;
+    if (j->floored) {
+      const AfterFloorArgs fa{c->d_keys, c->d_gmin, j->d_list, c->d_side_rows, side_count, ka.se.n_tiles, side_cap, j->floor.lo, j->floor.hi};
+      after_floor_kernel<<<(unsigned)((ka.se.n_tiles + 3) / 4), 256, 0, ts>>>(fa);
+    }
     launch_select(ka.se, ka.se.n_tiles, ts);
-    TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, done, ka.ra);
+    TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, j->floored ? none : done, ka.ra);
+    if (j->floored) {
+      const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
+                             s->dim, s->metric, side_cap};
+      // (a page has a row or two to decide: 64 workgroups stride over a full list of AFTER_SIDE_CAP ids; only a redo's
+      // larger list gets the re-rank's own grid)
+      TSH_LAUNCH_EV(after_side_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, ts, none, done, sd);
+    }
   }
   if (!quar) return TSH_OK;
   if (j->dev_target) launch_quarantine_append(s, c, j, ts);
   else launch_quarantine(s, c, ts);
   HIPCHK(hipEventRecord(c->ev_done, ts));
+  return TSH_OK;
+}
+
+// A cursor job whose cursor no scanned row can follow (a +inf or NaN distance): an empty block, and the quarantined rows
+// the mask keeps.  q: the staged query (job_stage)
+int enqueue_after_skip(Shard *s, Job *j, const float *q) {
+  Ctx *c = j->c;
+  BlockHeader *h = reinterpret_cast<BlockHeader *>(c->h_block);
+  memset(h, 0, sizeof *h);
+  h->entries = (uint32_t)j->entries;
+  h->k = (uint32_t)j->k;
+  h->metric = (uint32_t)s->metric;
+  h->row_base = s->row_base;
+  h->shard_rows = s->rows;
+  j->store = RowStore::F32;
+  j->timed = j->counted = false;
+  hipStream_t st = s->aux_stream;
+  if (!j->quar_sel.empty()) {
+    if (q != c->h_query) memcpy(c->h_query, q, (size_t)s->ld * sizeof(float));
+    HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
+    launch_quarantine(s, c, st);
+  }
+  HIPCHK(hipEventRecord(c->ev_done, st));
+  j->last_stream = st;
   return TSH_OK;
 }
 
@@ -1740,10 +1847,50 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   j->user_mask = rq.mask.words != nullptr;
   j->masked = j->user_mask || !s->all_live;
   j->no_i8 = rq.no_i8;
-  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8);
+  j->has_after = rq.after != nullptr;
+  j->after_redone = rq.side_want > 0;
+  if (rq.after) j->after = *rq.after;
+  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after);
+  // A cursor inside the error model gets its floor in the scan's key space (tsh_after_band.h); "from the start" has
+  // none; a +inf or NaN cursor can only be followed by quarantined rows -- every row the scan offers has a finite
+  // distance -- so no scan runs at all.  Safe mode: no floor, the finaliser filters.
+  j->floored = j->after_skip = false;
+  if (j->has_after && !r.band.force_all) {
+    if (!(j->after.dist < INFINITY)) {
+      j->after_skip = true;
+    } else {
+      j->floor = after_floor(s->metric, s->dim, r.band.eps_rel, r.band.delta_abs,
+                             s->metric == TSH_METRIC_COSINE ? query_mag_a(rq.query, s->dim) : 0.0, j->after.dist);
+      j->floored = !j->floor.none();
+    }
+  }
   float *q;
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
+  if (j->after_skip) return enqueue_after_skip(s, j, q);
+  if (j->floored) {
+    if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(rq.side_want, AFTER_SIDE_CAP), c->side_cap)))) return rc;
+    if (c->side_dirty) {  // (a context's first cursor job, or one after a job that failed on its way)
+      HIPCHK(hipMemsetAsync(c->d_side_cnt, 0, 2 * sizeof(uint32_t), s->aux_stream));
+      HIPCHK(hipStreamSynchronize(s->aux_stream));
+    }
+    c->side_dirty = true;  // until this job is seen finished (job_finish)
+    j->side_word = c->side_flip;
+    c->side_flip ^= 1;
+    // what a redo with a larger side list needs: the query, the tag and the mask, all by reference -- they outlive the
+    // job (a synchronous call finishes its jobs before it returns; a ticket holds the query).  Only a ticket behind a
+    // pointer mask (rq.mask_dies) must keep the words itself: the caller's slice is gone when it is waited for, and so
+    // is the list made from it -- that redo walks tiles behind the copied words
+    j->redo_query = rq.query;
+    j->tag = rq.tag;
+    j->redo_mask = rq.mask;
+    if (rq.mask_dies && !rq.mask.part && rq.mask.words) {
+      j->redo_mask.list = RowList();
+      if (rq.mask.words != j->redo_words.data())
+        j->redo_words.assign(rq.mask.words, rq.mask.words + (size_t)((s->rows + 63) / 64));
+      j->redo_mask.words = j->redo_words.data();
+    }
+  }
   // (an eligible scan uses up a denial of its route, if any are left, whatever its band; a scan that takes the int8
   // route neither asks for the fp16 copy nor touches the fp16 route's denials)
   j->store = RowStore::F32;
@@ -1952,6 +2099,34 @@ int redo_overflowed_scan(Shard *s, Job *j) {
   return TSH_OK;
 }
 
+// A finished cursor job whose floor pass found more undecided rows than its side list holds (ties by the thousand) is
+// redone once with a list sized to the count it reported: the same scan over the same rows finds the same count.
+int redo_after_side(Shard *s, Job *j) {
+  Ctx *c = j->c;
+  c->side_dirty = false;  // (finished: A2 left the context's other count word at zero)
+  const int64_t n = c->h_side[0].id;
+  if (n <= c->side_cap) return TSH_OK;
+  if (j->after_redone) return set_err(TSH_E_HIP, "a cursor search's side list overflowed twice (%lld rows): internal error", (long long)n);
+  s->c_after_redone++;
+  const Cursor cur = j->after;
+  JobReq rq(j->redo_query, j->k, j->entries);
+  rq.mask = j->redo_mask;
+  rq.mask_dies = !j->redo_words.empty() && j->redo_mask.words == j->redo_words.data();
+  rq.last_of_call = true;
+  rq.tag = j->tag;
+  rq.after = &cur;
+  rq.side_want = round_up(n, 1024);
+  int rc = job_enqueue(s, j, rq);
+  if (j->counted) {
+    s->inflight.fetch_sub(1);
+    j->counted = false;
+  }
+  if (rc) return rc;
+  HIPCHK(hipEventSynchronize(c->ev_done));
+  HIPCHK(hipGetLastError());
+  return redo_after_side(s, j);
+}
+
 // Waits for a job; afterwards c->h_block / c->d_block hold the final block
 // (and *spill every candidate when they did not fit); *extra gets the quarantined rows' entries.
 int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<BlockEntry> *extra) {
@@ -1965,6 +2140,10 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   HIPCHK(hipGetLastError());
   if (j->store != RowStore::F32) {
     int rc = redo_overflowed_scan(s, j);
+    if (rc) return rc;
+  }
+  if (j->floored) {
+    int rc = redo_after_side(s, j);
     if (rc) return rc;
   }
   if (j->timed) {
@@ -2015,6 +2194,17 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     extra->clear();
     for (uint32_t i : j->quar_sel) extra->push_back(c->h_quar[i]);
   }
+  if (j->has_after) {
+    s->c_after++;
+    if (j->after_skip || (j->route.band.force_all && !j->after.from_start())) s->c_after_nofloor++;
+  }
+  if (j->floored) {  // the rows the floor pass could not decide join the candidates too
+    if (!extra) return set_err(TSH_E_BAD_ARG, "no room for the side list's entries");
+    if (j->quar_sel.empty()) extra->clear();
+    const uint32_t side_n = (uint32_t)c->h_side[0].id;
+    extra->insert(extra->end(), c->h_side + 1, c->h_side + 1 + side_n);
+    s->c_after_side += side_n;
+  }
   s->c_searches++;
   return TSH_OK;
 }
@@ -2047,6 +2237,9 @@ struct SearchOut {
   std::function<void(int32_t q, hipEvent_t done, hipStream_t where, uint64_t seq)> on_enqueued;
   uint32_t tag = 0;  // generation stamped into the blocks' headers (BlockHeader.pad[1])
   bool leave_overflow = false;  // device mode: see Job::leave_overflow
+  // single-query pipeline, host mode: a cursor per query (tsh_search_after), or NULL
+  const double *after_dist = nullptr;
+  const int64_t *after_id = nullptr;
 };
 
 // One submitting thread's share of a multi-query call: queries [q0, q1) of the call, at most
@@ -2087,6 +2280,12 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       rq.more_coming = cnt > 1;
       rq.last_of_call = cnt > 1 && submitted == cnt - 1;
       rq.tag = out->tag;
+      Cursor cur;
+      if (out->after_dist) {
+        cur.dist = out->after_dist[q];
+        cur.id = out->after_id[q];
+        rq.after = &cur;
+      }
       rc = job_enqueue(s, &j, rq);
       if (rc) {
         release_all();
@@ -2161,6 +2360,8 @@ int shard_search_blocks(Shard *s, const float *queries, int32_t nq, int32_t k, c
 // shards stay share-locked until the wait so appends cannot move the rows
 struct Ticket {
   int32_t k = 0, entries = 0;
+  bool has_after = false;  // tsh_search_submit_after: the wait's finaliser filters by the cursor
+  Cursor after;
   std::vector<float> query;
   std::vector<Job> jobs;
   std::vector<std::shared_lock<RwLock>> locks;
@@ -2604,9 +2805,10 @@ int32_t tsh_default_block_entries(int32_t k) {
   return (int32_t)std::min<int64_t>(e, 1 << 20);
 }
 
+// after_dist / after_id: a cursor per query (tsh_search_after), or both NULL
 static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr,
                            const uint8_t *row_mask, tsh_mask *mask_h, int64_t *out_ids, double *out_dist,
-                           int32_t *out_count) {
+                           int32_t *out_count, const double *after_dist = nullptr, const int64_t *after_id = nullptr) {
   if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
   if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
   if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
@@ -2649,7 +2851,9 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
     so.h_blocks = blocks[g].get();
     so.spill = &spills[g];
     so.extra = &extras[g];
-    if (ns == 1)  // batched path: finalise a chunk of queries while the GPU still works on the next one
+    so.after_dist = after_dist;
+    so.after_id = after_id;
+    if (ns == 1 && !after_dist)  // batched path: finalise a chunk of queries while the GPU still works on the next one
       so.on_chunk = [&](int32_t q0, int32_t q1, const char *skip, const uint8_t *base, const double *mag_a) {
         parallel_for_range(q0, q1, [&](int32_t q) {
           if (skip[q]) return;
@@ -2664,7 +2868,7 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
           finalized[(size_t)q] = 1;
         });
       };
-    if (ns == 1) {
+    if (ns == 1 && !after_dist) {
       so.fin_thr = thr;
       so.on_final = [&](int32_t q0, int32_t q1, const char *skip, const int64_t *ids, const double *dist, const int32_t *cnt) {
         parallel_for_range(q0, q1, [&](int32_t q) {
@@ -2685,7 +2889,9 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
       }
       ms = MaskSrc(mp);
     }
-    rcs[g] = shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, ms, entries, &so);
+    // (cursor searches: the pipeline of single-query scans, never the batched path)
+    rcs[g] = after_dist ? shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH)
+                        : shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, ms, entries, &so);
     if (rcs[g]) errs[g] = g_err;
   };
   if (ns == 1) {
@@ -2723,8 +2929,13 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
       const std::vector<BlockEntry> &ex = extras[g][(size_t)q];
       if (!ex.empty()) lists.push_back({ex.data(), (uint32_t)ex.size()});
     }
+    Cursor cur;
+    if (after_dist) {
+      cur.dist = after_dist[q];
+      cur.id = after_id[q];
+    }
     out_count[q] = finalize_query(idx->metric, idx->dim, queries + (size_t)q * idx->dim, k, thr, lists,
-                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k);
+                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k, after_dist ? &cur : nullptr);
   });
   if (trace_batch() && nq >= 64)
     fprintf(stderr, "[tsh search] nq=%d shards %.0f us, finalize %.0f us\n", nq, t_shards - t_in, now_us() - t_shards);
@@ -2739,6 +2950,27 @@ int32_t tsh_search(tsh_index *idx, const float *queries, int32_t nq, int32_t k, 
 int32_t tsh_search_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, tsh_mask *mask,
                           int64_t *out_ids, double *out_dist, int32_t *out_count) {
   return search_impl(idx, queries, nq, k, thr, nullptr, mask, out_ids, out_dist, out_count);
+}
+
+int32_t tsh_search_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const uint8_t *row_mask,
+                         tsh_mask *mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                         double *out_dist, int32_t *out_count) {
+  if (row_mask && mask) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return search_impl(idx, queries, nq, k, thr, row_mask, mask, out_ids, out_dist, out_count, after_dist, after_id);
+}
+
+int32_t tsh_search_after_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  for (auto &sp : idx->shards) {
+    out[0] += sp->c_after.load();
+    out[1] += sp->c_after_side.load();
+    out[2] += sp->c_after_redone.load();
+    out[3] += sp->c_after_nofloor.load();
+  }
+  return TSH_OK;
 }
 
 int32_t tsh_mask_create(tsh_index *idx, const uint8_t *bits, int64_t n_bytes, tsh_mask **out) {
@@ -2812,7 +3044,7 @@ int64_t tsh_mask_kept(tsh_mask *mask) {
 int32_t tsh_max_inflight(void) { return MAX_CTX; }
 
 static int32_t submit_impl(tsh_index *idx, const float *query, int32_t k, const uint8_t *row_mask, tsh_mask *mask_h,
-                           int32_t *out_ticket) {
+                           int32_t *out_ticket, const Cursor *after = nullptr) {
   if (!idx || !query || !out_ticket) return set_err(TSH_E_BAD_ARG, "NULL pointer");
   if (k <= 0) return set_err(TSH_E_BAD_ARG, "k <= 0");
   if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
@@ -2821,6 +3053,8 @@ static int32_t submit_impl(tsh_index *idx, const float *query, int32_t k, const 
   t->k = k;
   t->entries = tsh_default_block_entries(k);
   t->query.assign(query, query + idx->dim);
+  t->has_after = after != nullptr;
+  if (after) t->after = *after;
   t->jobs.resize(idx->shards.size());
   t->locks.resize(idx->shards.size());
   int rc = TSH_OK;
@@ -2855,8 +3089,10 @@ static int32_t submit_impl(tsh_index *idx, const float *query, int32_t k, const 
       if (!mp) break;
       src = MaskSrc(mp);
     }
-    JobReq rq(query, k, t->entries);
+    JobReq rq(t->query.data(), k, t->entries);  // (the ticket's copy: a cursor job may be redone from it at the wait)
     rq.mask = resolve_mask(s, src, k, t->entries, &words, &list_ids);
+    rq.after = after;
+    rq.mask_dies = true;
     rc = job_enqueue(s, &t->jobs[g], rq);
   }
   if (rc != TSH_OK) {
@@ -2892,6 +3128,16 @@ int32_t tsh_search_submit(tsh_index *idx, const float *query, int32_t k, const u
 }
 int32_t tsh_search_submit_masked(tsh_index *idx, const float *query, int32_t k, tsh_mask *mask, int32_t *out_ticket) {
   return submit_impl(idx, query, k, nullptr, mask, out_ticket);
+}
+
+int32_t tsh_search_submit_after(tsh_index *idx, const float *query, int32_t k, const uint8_t *row_mask, tsh_mask *mask,
+                                double after_dist, int64_t after_id, int32_t *out_ticket) {
+  if (row_mask && mask) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  Cursor cur;
+  cur.dist = after_dist;
+  cur.id = after_id;
+  return submit_impl(idx, query, k, row_mask, mask, out_ticket, &cur);
 }
 
 int32_t tsh_search_ready(tsh_index *idx, int32_t ticket) {
@@ -2948,7 +3194,8 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double thr, int64_t *out
     }
   }
   if (rc == TSH_OK)
-    *out_count = finalize_query(idx->metric, idx->dim, t->query.data(), t->k, thr, lists, out_ids, out_dist);
+    *out_count = finalize_query(idx->metric, idx->dim, t->query.data(), t->k, thr, lists, out_ids, out_dist,
+                                t->has_after ? &t->after : nullptr);
   std::string keep = g_err;
   for (size_t g = 0; g < idx->shards.size(); ++g)
     if (t->jobs[g].c) ctx_release(idx->shards[g].get(), t->jobs[g].c);

@@ -106,6 +106,16 @@ typedef _ProbeScanF16C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<F
 typedef _ProbeScanF16D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ScanI8StatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
 typedef _ScanI8StatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchAfterC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SearchAfterD = int Function(Pointer<Void>, Pointer<Float>, int, int, double, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SubmitAfterC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Pointer<Uint8>, Pointer<Void>,
+    Double, Int64, Pointer<Int32>);
+typedef _SubmitAfterD = int Function(Pointer<Void>, Pointer<Float>, int, Pointer<Uint8>, Pointer<Void>,
+    double, int, Pointer<Int32>);
+typedef _SearchAfterStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchAfterStatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
@@ -315,6 +325,9 @@ final class HipVectorBackend {
   static late final _ScanF16StatsD _scanF16Stats;
   static late final _ProbeScanF16D _probeScanF16;
   static late final _ScanI8StatsD _scanI8Stats;
+  static late final _SearchAfterD _searchAfter;
+  static late final _SubmitAfterD _submitAfter;
+  static late final _SearchAfterStatsD _searchAfterStats;
   static late final _ProbeScanI8D _probeScanI8;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
@@ -373,6 +386,10 @@ final class HipVectorBackend {
       _scanF16Stats = lib.lookupFunction<_ScanF16StatsC, _ScanF16StatsD>('tsh_scan_f16_stats');
       _probeScanF16 = lib.lookupFunction<_ProbeScanF16C, _ProbeScanF16D>('tsh_probe_scan_f16_keys');
       _scanI8Stats = lib.lookupFunction<_ScanI8StatsC, _ScanI8StatsD>('tsh_scan_i8_stats');
+      _searchAfter = lib.lookupFunction<_SearchAfterC, _SearchAfterD>('tsh_search_after');
+      _submitAfter = lib.lookupFunction<_SubmitAfterC, _SubmitAfterD>('tsh_search_submit_after');
+      _searchAfterStats =
+          lib.lookupFunction<_SearchAfterStatsC, _SearchAfterStatsD>('tsh_search_after_stats');
       _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
@@ -747,6 +764,11 @@ final class HipVectorBackend {
       calloc.free(ticket);
       if (maskBytes != nullptr) calloc.free(maskBytes);
     }
+    return _collect(t, topK, distanceThreshold);
+  }
+
+  /// Polls a ticket and collects its result (the second half of [searchAsync] and [searchAfterAsync]).
+  Future<List<NghSearchResult>?> _collect(int t, int topK, double? distanceThreshold) async {
     // every ticket must be waited exactly once: from here on nothing may return before _wait ran.
     // The first polls yield with a zero delay (a short scan is over by then); after that the isolate sleeps
     // between polls -- a zero-delay timer loop would keep its event loop at 100 % CPU for the whole scan, and
@@ -781,6 +803,103 @@ final class HipVectorBackend {
       calloc.free(ids);
       calloc.free(dist);
       calloc.free(cnt);
+    }
+  }
+
+  /// The next `topK` rows past a cursor (tsh_search_after; no reference counterpart): the first `topK` entries of
+  /// the list [search] would return with topK = infinity -- ordered by distance (double.compareTo), ties by node id,
+  /// ngh_graph_engine.dart:122-134 -- that are strictly greater than (`afterDistance`, `afterNodeId`), usually the
+  /// last entry of the page before.  `afterDistance` = double.negativeInfinity starts a list.  Successive pages
+  /// concatenate to exactly that list; a page shorter than `topK` is the last one; each page costs one scan however
+  /// deep it is.  "Every row within distanceThreshold" is a loop of pages.  Null on any native failure.
+  List<NghSearchResult>? searchAfter(Float32List query, int topK, double afterDistance, int afterNodeId,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) {
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchAfter with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (topK <= 0 || size == 0) return const [];
+    final q = calloc<Float>(dimensions);
+    final ids = calloc<Int64>(topK);
+    final dist = calloc<Double>(topK);
+    final cnt = calloc<Int32>();
+    final aDist = calloc<Double>();
+    final aId = calloc<Int64>();
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      aDist.value = afterDistance;
+      aId.value = afterNodeId;
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _searchAfter(_handle, q, 1, topK, distanceThreshold ?? double.nan, maskBytes,
+          mask != null ? mask._mask : nullptr, aDist, aId, ids, dist, cnt);
+      if (rc != 0) {
+        Logger.warn('tsh_search_after failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      final n = cnt.value;
+      return [
+        for (var i = 0; i < n; i++) NghSearchResult(nodeId: ids[i], distance: dist[i])
+      ];
+    } finally {
+      calloc.free(q);
+      calloc.free(ids);
+      calloc.free(dist);
+      calloc.free(cnt);
+      calloc.free(aDist);
+      calloc.free(aId);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+  }
+
+  /// The asynchronous form of [searchAfter], as [searchAsync] is of [search] (tsh_search_submit_after; the ticket
+  /// is polled and waited for like any other).
+  Future<List<NghSearchResult>?> searchAfterAsync(
+      Float32List query, int topK, double afterDistance, int afterNodeId,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) async {
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchAfterAsync with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (topK <= 0 || size == 0) return const [];
+    final q = calloc<Float>(dimensions);
+    final ticket = calloc<Int32>();
+    Pointer<Uint8> maskBytes = nullptr;
+    int t;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _submitAfter(_handle, q, topK, maskBytes, mask != null ? mask._mask : nullptr,
+          afterDistance, afterNodeId, ticket);
+      if (rc != 0) {
+        Logger.warn('tsh_search_submit_after failed ($rc): ${_errorText()}',
+            label: 'HipVectorBackend');
+        return null;
+      }
+      t = ticket.value;
+    } finally {
+      calloc.free(q);
+      calloc.free(ticket);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+    return _collect(t, topK, distanceThreshold);
+  }
+
+  /// The cursor searches' counters (tsh_search_after_stats), per shard search: all of them, rows their floor passes
+  /// sent to the side list, searches redone with a larger side list, searches answered without a floor pass.
+  Map<String, int>? searchAfterStats() {
+    final o = calloc<Int64>(4);
+    try {
+      if (_searchAfterStats(_handle, o) != 0) return null;
+      return {'searches': o[0], 'sideRows': o[1], 'redone': o[2], 'noFloor': o[3]};
+    } finally {
+      calloc.free(o);
     }
   }
 

@@ -92,6 +92,7 @@ class VectorSearchResult:
     primaryKey: str
     distance: float
     score: float
+    nodeId: Optional[int] = None  # (not in the reference's result: what a cursor names, vectorSearch(after=))
 
 
 class VectorIndexManager:
@@ -141,8 +142,23 @@ class VectorIndexManager:
     # -- query path -----------------------------------------------------------------
     def vectorSearch(self, queryVector: Sequence[float], topK: int = 10, efSearch: Optional[int] = None,
                      distanceThreshold: Optional[float] = None, rowMask=None,
-                     pk_of: Optional[Callable[[int], Optional[str]]] = None) -> list:
-        """ref: core/vector_index_manager.dart:475-589."""
+                     pk_of: Optional[Callable[[int], Optional[str]]] = None, after=None) -> list:
+        """ref: core/vector_index_manager.dart:475-589.
+        after (no reference counterpart): a cursor (distance, nodeId), usually `(r.distance, r.nodeId)` of the last entry
+        of the page before: the answer is the next topK rows past it in the result order (distance, then node id), so
+        successive pages concatenate to the full list.  The node id form keeps working when that row has been deleted
+        since (a cursor need not name a live row).  (distance, primaryKey) is accepted for a row this manager still
+        holds; for a key it no longer knows -- deleted since the last page -- it raises ValueError: pass the node id.
+        End of the list: rows whose primary key `pk_of` does not know are dropped AFTER the cut to topK
+        (:579), as in the reference, so a page can come back shorter than topK -- even empty -- without being the last
+        one.  "A short page is the last" holds where no row can be dropped (the default lookup, which knows every live
+        row); a caller whose `pk_of` may drop rows pages with `self.backend.search(..., after=)`, whose pages are
+        short only at the end, and maps the keys itself."""
+        if after is not None and not isinstance(after[1], (int, np.integer)):
+            node = self._node_of_pk.get(str(after[1]))
+            if node is None:
+                raise ValueError(f"after: primary key {after[1]!r} is not (or no longer) in this index; pass (distance, nodeId)")
+            after = (after[0], node)
         if self.index.size == 0:  # :504 `meta.totalVectors == 0` -> const []
             return []
         query_f32 = to_float32(queryVector, self.dimensions)  # :514
@@ -150,7 +166,7 @@ class VectorIndexManager:
         if self.metric == METRIC_COSINE:  # :516-520
             search_query = normalize_float32(query_f32)
         results = self.backend.search(query=search_query, topK=topK, efSearch=efSearch,
-                                      distanceThreshold=distanceThreshold, rowMask=rowMask)  # :538
+                                      distanceThreshold=distanceThreshold, rowMask=rowMask, after=after)  # :538
         if not results:  # :553
             return []
         sorted_by_node = sorted(results, key=lambda r: r.nodeId)  # :555-556
@@ -161,7 +177,7 @@ class VectorIndexManager:
             if pk is None:  # :579
                 continue
             entries.append(VectorSearchResult(primaryKey=pk, distance=r.distance,
-                                              score=distance_to_score(r.distance, self.metric)))
+                                              score=distance_to_score(r.distance, self.metric), nodeId=r.nodeId))
         # :587 re-sort by distance; Dart's sort is not stable, ours keeps node order on ties
         import functools
         entries.sort(key=functools.cmp_to_key(lambda a, b: _dart_compare(a.distance, b.distance)))
