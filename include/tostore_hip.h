@@ -48,7 +48,8 @@ extern "C" {
  *    exchanges instead of a constant.
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
  *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS;
- *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats. */
+ *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats;
+ *    tsh_search_shard_after, tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after. */
 
 /* status codes */
 #define TSH_OK 0
@@ -375,8 +376,10 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double distance_threshol
  * because the side list overflowed (more than 1024 rows tied with the cursor), out[3] = searches answered without a
  * floor on the device (safe mode, where the finaliser filters; a +inf or NaN cursor, which only quarantined rows can
  * follow: no scan runs).
- * Not covered: the sharded entries (tsh_search_shard*, tsh_search_sharded) -- a sharded caller pages per shard and
- * merges. */
+ * Sharded callers page with the *_after forms of the sharded entries below (tsh_search_shard_after,
+ * tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after): the cursor is GLOBAL, and the
+ * order is total across shards, so the rows after it are the union of every shard's rows after it.  These calls count
+ * in tsh_search_after_stats of the shard handle like any other cursor search. */
 int32_t tsh_search_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double distance_threshold,
                          const uint8_t *row_mask, tsh_mask *mask, const double *after_dist, const int64_t *after_id,
                          int64_t *out_ids, double *out_dist, int32_t *out_count);
@@ -443,6 +446,27 @@ int32_t tsh_merge_candidates(int32_t metric, int32_t dim, const float *queries,
                              const void *blocks, int32_t n_blocks, int32_t entries,
                              int64_t *out_ids, double *out_dist, int32_t *out_count,
                              int32_t *needed_entries);
+/* The sharded entries behind a cursor (tsh_search_after's semantics; additive since ABI 5).  after_dist / after_id: nq
+ * each, the same GLOBAL cursor on every rank, like the queries; -inf is "from the start" and the merged answer equals
+ * the cursor-less entries' bit for bit; a NULL cursor array is TSH_E_BAD_ARG.  Every shard emits a block of the rows
+ * that can be among ITS first k past the cursor: the floor pass runs on the device as for tsh_search_after, and the few
+ * rows whose f32 key cannot tell are appended to the query's device block with their exact sums (a block they do not
+ * fit in reports count > entries: the usual overflow protocol).  tsh_merge_candidates_after drops what is at or before
+ * the exact (distance, id), orders and cuts: pages concatenate to exactly the list the cursor-less merge would return
+ * with k = infinity.  Blocks keep their layout; _progress and _end of the progressive form are the ones above.  A
+ * cursor call is never batched, whatever step or TSH_OPT_BATCH_MIN_NQ say: every query is its own f32 tile scan or
+ * list scan.  Safe mode runs no floor pass: its blocks are tsh_search_shard's and the merge filters.  A +inf or NaN
+ * cursor launches no scan: only rows kept out of the scan can follow it. */
+int32_t tsh_search_shard_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
+                               const double *after_dist, const int64_t *after_id, int32_t entries,
+                               void *d_out_blocks, void *stream);
+int32_t tsh_search_shard_begin_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
+                                     const double *after_dist, const int64_t *after_id, int32_t entries,
+                                     void *d_out_blocks, int32_t step, tsh_shard_stream **out);
+int32_t tsh_merge_candidates_after(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k,
+                                   double distance_threshold, const double *after_dist, const int64_t *after_id,
+                                   const void *blocks, int32_t n_blocks, int32_t entries, int64_t *out_ids,
+                                   double *out_dist, int32_t *out_count, int32_t *needed_entries);
 
 /* ---- the same exchange from a host without torch (a Dart process per GPU) ------------------------------------
  * RCCL all-gather of the per-shard candidate blocks over xGMI + host merge, behind plain C.  librccl is loaded
@@ -490,6 +514,15 @@ int32_t tsh_comm_set_group(tsh_comm *comm, int32_t queries_per_exchange);
 int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *comm, const float *queries, int32_t nq, int32_t k,
                            double distance_threshold, const uint8_t *row_mask, int64_t *out_ids, double *out_dist,
                            int32_t *out_count);
+/* tsh_search_sharded behind a GLOBAL cursor per query (same arrays on every rank): identical answer on every rank -- the
+ * one tsh_search_after gives on one un-sharded index over the same rows.  Groups follow the scan schedule above (the
+ * shrinking groups), never the one-group batched schedule, on every rank alike and whatever any rank's
+ * TSH_OPT_BATCH_MIN_NQ says.  A cursor call exchanges a group when its blocks are FINAL, whatever
+ * TSH_OPT_EXCHANGE_AHEAD says: a search whose side list overflowed is redone by the host, so a block whose kernels are
+ * enqueued is not yet the block that will be read.  Failure protocol and timeline: tsh_search_sharded's. */
+int32_t tsh_search_sharded_after(tsh_index *shard, tsh_comm *comm, const float *queries, int32_t nq, int32_t k,
+                                 double distance_threshold, const uint8_t *row_mask, const double *after_dist,
+                                 const int64_t *after_id, int64_t *out_ids, double *out_dist, int32_t *out_count);
 
 /* Where the time of this rank's tsh_search_sharded calls went: sums over the calls since the communicator was made
  * (or since the last reset).  On the calling thread a call is, group after group,
@@ -607,7 +640,9 @@ int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
  * (their header's pad[1]) so that a block of an earlier call is never taken for an answer, and a block the host is
  * still going to redo (ties) asks for a retry like a truncated one.  Measured on one MI355X with 125 k x 768 shards it
  * LOSES 3-6 % (the early packets on the communicator's queue run late), hence off by default;
- * kept for hosts whose collectives are costlier to launch.  Same value on every rank. */
+ * kept for hosts whose collectives are costlier to launch.  Same value on every rank.  tsh_search_sharded_after does not
+ * look at it: a cursor search whose side list overflowed is redone by the host, so "enqueued" is not "final" there, and
+ * its groups are exchanged when their blocks are final. */
 #define TSH_OPT_EXCHANGE_AHEAD 3
 /* TSH_OPT_EXACT_SCAN_ROWS (default and maximum 16384; 0 = never): a single-query search that has at most this many
  * rows to look at -- the kept rows of a selective row mask, or all rows of a small index or shard -- computes the exact

@@ -17,12 +17,19 @@
 //                           strictly in element order), into pinned host memory with their count; the finaliser
 //                           decides them by (distance, id).  (A lane per row, the quarantine kernel's shape, was
 //                           measured first: its one dependent load chain per row cost a lone 1 M x 768 page 45 us more.)
-// The side count alternates between two words: A2 leaves the one the context's NEXT cursor job counts in at zero, so no
-// launch is spent on clearing it.
+//   A2' after_side_append_kernel   shard mode (tsh_search_shard_after, tsh_search_sharded_after): the job's block lives
+//                           in device memory and is all-gathered device to device, so the AMBIGUOUS rows' entries are
+//                           APPENDED to it -- the same sums by the same code, a wave per row; the position comes from an
+//                           atomic add on BlockHeader.count, as quarantine_append_kernel has it: a position at or
+//                           beyond `entries` is counted, not written, which is the blocks' own overflow protocol.  The
+//                           merge (tsh_merge_candidates_after) decides every entry by (distance, id).
+// The side count alternates between two words: A2 / A2' leave the one the context's NEXT cursor job counts in at zero,
+// so no launch is spent on clearing it; both report the list's total to the pinned word the host reads (a list that
+// overflowed is redone with room for that many).
 //
 // Out of scope here: cursors on the fp16 / int8 routes and on the exact path (a cursor job always takes the f32 tile
 // scan or the list scan); the batched matrix-core path (several queries per call run as the usual pipeline of
-// single-query scans); tsh_search_shard* / tsh_search_sharded (a sharded caller pages per shard and merges).
+// single-query scans, in shard mode too).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -94,6 +101,50 @@ static __global__ void __launch_bounds__(64) after_side_kernel(AfterSideArgs a) 
   }
   const RerankArgs r{a.rows, a.query, a.side_rows, a.side_count, a.out + 1, a.ld, a.row_base, a.dim, (int32_t)a.side_cap, a.metric};
   rerank_rows(r, total < a.side_cap ? total : a.side_cap, t0, t1);
+}
+
+struct AfterSideAppendArgs {
+  const float *rows;
+  const float *query;          // the context's device copy, ld floats
+  const uint32_t *side_rows;
+  const uint32_t *side_count;  // this job's word ...
+  uint32_t *next_count;        // ... and the other one, left at zero for the context's next cursor job
+  int64_t *total_out;          // pinned host memory: the count (capacity or not), for the host's redo
+  uint8_t *block;              // the job's device block: header, then `entries` entries
+  int64_t ld, row_base;
+  int32_t dim, metric;
+  uint32_t side_cap;
+  int32_t entries;
+};
+
+// A2': a wave per row, the re-rank's own sums (rerank_row_sums); lane 0 draws the entry's place in the block
+static __global__ void __launch_bounds__(64) after_side_append_kernel(AfterSideAppendArgs a) {
+  __shared__ __attribute__((aligned(16))) double t0[RR_CHUNK];
+  __shared__ __attribute__((aligned(16))) double t1[RR_CHUNK];
+  const uint32_t total = *a.side_count;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *a.total_out = (int64_t)total;
+    *a.next_count = 0u;
+  }
+  BlockHeader *hdr = reinterpret_cast<BlockHeader *>(a.block);
+  BlockEntry *out = reinterpret_cast<BlockEntry *>(a.block + sizeof(BlockHeader));
+  const RerankArgs r{a.rows, a.query, a.side_rows, a.side_count, out, a.ld, a.row_base, a.dim, a.entries, a.metric};
+  const uint32_t count = total < a.side_cap ? total : a.side_cap;
+  const int lane = threadIdx.x;
+  const int chains = a.metric == METRIC_COS ? 2 : 1;  // lane 0: s0, lane 1: row norm
+  for (uint32_t c = blockIdx.x; c < count; c += gridDim.x) {  // (wave-uniform: the sums synchronise the workgroup)
+    const uint32_t row = a.side_rows[c];
+    const double s = rerank_row_sums(r, a.rows + (int64_t)row * a.ld, lane, chains, t0, t1);
+    const double s1 = __shfl(s, 1);
+    if (lane == 0) {
+      const uint32_t pos = atomicAdd(&hdr->count, 1u);
+      if (pos < (uint32_t)a.entries) {
+        out[pos].id = a.row_base + (int64_t)row;
+        out[pos].s0 = s;
+        out[pos].s1 = a.metric == METRIC_COS ? s1 : 0.0;
+      }
+    }
+  }
 }
 
 }  // namespace tsh

@@ -366,10 +366,12 @@ int comm_exchange_enqueue(tsh_comm *c, const uint8_t *d_blocks, int32_t gq, int3
 // enqueued: comm_exchange_enqueue has run for this group already (stream-ordered behind the group's block writers);
 // then a rank whose scans failed cannot mark its blocks any more -- its peers see that from the blocks' generation
 // (tag: what BlockHeader.pad[1] of every block of this group must say; 0 = blocks of a synchronous shard search).
+// after_dist / after_id: the cursors of the group's queries (tsh_search_sharded_after), or both NULL.
 // Collective; returns the same verdict class on every rank (own error / TSH_E_PEER / TSH_OK + need).
 int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int local_rc, const float *queries, int32_t gq,
                         int32_t k, double thr, int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count,
-                        GroupOut *go, bool enqueued = false, uint32_t tag = 0) {
+                        GroupOut *go, bool enqueued = false, uint32_t tag = 0, const double *after_dist = nullptr,
+                        const int64_t *after_id = nullptr) {
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries), W = (size_t)c->world, mine = bb * (size_t)gq;
   const bool whole = merge_whole(W, (size_t)gq);  // (same on every rank: W and gq are)
   const int32_t slice_q = whole ? gq : (int32_t)(((size_t)gq + W - 1) / W);
@@ -469,7 +471,12 @@ int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int lo
         int64_t *ids = reinterpret_cast<int64_t *>(r);
         double *dd = reinterpret_cast<double *>(r + (size_t)k * 8);
         int32_t *cnt = reinterpret_cast<int32_t *>(r + (size_t)k * 16);
-        cnt[0] = finalize_query(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, ids, dd);
+        Cursor cur;  // (this rank's slice and the whole group alike: the cursor of query a + i)
+        if (after_dist) {
+          cur.dist = after_dist[a + i];
+          cur.id = after_id[a + i];
+        }
+        cnt[0] = finalize_query(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, ids, dd, nullptr, after_dist ? &cur : nullptr);
         cnt[1] = 0;
       });
     }
@@ -571,6 +578,10 @@ int comm_check_create(const void *id_or_fn, int32_t world, int32_t rank, int32_t
   return TSH_OK;
 }
 
+int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
+                        const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                        double *out_dist, int32_t *out_count);
+
 }  // namespace
 
 extern "C" {
@@ -664,6 +675,27 @@ int32_t tsh_comm_get_timeline(tsh_comm *c, tsh_comm_timeline *out, int32_t reset
 
 int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
                            const uint8_t *row_mask, int64_t *out_ids, double *out_dist, int32_t *out_count) {
+  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, nullptr, nullptr, out_ids, out_dist, out_count);
+}
+int32_t tsh_search_sharded_after(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
+                                 const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                                 double *out_dist, int32_t *out_count) {
+  if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
+  if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, after_dist, after_id, out_ids, out_dist, out_count);
+}
+
+}  // extern "C"
+
+namespace {
+
+// tsh_search_sharded; after_dist / after_id: a global cursor per query (tsh_search_sharded_after: the same on every rank,
+// like the queries), or both NULL.  A cursor call differs in three places: its groups follow the scan schedule (every
+// query is its own scan on every rank, whatever a rank's batch threshold says), its exchanges go out when the blocks are
+// final (a side-list redo rewrites a block after its kernels were enqueued), and every merge passes its queries' cursors.
+int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
+                        const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                        double *out_dist, int32_t *out_count) {
   // arguments that are the same on every rank by contract are answered locally ...
   if (!c) return set_err(TSH_E_BAD_ARG, "comm is NULL");
   if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
@@ -721,7 +753,8 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
   if (c->group > 0) {
     for (int32_t q = 0; q < nq; q += Gmax) sizes.push_back(std::min(Gmax, nq - q));
   } else {
-    sharded_schedule(nq, (double)c->scan_bytes_hint / 6.5e6, &sizes, c->batch_hint);
+    // (a cursor call: the scan schedule -- the argument is the same on every rank, which no rank's own batch flag is)
+    sharded_schedule(nq, (double)c->scan_bytes_hint / 6.5e6, &sizes, after_dist ? false : c->batch_hint);
   }
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
   size_t gi = 0;  // next group
@@ -741,9 +774,11 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
     if (scan_rc == TSH_OK) {
       // (launched ahead, a group's all-gather may read a block while its rank's host still looks at it: such a
       // block is never rewritten in place -- Job::leave_overflow)
-      const bool ahead = c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
+      // (never a cursor call: "enqueued" is not "final" where a side list may be redone)
+      const bool ahead = !after_dist && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
       scan_rc = shard_stream_begin(shard, queries + (size_t)w0 * dim, wn, k, row_mask, entries, c->d_mine, sizes[gi],
-                                   /*copy_inputs=*/false, &ss, ss_tag, c->worker.get(), ahead);
+                                   /*copy_inputs=*/false, &ss, ss_tag, c->worker.get(), ahead, after_dist ? after_dist + w0 : nullptr,
+                                   after_dist ? after_id + w0 : nullptr);
       if (scan_rc) scan_err = g_err;
     }
     auto end_stream = [&] {  // nothing of this call may still run when it returns
@@ -759,7 +794,7 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
       // behind their block writers (comm_exchange_enqueue): the collective's launch costs the host tens of
       // microseconds, which would otherwise follow the last block
       bool enqueued = false;
-      if (ss && scan_rc == TSH_OK && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire)) {
+      if (ss && scan_rc == TSH_OK && !after_dist && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire)) {
         const double t_e = now_us();
         hipEvent_t after[MAX_CTX];
         const int n_after = shard_stream_enqueued(ss, q0 + gq, after, MAX_CTX);
@@ -788,7 +823,7 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
       GroupOut go;
       rc = comm_exchange_group(c, shard, c->d_mine + (size_t)q0 * bb, scan_rc, queries + (size_t)qa * dim, gq, k, thr,
                                entries, out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, enqueued,
-                               ss_tag);
+                               ss_tag, after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
       tl.groups++;
       for (int attempt = 0; rc == TSH_OK && go.need > 0; ++attempt) {
         // ties made a block overflow: every rank saw the same verdict and redoes this group with larger blocks, in a
@@ -809,7 +844,8 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
         std::string again_err = local_rc != TSH_OK ? local_err : scan_err;
         if (again_rc == TSH_OK) {
           const double t0 = now_us();
-          again_rc = tsh_search_shard(shard, queries + (size_t)qa * dim, gq, k, row_mask, ent, c->d_retry, nullptr);
+          again_rc = search_shard_impl(shard, queries + (size_t)qa * dim, gq, k, row_mask, ent, c->d_retry, nullptr,
+                                       after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
           c->scan_ns.fetch_add((int64_t)((now_us() - t0) * 1e3), std::memory_order_relaxed);
           if (again_rc) again_err = g_err;
         }
@@ -817,7 +853,8 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
         if (again_rc) g_err = again_err;
         go = GroupOut();
         rc = comm_exchange_group(c, shard, c->d_retry, again_rc, queries + (size_t)qa * dim, gq, k, thr, ent,
-                                 out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go);
+                                 out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, false, 0,
+                                 after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
         tl.groups++;
       }
       if (rc) {
@@ -836,4 +873,4 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, 
   return TSH_OK;
 }
 
-}  // extern "C"
+}  // namespace

@@ -1143,6 +1143,44 @@ struct RerankArgs {
 };
 constexpr int RR_CHUNK = 1024;
 
+// One candidate's exact sums, by a whole wave (t0 / t1: RR_CHUNK doubles of LDS each): -> s0 in lane 0, the cosine row norm
+// in lane 1.  The arithmetic of rerank_kernel and of the side re-ranks of a cursor search (tsh_after.hip.h)
+__device__ __forceinline__ double rerank_row_sums(const RerankArgs &a, const float *rp, const int lane, const int chains, double *t0,
+                                                  double *t1) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  for (int base = 0; base < a.dim; base += RR_CHUNK) {
+    int m = a.dim - base < RR_CHUNK ? a.dim - base : RR_CHUNK;
+    for (int i = lane; i < m; i += 64) {
+      double qv = (double)a.query[base + i], bv = (double)rp[base + i];
+      if (a.metric == METRIC_L2) {
+        double diff = qv - bv;
+        t0[i] = diff * diff;
+      } else {
+        t0[i] = qv * bv;
+        if (a.metric == METRIC_COS) t1[i] = bv * bv;
+      }
+    }
+    __syncthreads();
+    if (lane < chains) {
+      // strictly sequential adds; LDS reads are issued 32 elements ahead so
+      // only the add chain's own latency remains
+      const double *src = lane == 0 ? t0 : t1;
+      int i = 0;
+      for (; i + 32 <= m; i += 32) {
+        double x[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) x[u] = src[i + u];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) s = s + x[u];
+      }
+      for (; i < m; ++i) s = s + src[i];
+    }
+    __syncthreads();
+  }
+  return s;
+}
+
 // a workgroup's share of K4: candidates blockIdx.x, + gridDim.x, ... below count (t0 / t1: RR_CHUNK doubles of LDS each).
 // rerank_kernel's body, shared with the side re-rank of a cursor search (after_side_kernel, tsh_after.hip.h)
 __device__ __forceinline__ void rerank_rows(const RerankArgs &a, const uint32_t count, double *t0, double *t1) {
@@ -1152,36 +1190,7 @@ __device__ __forceinline__ void rerank_rows(const RerankArgs &a, const uint32_t 
   for (uint32_t c = blockIdx.x; c < count; c += gridDim.x) {
     uint32_t row = a.cand_rows[c];
     const float *rp = a.rows + (int64_t)row * a.ld;
-    double s = 0.0;
-    for (int base = 0; base < a.dim; base += RR_CHUNK) {
-      int m = a.dim - base < RR_CHUNK ? a.dim - base : RR_CHUNK;
-      for (int i = lane; i < m; i += 64) {
-        double qv = (double)a.query[base + i], bv = (double)rp[base + i];
-        if (a.metric == METRIC_L2) {
-          double diff = qv - bv;
-          t0[i] = diff * diff;
-        } else {
-          t0[i] = qv * bv;
-          if (a.metric == METRIC_COS) t1[i] = bv * bv;
-        }
-      }
-      __syncthreads();
-      if (lane < chains) {
-        // strictly sequential adds; LDS reads are issued 32 elements ahead so
-        // only the add chain's own latency remains
-        const double *src = lane == 0 ? t0 : t1;
-        int i = 0;
-        for (; i + 32 <= m; i += 32) {
-          double x[32];
-#pragma unroll
-          for (int u = 0; u < 32; ++u) x[u] = src[i + u];
-#pragma unroll
-          for (int u = 0; u < 32; ++u) s = s + x[u];
-        }
-        for (; i < m; ++i) s = s + src[i];
-      }
-      __syncthreads();
-    }
+    double s = rerank_row_sums(a, rp, lane, chains, t0, t1);
     double s1 = __shfl(s, 1);
     if (lane == 0) {
       a.out[c].id = a.row_base + (int64_t)row;

@@ -1763,6 +1763,17 @@ int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipSt
   return TSH_OK;
 }
 
+// shard mode, a cursor job: the rows its floor pass could not decide go into the job's device block as well (A2',
+// tsh_after.hip.h); `done`: an event to ride on the kernel's packet, or NULL
+void launch_after_side_append(Shard *s, Ctx *c, Job *j, hipStream_t st, hipEvent_t done) {
+  const uint32_t side_cap = (uint32_t)c->side_cap;
+  const AfterSideAppendArgs sd{s->d_rows, c->d_query, c->d_side_rows, c->d_side_cnt + j->side_word, c->d_side_cnt + (j->side_word ^ 1),
+                               &c->h_side_dev[0].id, j->dev_target, s->ld, s->row_base, s->dim, s->metric, side_cap, j->entries};
+  const hipEvent_t none = nullptr;
+  // (the grid of after_side_kernel: a page has a row or two to decide)
+  TSH_LAUNCH_EV(after_side_append_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, st, none, done, sd);
+}
+
 // What follows the scan, on ts: the exact path's pick or select, or select + re-rank; then the quarantined rows the
 // mask keeps, if any.  The completion event rides on the last kernel's own dispatch packet unless more kernels follow
 // (a separate hipEventRecord is one more runtime call and one more barrier packet per query)
@@ -1802,7 +1813,9 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     }
     launch_select(ka.se, ka.se.n_tiles, ts);
     TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, j->floored ? none : done, ka.ra);
-    if (j->floored) {
+    if (j->floored && j->dev_target) {
+      launch_after_side_append(s, c, j, ts, done);  // (in front of the quarantined rows' append: both draw places in the block)
+    } else if (j->floored) {
       const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
                              s->dim, s->metric, side_cap};
       // (a page has a row or two to decide: 64 workgroups stride over a full list of AFTER_SIDE_CAP ids; only a redo's
@@ -1818,8 +1831,8 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
 }
 
 // A cursor job whose cursor no scanned row can follow (a +inf or NaN distance): an empty block, and the quarantined rows
-// the mask keeps.  q: the staged query (job_stage)
-int enqueue_after_skip(Shard *s, Job *j, const float *q) {
+// the mask keeps -- in shard mode both in the caller's device block.  q: the staged query (job_stage)
+int enqueue_after_skip(Shard *s, Job *j, const JobReq &rq, const float *q) {
   Ctx *c = j->c;
   BlockHeader *h = reinterpret_cast<BlockHeader *>(c->h_block);
   memset(h, 0, sizeof *h);
@@ -1828,14 +1841,28 @@ int enqueue_after_skip(Shard *s, Job *j, const float *q) {
   h->metric = (uint32_t)s->metric;
   h->row_base = s->row_base;
   h->shard_rows = s->rows;
+  h->pad[1] = rq.tag;
   j->store = RowStore::F32;
   j->timed = j->counted = false;
   hipStream_t st = s->aux_stream;
+  // (the pinned header is this job's until it is finished: the copy reads it in place)
+  if (j->dev_target) HIPCHK(hipMemcpyAsync(j->dev_target, h, sizeof *h, hipMemcpyHostToDevice, st));
   if (!j->quar_sel.empty()) {
     if (q != c->h_query) memcpy(c->h_query, q, (size_t)s->ld * sizeof(float));
     HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, st));
-    launch_quarantine(s, c, st);
+    if (j->dev_target) {
+      if (j->up_mask) {  // (no scan uploads the mask words the append matches the quarantined rows against)
+        HIPCHK(hipMemcpyAsync(c->d_mask, c->h_mask, (size_t)((s->rows + 63) / 64) * 8, hipMemcpyHostToDevice, st));
+        j->up_mask = false;
+      }
+      launch_quarantine_append(s, c, j, st);
+    } else {
+      launch_quarantine(s, c, st);
+    }
   }
+  // (what job_stage staged for a scan that does not run never reaches the device: the context's copies are not current)
+  if (j->up_mask) c->mask_epoch = 0;
+  if (j->up_list) c->list_epoch = 0;
   HIPCHK(hipEventRecord(c->ev_done, st));
   j->last_stream = st;
   return TSH_OK;
@@ -1867,7 +1894,7 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   float *q;
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
-  if (j->after_skip) return enqueue_after_skip(s, j, q);
+  if (j->after_skip) return enqueue_after_skip(s, j, rq, q);
   if (j->floored) {
     if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(rq.side_want, AFTER_SIDE_CAP), c->side_cap)))) return rc;
     if (c->side_dirty) {  // (a context's first cursor job, or one after a job that failed on its way)
@@ -2112,6 +2139,7 @@ int redo_after_side(Shard *s, Job *j) {
   JobReq rq(j->redo_query, j->k, j->entries);
   rq.mask = j->redo_mask;
   rq.mask_dies = !j->redo_words.empty() && j->redo_mask.words == j->redo_words.data();
+  rq.dev_target = j->dev_target;  // (Job::leave_overflow stays with the job)
   rq.last_of_call = true;
   rq.tag = j->tag;
   rq.after = &cur;
@@ -2182,9 +2210,11 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   } else if (h->flags & FLAG_LIST_OVERFLOW) {
     int rc = run_fallback(s, j, h->band_key, spill);  // keys[] of this query are still in the context
     if (rc) return rc;
-    if (!j->quar_sel.empty() && j->dev_target) {  // the fallback rewrote the device block: append again
-      launch_quarantine_append(s, c, j, s->aux_stream);
+    if (j->dev_target && (j->floored || !j->quar_sel.empty())) {  // the fallback rewrote the device block: append again
+      if (j->floored) launch_after_side_append(s, c, j, s->aux_stream, nullptr);
+      if (!j->quar_sel.empty()) launch_quarantine_append(s, c, j, s->aux_stream);
       HIPCHK(hipStreamSynchronize(s->aux_stream));
+      HIPCHK(hipGetLastError());
     }
   } else {
     s->c_cands += h->count;
@@ -2198,7 +2228,9 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     s->c_after++;
     if (j->after_skip || (j->route.band.force_all && !j->after.from_start())) s->c_after_nofloor++;
   }
-  if (j->floored) {  // the rows the floor pass could not decide join the candidates too
+  if (j->floored && j->dev_target) {  // (shard mode: the side rows' entries are in the device block already)
+    s->c_after_side += c->h_side[0].id;
+  } else if (j->floored) {  // the rows the floor pass could not decide join the candidates too
     if (!extra) return set_err(TSH_E_BAD_ARG, "no room for the side list's entries");
     if (j->quar_sel.empty()) extra->clear();
     const uint32_t side_n = (uint32_t)c->h_side[0].id;
@@ -2237,7 +2269,7 @@ struct SearchOut {
   std::function<void(int32_t q, hipEvent_t done, hipStream_t where, uint64_t seq)> on_enqueued;
   uint32_t tag = 0;  // generation stamped into the blocks' headers (BlockHeader.pad[1])
   bool leave_overflow = false;  // device mode: see Job::leave_overflow
-  // single-query pipeline, host mode: a cursor per query (tsh_search_after), or NULL
+  // single-query pipeline, host or device mode: a cursor per query (tsh_search_after, tsh_search_shard_after), or NULL
   const double *after_dist = nullptr;
   const int64_t *after_id = nullptr;
 };
@@ -3203,8 +3235,10 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double thr, int64_t *out
   return rc;
 }
 
-int32_t tsh_search_shard(tsh_index *idx, const float *queries, int32_t nq, int32_t k,
-                         const uint8_t *row_mask, int32_t entries, void *d_out_blocks, void *stream) {
+namespace {
+// tsh_search_shard; after_dist / after_id: a cursor per query (tsh_search_shard_after), or both NULL
+int32_t search_shard_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask, int32_t entries,
+                          void *d_out_blocks, void *stream, const double *after_dist, const int64_t *after_id) {
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
   if (nq <= 0 || !queries || !d_out_blocks || k <= 0 || entries < 1)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / pointers");
@@ -3227,7 +3261,24 @@ int32_t tsh_search_shard(tsh_index *idx, const float *queries, int32_t nq, int32
   SearchOut so;
   so.d_blocks = static_cast<uint8_t *>(d_out_blocks);
   so.user_stream = static_cast<hipStream_t>(stream);
+  if (after_dist) {  // a cursor call is never batched: every query is its own scan
+    so.after_dist = after_dist;
+    so.after_id = after_id;
+    return shard_search_blocks(s, queries, nq, k, row_mask, entries, &so, PIPE_DEPTH);
+  }
   return shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, row_mask, entries, &so);
+}
+}  // namespace
+
+int32_t tsh_search_shard(tsh_index *idx, const float *queries, int32_t nq, int32_t k,
+                         const uint8_t *row_mask, int32_t entries, void *d_out_blocks, void *stream) {
+  return search_shard_impl(idx, queries, nq, k, row_mask, entries, d_out_blocks, stream, nullptr, nullptr);
+}
+int32_t tsh_search_shard_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
+                               const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks, void *stream) {
+  if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return search_shard_impl(idx, queries, nq, k, row_mask, entries, d_out_blocks, stream, after_dist, after_id);
 }
 
 // ---- progressive shard search ---------------------------------------------------------------------------------
@@ -3240,8 +3291,12 @@ struct tsh_shard_stream {
   tsh_index *idx = nullptr;
   const float *queries = nullptr;
   const uint8_t *mask = nullptr;
+  const double *after_dist = nullptr;  // a cursor per query (tsh_search_shard_begin_after), or both NULL
+  const int64_t *after_id = nullptr;
   std::vector<float> own_queries;  // public entry points: the caller's arrays are consumed before begin returns
   std::vector<uint8_t> own_mask;
+  std::vector<double> own_after_dist;
+  std::vector<int64_t> own_after_id;
   int32_t nq = 0, k = 0, entries = 0, step = 0;
   uint8_t *d_blocks = nullptr;
   std::mutex mu;
@@ -3337,7 +3392,8 @@ struct tsh_shard_stream {
     }
     const int32_t min_nq = idx->batch_min_nq.load();
     const int32_t st = step > 0 ? std::min(step, nq) : nq;
-    if (!shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
+    // (a cursor call is never batched, whatever step or the handle's batch threshold say)
+    if (after_dist || !shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
       done_q.assign((size_t)nq, 0);
       enq_q.assign((size_t)nq, 0);
       ev_q.assign((size_t)nq, nullptr);
@@ -3347,6 +3403,8 @@ struct tsh_shard_stream {
       so.d_blocks = d_blocks;
       so.tag = tag;
       so.leave_overflow = leave_overflow;
+      so.after_dist = after_dist;
+      so.after_id = after_id;
       so.on_done = [this](int32_t q) { mark(q); };
       so.on_enqueued = [this](int32_t q, hipEvent_t ev, hipStream_t where, uint64_t seq) { mark_enqueued(q, ev, where, seq); };
       route.store(1, std::memory_order_release);
@@ -3392,7 +3450,8 @@ struct tsh_shard_stream {
 namespace {
 int shard_stream_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
                        int32_t entries, void *d_out_blocks, int32_t step, bool copy_inputs, tsh_shard_stream **out,
-                       uint32_t tag = 0, OneWorker *exec = nullptr, bool leave_overflow = false) {
+                       uint32_t tag = 0, OneWorker *exec = nullptr, bool leave_overflow = false,
+                       const double *after_dist = nullptr, const int64_t *after_id = nullptr) {
   if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
   *out = nullptr;
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
@@ -3409,10 +3468,18 @@ int shard_stream_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t
   st->d_blocks = static_cast<uint8_t *>(d_out_blocks);
   st->queries = queries;
   st->mask = row_mask;
+  st->after_dist = after_dist;
+  st->after_id = after_id;
   if (copy_inputs) {
     Shard *s = idx->shards[0].get();
     st->own_queries.assign(queries, queries + (size_t)nq * (size_t)s->dim);
     st->queries = st->own_queries.data();
+    if (after_dist) {
+      st->own_after_dist.assign(after_dist, after_dist + nq);
+      st->own_after_id.assign(after_id, after_id + nq);
+      st->after_dist = st->own_after_dist.data();
+      st->after_id = st->own_after_id.data();
+    }
     if (row_mask) {
       int64_t bits;
       {
@@ -3515,6 +3582,15 @@ int32_t tsh_search_shard_begin(tsh_index *idx, const float *queries, int32_t nq,
                                int32_t entries, void *d_out_blocks, int32_t step, tsh_shard_stream **out) {
   return shard_stream_begin(idx, queries, nq, k, row_mask, entries, d_out_blocks, step, /*copy_inputs=*/true, out);
 }
+int32_t tsh_search_shard_begin_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
+                                     const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks,
+                                     int32_t step, tsh_shard_stream **out) {
+  if (out) *out = nullptr;
+  if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return shard_stream_begin(idx, queries, nq, k, row_mask, entries, d_out_blocks, step, /*copy_inputs=*/true, out, 0, nullptr, false,
+                            after_dist, after_id);
+}
 int32_t tsh_search_shard_progress(tsh_shard_stream *st, int32_t want, int32_t *out_done) {
   if (!st) return set_err(TSH_E_BAD_ARG, "stream is NULL");
   return shard_stream_progress(st, want, out_done);
@@ -3524,10 +3600,11 @@ int32_t tsh_search_shard_end(tsh_shard_stream *st) {
   return shard_stream_end(st);
 }
 
-int32_t tsh_merge_candidates(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k,
-                             double thr, const void *blocks, int32_t n_blocks, int32_t entries,
-                             int64_t *out_ids, double *out_dist, int32_t *out_count,
-                             int32_t *needed_entries) {
+namespace {
+// tsh_merge_candidates; after_dist / after_id: a cursor per query (tsh_merge_candidates_after), or both NULL
+int32_t merge_candidates_impl(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k, double thr,
+                              const double *after_dist, const int64_t *after_id, const void *blocks, int32_t n_blocks,
+                              int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count, int32_t *needed_entries) {
   if (metric < 0 || metric > 2 || dim <= 0 || nq < 0 || n_blocks < 0 || entries < 0)
     return set_err(TSH_E_BAD_ARG, "bad metric / dim / nq / n_blocks / entries");
   if (nq == 0) return TSH_OK;
@@ -3557,10 +3634,32 @@ int32_t tsh_merge_candidates(int32_t metric, int32_t dim, const float *queries, 
       const BlockHeader *h = reinterpret_cast<const BlockHeader *>(p);
       lists.push_back({reinterpret_cast<const BlockEntry *>(p + sizeof(BlockHeader)), h->count});
     }
+    Cursor cur;
+    if (after_dist) {
+      cur.dist = after_dist[q];
+      cur.id = after_id[q];
+    }
     out_count[q] = finalize_query(metric, dim, queries + (size_t)q * dim, k, thr, lists,
-                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k);
+                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k, after_dist ? &cur : nullptr);
   });
   return TSH_OK;
+}
+}  // namespace
+
+int32_t tsh_merge_candidates(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k,
+                             double thr, const void *blocks, int32_t n_blocks, int32_t entries,
+                             int64_t *out_ids, double *out_dist, int32_t *out_count,
+                             int32_t *needed_entries) {
+  return merge_candidates_impl(metric, dim, queries, nq, k, thr, nullptr, nullptr, blocks, n_blocks, entries, out_ids, out_dist,
+                               out_count, needed_entries);
+}
+int32_t tsh_merge_candidates_after(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k, double thr,
+                                   const double *after_dist, const int64_t *after_id, const void *blocks, int32_t n_blocks,
+                                   int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count,
+                                   int32_t *needed_entries) {
+  if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
+  return merge_candidates_impl(metric, dim, queries, nq, k, thr, after_dist, after_id, blocks, n_blocks, entries, out_ids, out_dist,
+                               out_count, needed_entries);
 }
 
 int32_t tsh_get_counters(tsh_index *idx, tsh_counters *out) {

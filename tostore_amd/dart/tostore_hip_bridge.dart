@@ -162,6 +162,22 @@ typedef _SearchShardedC = Int32 Function(Pointer<Void>, Pointer<Void>, Pointer<F
     Double, Pointer<Uint8>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchShardedD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, int, int,
     double, Pointer<Uint8>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SearchShardAfterC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Uint8>,
+    Pointer<Double>, Pointer<Int64>, Int32, Pointer<Void>, Pointer<Void>);
+typedef _SearchShardAfterD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Uint8>,
+    Pointer<Double>, Pointer<Int64>, int, Pointer<Void>, Pointer<Void>);
+typedef _ShardBeginAfterC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Uint8>,
+    Pointer<Double>, Pointer<Int64>, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
+typedef _ShardBeginAfterD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Uint8>,
+    Pointer<Double>, Pointer<Int64>, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
+typedef _MergeAfterC = Int32 Function(Int32, Int32, Pointer<Float>, Int32, Int32, Double, Pointer<Double>,
+    Pointer<Int64>, Pointer<Void>, Int32, Int32, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _MergeAfterD = int Function(int, int, Pointer<Float>, int, int, double, Pointer<Double>,
+    Pointer<Int64>, Pointer<Void>, int, int, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchShardedAfterC = Int32 Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, Int32, Int32,
+    Double, Pointer<Uint8>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SearchShardedAfterD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, int, int,
+    double, Pointer<Uint8>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 
 /// `tsh_counters` (include/tostore_hip.h).  Field order and widths are checked against the header by
 /// tests/test_dart_bridge.py.
@@ -343,6 +359,10 @@ final class HipVectorBackend {
   static late final _CommWorldD _commWorld;
   static late final _CommSetGroupD _commSetGroup;
   static late final _SearchShardedD _searchSharded;
+  static late final _SearchShardAfterD _searchShardAfter;
+  static late final _ShardBeginAfterD _shardBeginAfter;
+  static late final _MergeAfterD _mergeAfter;
+  static late final _SearchShardedAfterD _searchShardedAfter;
   static late final _CommTimelineD _commTimeline;
   static late final _OpenNghShardD _openNghShard;
   static late final _MaskCreateD _maskCreate;
@@ -408,6 +428,13 @@ final class HipVectorBackend {
       _commSetGroup = lib.lookupFunction<_CommSetGroupC, _CommSetGroupD>('tsh_comm_set_group');
       _searchSharded =
           lib.lookupFunction<_SearchShardedC, _SearchShardedD>('tsh_search_sharded');
+      _searchShardAfter =
+          lib.lookupFunction<_SearchShardAfterC, _SearchShardAfterD>('tsh_search_shard_after');
+      _shardBeginAfter =
+          lib.lookupFunction<_ShardBeginAfterC, _ShardBeginAfterD>('tsh_search_shard_begin_after');
+      _mergeAfter = lib.lookupFunction<_MergeAfterC, _MergeAfterD>('tsh_merge_candidates_after');
+      _searchShardedAfter =
+          lib.lookupFunction<_SearchShardedAfterC, _SearchShardedAfterD>('tsh_search_sharded_after');
       _commTimeline =
           lib.lookupFunction<_CommTimelineC, _CommTimelineD>('tsh_comm_get_timeline');
       _openNghShard =
@@ -1032,6 +1059,36 @@ final class HipVectorBackend {
         0;
   }
 
+  /// The same three behind a GLOBAL cursor per query (`afterDist` / `afterId`: nq each, the same on every rank;
+  /// -inf = from the start): every shard's block holds the rows that can be among ITS next topK past the cursor,
+  /// and the merge drops what is at or before the exact (distance, id) -- pages concatenate to the list the
+  /// cursor-less merge would return with topK = infinity (tsh_search_shard_after, tsh_search_shard_begin_after,
+  /// tsh_merge_candidates_after).  [shardStreamProgress] / [shardStreamEnd] serve [shardStreamBeginAfter] too.
+  bool searchShardAfter(Pointer<Float> queries, int nq, int topK, Pointer<Uint8> rowMask,
+          Pointer<Double> afterDist, Pointer<Int64> afterId, int entries, Pointer<Void> deviceBlocks) =>
+      _searchShardAfter(_handle, queries, nq, topK, rowMask, afterDist, afterId, entries, deviceBlocks, nullptr) == 0;
+
+  Pointer<Void> shardStreamBeginAfter(Pointer<Float> queries, int nq, int topK, Pointer<Uint8> rowMask,
+      Pointer<Double> afterDist, Pointer<Int64> afterId, int entries, Pointer<Void> deviceBlocks, int step) {
+    final out = calloc<Pointer<Void>>();
+    try {
+      final rc = _shardBeginAfter(
+          _handle, queries, nq, topK, rowMask, afterDist, afterId, entries, deviceBlocks, step, out);
+      return rc == 0 ? out.value : nullptr;
+    } finally {
+      calloc.free(out);
+    }
+  }
+
+  static bool mergeCandidatesAfter(int metric, int dim, Pointer<Float> queries, int nq, int topK,
+      double? distanceThreshold, Pointer<Double> afterDist, Pointer<Int64> afterId, Pointer<Void> blocks,
+      int nBlocks, int entries, Pointer<Int64> outIds, Pointer<Double> outDist, Pointer<Int32> outCount,
+      Pointer<Int32> neededEntries) {
+    return _mergeAfter(metric, dim, queries, nq, topK, distanceThreshold ?? double.nan, afterDist, afterId,
+            blocks, nBlocks, entries, outIds, outDist, outCount, neededEntries) ==
+        0;
+  }
+
   void dispose() {
     if (_handle != nullptr) {
       _destroy(_handle);
@@ -1108,10 +1165,27 @@ final class HipShardComm {
   /// (its error is logged) or another rank's (TSH_E_PEER = -11): every rank then takes the same
   /// fallback, and the communicator stays usable.
   List<List<NghSearchResult>>? search(List<Float32List> queries, int topK,
+          {double? distanceThreshold, Uint8List? rowMask}) =>
+      _search(queries, topK, distanceThreshold, rowMask, null, null);
+
+  /// [search] behind a GLOBAL cursor per query -- the last (distance, nodeId) the caller saw of each; the same
+  /// lists on every rank; double.negativeInfinity = from the start: the next topK rows past it, identical on every
+  /// rank and equal to what [HipVectorBackend.searchAfter] gives on one un-sharded index over the same rows
+  /// (tsh_search_sharded_after).  A page shorter than topK is the last one.
+  List<List<NghSearchResult>>? searchShardedAfter(List<Float32List> queries, int topK,
+      List<double> afterDistances, List<int> afterNodeIds,
       {double? distanceThreshold, Uint8List? rowMask}) {
+    if (afterDistances.length != queries.length || afterNodeIds.length != queries.length) return null;
+    return _search(queries, topK, distanceThreshold, rowMask, afterDistances, afterNodeIds);
+  }
+
+  List<List<NghSearchResult>>? _search(List<Float32List> queries, int topK, double? distanceThreshold,
+      Uint8List? rowMask, List<double>? afterDistances, List<int>? afterNodeIds) {
     final nq = queries.length, d = shard.dimensions;
     if (nq == 0 || topK <= 0) return [for (var i = 0; i < nq; i++) const []];
     final q = calloc<Float>(nq * d);
+    Pointer<Double> ad = nullptr;
+    Pointer<Int64> ai = nullptr;
     final ids = calloc<Int64>(nq * topK);
     final dist = calloc<Double>(nq * topK);
     final cnt = calloc<Int32>(nq);
@@ -1125,8 +1199,17 @@ final class HipShardComm {
         mask = calloc<Uint8>(rowMask.length);
         mask.asTypedList(rowMask.length).setAll(0, rowMask);
       }
-      final rc = HipVectorBackend._searchSharded(shard._handle, _comm, q, nq, topK,
-          distanceThreshold ?? double.nan, mask, ids, dist, cnt);
+      if (afterDistances != null && afterNodeIds != null) {
+        ad = calloc<Double>(nq);
+        ai = calloc<Int64>(nq);
+        ad.asTypedList(nq).setAll(0, afterDistances);
+        ai.asTypedList(nq).setAll(0, afterNodeIds);
+      }
+      final rc = ad != nullptr
+          ? HipVectorBackend._searchShardedAfter(shard._handle, _comm, q, nq, topK,
+              distanceThreshold ?? double.nan, mask, ad, ai, ids, dist, cnt)
+          : HipVectorBackend._searchSharded(shard._handle, _comm, q, nq, topK,
+              distanceThreshold ?? double.nan, mask, ids, dist, cnt);
       if (rc != 0) {
         Logger.warn('tsh_search_sharded failed ($rc): ${HipVectorBackend._errorText()}',
             label: 'HipShardComm');
@@ -1145,6 +1228,8 @@ final class HipShardComm {
       calloc.free(dist);
       calloc.free(cnt);
       if (mask != nullptr) calloc.free(mask);
+      if (ad != nullptr) calloc.free(ad);
+      if (ai != nullptr) calloc.free(ai);
     }
   }
 

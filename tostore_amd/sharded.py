@@ -21,10 +21,35 @@ import numpy as np
 from . import _ffi
 
 
+def cursor_arrays(after, nq: int):
+    """`after` -- one (distance, id) for every query, or nq of them -- as the (after_dist[nq], after_id[nq]) arrays
+    the *_after entries take (tsh_search_after's cursor: GLOBAL, the same on every rank).  A pair of such arrays
+    passes through."""
+    if isinstance(after, tuple) and len(after) == 2 and all(isinstance(x, np.ndarray) and x.ndim == 1 for x in after):
+        ad = np.ascontiguousarray(after[0], dtype=np.float64)
+        ai = np.ascontiguousarray(after[1], dtype=np.int64)
+        if ad.shape[0] != nq or ai.shape[0] != nq:
+            raise ValueError("after: one distance and one id per query")
+        return ad, ai
+    a = np.asarray(after, dtype=object)
+    if a.ndim == 1:
+        if a.shape[0] != 2:
+            raise ValueError("after must be (distance, id) or one such pair per query")
+        a = np.broadcast_to(a, (nq, 2))
+    if a.shape != (nq, 2):
+        raise ValueError("after must be (distance, id) or one such pair per query")
+    ad = np.ascontiguousarray([float(x) for x in a[:, 0]], dtype=np.float64)
+    ai = np.ascontiguousarray([int(x) for x in a[:, 1]], dtype=np.int64)
+    return ad, ai
+
+
 def merge_candidate_blocks(metric: int, dim: int, queries: np.ndarray, k: int,
                            distance_threshold: Optional[float], blocks: np.ndarray, n_blocks: int,
-                           entries: int):
+                           entries: int, after=None):
     """Host merge of `n_blocks` x nq candidate blocks (uint8 array, layout [block][query]).
+
+    `after`: a cursor -- one (distance, id), or one per query -- behind which the answer starts
+    (tsh_merge_candidates_after); None = from the start (tsh_merge_candidates).
 
     Returns (ids[nq,k], dist[nq,k], count[nq]); raises _ffi.TshError(TSH_E_OVERFLOW) with
     `.needed_entries` set when a block was truncated."""
@@ -42,10 +67,18 @@ def merge_candidate_blocks(metric: int, dim: int, queries: np.ndarray, k: int,
     cnt = np.zeros(nq, dtype=np.int32)
     need = ctypes.c_int32(entries)
     thr = math.nan if distance_threshold is None else float(distance_threshold)
-    rc = _ffi.lib().tsh_merge_candidates(metric, dim, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr,
-                                         blocks.ctypes.data_as(ctypes.c_void_p), n_blocks, entries,
-                                         ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
-                                         cnt.ctypes.data_as(_ffi.p_i32), ctypes.byref(need))
+    if after is None:
+        rc = _ffi.lib().tsh_merge_candidates(metric, dim, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr,
+                                             blocks.ctypes.data_as(ctypes.c_void_p), n_blocks, entries,
+                                             ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                             cnt.ctypes.data_as(_ffi.p_i32), ctypes.byref(need))
+    else:
+        ad, ai = cursor_arrays(after, nq)
+        rc = _ffi.lib().tsh_merge_candidates_after(metric, dim, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr,
+                                                   ad.ctypes.data_as(_ffi.p_f64), ai.ctypes.data_as(_ffi.p_i64),
+                                                   blocks.ctypes.data_as(ctypes.c_void_p), n_blocks, entries,
+                                                   ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                   cnt.ctypes.data_as(_ffi.p_i32), ctypes.byref(need))
     if rc != _ffi.TSH_OK:
         err = _ffi.TshError(rc, _ffi.last_error())
         err.needed_entries = need.value
@@ -84,13 +117,20 @@ class ShardedSearcher:
         _, mine, allb, host = cur
         return mine[: nq * bb], allb[: self.world * nq * bb], host[: self.world * nq * bb]
 
-    def _scan(self, q: np.ndarray, k: int, mp, entries: int, slot: int):
-        """This rank's shard: candidate blocks for the queries of one group, left in device memory."""
+    def _scan(self, q: np.ndarray, k: int, mp, entries: int, slot: int, cur=None):
+        """This rank's shard: candidate blocks for the queries of one group, left in device memory.
+        cur: the queries' cursor arrays (cursor_arrays), or None."""
         mine, _, _ = self._buffers(q.shape[0], entries, slot)
-        _ffi.check(_ffi.lib().tsh_search_shard(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k), mp,
-                                               entries, ctypes.c_void_p(mine.data_ptr()), None))
+        if cur is None:
+            _ffi.check(_ffi.lib().tsh_search_shard(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k), mp,
+                                                   entries, ctypes.c_void_p(mine.data_ptr()), None))
+        else:
+            _ffi.check(_ffi.lib().tsh_search_shard_after(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k),
+                                                         mp, cur[0].ctypes.data_as(_ffi.p_f64),
+                                                         cur[1].ctypes.data_as(_ffi.p_i64), entries,
+                                                         ctypes.c_void_p(mine.data_ptr()), None))
 
-    def _exchange_merge(self, q: np.ndarray, k: int, thr, entries: int, slot: int, mine=None):
+    def _exchange_merge(self, q: np.ndarray, k: int, thr, entries: int, slot: int, mine=None, after=None):
         t = self._torch
         own, allb, host = self._buffers(q.shape[0], entries, slot)
         mine = own if mine is None else mine
@@ -99,7 +139,7 @@ class ShardedSearcher:
             mine_h = mine.cpu()
             self._dist.all_gather_into_tensor(host, mine_h, group=self.group)
             return merge_candidate_blocks(self.index.metric, self.index.dim, q, k, thr, host.numpy(),
-                                          self.world, entries)
+                                          self.world, entries, after)
         if self._dist.is_initialized():
             self._dist.all_gather_into_tensor(allb, mine, group=self.group)
         else:
@@ -107,14 +147,14 @@ class ShardedSearcher:
         host[: allb.numel()].copy_(allb, non_blocking=True)
         t.cuda.current_stream().synchronize()
         return merge_candidate_blocks(self.index.metric, self.index.dim, q, k, thr, host[: allb.numel()].numpy(),
-                                      self.world, entries)
+                                      self.world, entries, after)
 
     def search_many(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None,
-                    group: int = 8):
+                    group: int = 8, after=None):
         """A stream of independent queries, exchanged in groups: this rank's scans of ALL the queries run as one
         pipeline on a library thread (tsh_search_shard_begin: the GPU sees no group boundaries), and the calling
         thread all-gathers and merges every group as soon as its blocks are final (collectives stay on one thread,
-        in one order on every rank).  Same results as search()."""
+        in one order on every rank).  Same results as search().  `after`: as in search()."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -138,26 +178,37 @@ class ShardedSearcher:
             self._torch.cuda.current_stream().synchronize()
         mine_all = cur[1]
         st = ctypes.c_void_p()
-        _ffi.check(L.tsh_search_shard_begin(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mp, entries,
-                                            ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
+        cursors = None if after is None else cursor_arrays(after, nq)
+        if cursors is None:
+            _ffi.check(L.tsh_search_shard_begin(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mp, entries,
+                                                ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
+        else:
+            _ffi.check(L.tsh_search_shard_begin_after(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mp,
+                                                      cursors[0].ctypes.data_as(_ffi.p_f64),
+                                                      cursors[1].ctypes.data_as(_ffi.p_i64), entries,
+                                                      ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
         try:
             for g, (lo, hi) in enumerate(spans):
                 _ffi.check(L.tsh_search_shard_progress(st, hi, None))  # this group's blocks are final
                 try:
+                    part = None if cursors is None else (cursors[0][lo:hi], cursors[1][lo:hi])
                     i, d, c = self._exchange_merge(q[lo:hi], k, distance_threshold, entries, g % 2,
-                                                   mine_all[lo * bb: hi * bb])
+                                                   mine_all[lo * bb: hi * bb], part)
                 except _ffi.TshError as e:
                     if e.code != _ffi.TSH_E_OVERFLOW:
                         raise
                     _ffi.check(L.tsh_search_shard_progress(st, nq, None))  # nothing overlaps a retry
-                    i, d, c = self.search(q[lo:hi], k, distance_threshold, row_mask)  # ties: bigger blocks
+                    i, d, c = self.search(q[lo:hi], k, distance_threshold, row_mask, part)  # ties: bigger blocks
                 ids[lo:hi], dist[lo:hi], cnt[lo:hi] = i, d, c
         finally:
             rc = L.tsh_search_shard_end(st)
         _ffi.check(rc)
         return ids, dist, cnt
 
-    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None):
+    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, after=None):
+        """`after`: a GLOBAL cursor -- one (distance, id), or one per query; the same on every rank -- behind which
+        the answer starts: the next k rows past it (tsh_search_shard_after + tsh_merge_candidates_after).  A page
+        shorter than k is the last one."""
         t = self._torch
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
@@ -166,10 +217,11 @@ class ShardedSearcher:
         L = _ffi.lib()
         entries = L.tsh_default_block_entries(int(k))
         row_mask, mp = self.index.mask_arg(row_mask)  # GLOBAL mask: one bit per row id below this shard's end
+        cur = None if after is None else cursor_arrays(after, nq)
         for _attempt in range(3):
-            self._scan(q, k, mp, entries, 0)
+            self._scan(q, k, mp, entries, 0, cur)
             try:
-                return self._exchange_merge(q, k, distance_threshold, entries, 0)
+                return self._exchange_merge(q, k, distance_threshold, entries, 0, None, after)
             except _ffi.TshError as e:
                 if e.code != _ffi.TSH_E_OVERFLOW:
                     raise
@@ -262,9 +314,10 @@ class CommSearcher:
     def __exit__(self, *exc):
         self.close()
 
-    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, shard=...):
+    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, shard=..., after=None):
         """Collective.  `shard=None` (tests) passes a NULL handle: this rank fails locally and stays in the
-        collective."""
+        collective.  `after`: a GLOBAL cursor -- one (distance, id), or one per query; the same on every rank --
+        behind which the answer starts (tsh_search_sharded_after)."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -275,18 +328,26 @@ class CommSearcher:
         thr = math.nan if distance_threshold is None else float(distance_threshold)
         row_mask, mp = self.index.mask_arg(row_mask)
         h = self.index._h if shard is ... else shard
-        _ffi.check(_ffi.lib().tsh_search_sharded(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp,
-                                                 ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
-                                                 cnt.ctypes.data_as(_ffi.p_i32)))
+        if after is None:
+            _ffi.check(_ffi.lib().tsh_search_sharded(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp,
+                                                     ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                     cnt.ctypes.data_as(_ffi.p_i32)))
+        else:
+            ad, ai = cursor_arrays(after, nq)
+            _ffi.check(_ffi.lib().tsh_search_sharded_after(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp,
+                                                           ad.ctypes.data_as(_ffi.p_f64), ai.ctypes.data_as(_ffi.p_i64),
+                                                           ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                           cnt.ctypes.data_as(_ffi.p_i32)))
         return ids[:, :kk], dist[:, :kk], cnt
 
-    def search_many(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, group: int = 0):
+    def search_many(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, group: int = 0,
+                    after=None):
         """One collective call; the library forms the groups itself (same signature as
         ShardedSearcher.search_many; `group` > 0 overrides the library's choice)."""
         if group:
             self.set_group(group)
         try:
-            return self.search(queries, k, distance_threshold, row_mask)
+            return self.search(queries, k, distance_threshold, row_mask, after=after)
         finally:
             if group:
                 self.set_group(0)
