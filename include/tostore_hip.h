@@ -49,7 +49,8 @@ extern "C" {
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
  *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS;
  *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats;
- *    tsh_search_shard_after, tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after. */
+ *    tsh_search_shard_after, tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after;
+ *    tsh_search_shard_masked, tsh_search_shard_begin_masked, tsh_search_sharded_masked. */
 
 /* status codes */
 #define TSH_OK 0
@@ -467,6 +468,38 @@ int32_t tsh_merge_candidates_after(int32_t metric, int32_t dim, const float *que
                                    double distance_threshold, const double *after_dist, const int64_t *after_id,
                                    const void *blocks, int32_t n_blocks, int32_t entries, int64_t *out_ids,
                                    double *out_dist, int32_t *out_count, int32_t *needed_entries);
+/* The sharded entries with a mask HANDLE (tsh_mask_create on the shard handle) in place of the row_mask pointer, and an
+ * OPTIONAL cursor (additive since ABI 5).  The pointer entries slice, count and -- for a selective mask -- list the
+ * caller's GLOBAL bitmap on the host in every call, on every rank, and the progressive form copies the bitmap up to the
+ * shard's end first; these read the handle's device words and list in place: no per-call slice, count, list, upload or
+ * bitmap copy happens anywhere in a handle call.
+ *   mask        NULL = no filter: the call behaves as the pointer entry with row_mask == NULL.  Otherwise a handle made
+ *               for `idx` (tsh_search_sharded_masked: for `shard`); a handle made for another index, or an orphaned
+ *               one, is TSH_E_BAD_ARG.  The handle must outlive the call -- for _begin_masked the stream, up to _end:
+ *               only the handle is kept, never a copy of a bitmap.
+ *   after_dist / after_id   both NULL: no cursor (tsh_search_shard / _begin / tsh_search_sharded).  Both given: nq each,
+ *               tsh_search_after's semantics (tsh_search_shard_after / _begin_after / tsh_search_sharded_after).
+ *               Exactly one NULL is TSH_E_BAD_ARG.
+ * The blocks, and the answer merged from them (tsh_merge_candidates / _after), are those of the pointer entry given the
+ * bitmap the handle was made from, zero-extended to the shard's current end: rows appended after tsh_mask_create are
+ * not kept, as in tsh_search_masked.  The shard's part of the handle is looked up under the shard's shared lock and
+ * rebuilt there if the shard grew; the first scans, an overflow retry with larger blocks, a cursor job's side-list redo
+ * and the batched path's listed and dense modes all read it.  Block layout, overflow protocol (count > entries,
+ * TSH_E_OVERFLOW with the entry count to retry with), _progress / _end, the batched route and `step`, "a cursor call is
+ * never batched", TSH_OPT_EXCHANGE_AHEAD ignored behind a cursor, failure protocol and timeline: the pointer entries'.
+ * Every rank makes its own handle from the same GLOBAL bitmap; as with the pointer form, the library does not check
+ * that the ranks agree.  In tsh_search_sharded_masked a bad handle is a LOCAL failure like a bad shard handle: the rank
+ * stays in the collective and returns its own error, its peers return TSH_E_PEER, the communicator stays usable.
+ * Measured on one MI355X (profiles/shard_mask_handle_ab.json, tools/ab_shard_mask_handle.py; one shard handle of
+ * 1 M x 768 f32, L2, k = 100, medians, two processes): a lone query behind a keep-1 % mask 104.9 - 107.7 us per call
+ * through tsh_search_shard, 33.9 - 34.6 us through tsh_search_shard_masked; a 64-query call behind a keep-50 % mask
+ * 587 us by pointer, 493 us by handle. */
+int32_t tsh_search_shard_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
+                                const double *after_dist, const int64_t *after_id, int32_t entries,
+                                void *d_out_blocks, void *stream);
+int32_t tsh_search_shard_begin_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
+                                      const double *after_dist, const int64_t *after_id, int32_t entries,
+                                      void *d_out_blocks, int32_t step, tsh_shard_stream **out);
 
 /* ---- the same exchange from a host without torch (a Dart process per GPU) ------------------------------------
  * RCCL all-gather of the per-shard candidate blocks over xGMI + host merge, behind plain C.  librccl is loaded
@@ -523,6 +556,12 @@ int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *comm, const float *querie
 int32_t tsh_search_sharded_after(tsh_index *shard, tsh_comm *comm, const float *queries, int32_t nq, int32_t k,
                                  double distance_threshold, const uint8_t *row_mask, const double *after_dist,
                                  const int64_t *after_id, int64_t *out_ids, double *out_dist, int32_t *out_count);
+/* tsh_search_sharded / tsh_search_sharded_after with this rank's mask handle (see tsh_search_shard_masked above): mask
+ * NULL = no filter, after_dist / after_id both NULL = no cursor.  Collective like the two; a bad handle on one rank
+ * does not leave the ranks out of step. */
+int32_t tsh_search_sharded_masked(tsh_index *shard, tsh_comm *comm, const float *queries, int32_t nq, int32_t k,
+                                  double distance_threshold, tsh_mask *mask, const double *after_dist,
+                                  const int64_t *after_id, int64_t *out_ids, double *out_dist, int32_t *out_count);
 
 /* Where the time of this rank's tsh_search_sharded calls went: sums over the calls since the communicator was made
  * (or since the last reset).  On the calling thread a call is, group after group,

@@ -579,8 +579,8 @@ int comm_check_create(const void *id_or_fn, int32_t world, int32_t rank, int32_t
 }
 
 int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
-                        const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
-                        double *out_dist, int32_t *out_count);
+                        const uint8_t *row_mask, tsh_mask *mask_h, const double *after_dist, const int64_t *after_id,
+                        int64_t *out_ids, double *out_dist, int32_t *out_count);
 
 }  // namespace
 
@@ -675,14 +675,21 @@ int32_t tsh_comm_get_timeline(tsh_comm *c, tsh_comm_timeline *out, int32_t reset
 
 int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
                            const uint8_t *row_mask, int64_t *out_ids, double *out_dist, int32_t *out_count) {
-  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, nullptr, nullptr, out_ids, out_dist, out_count);
+  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, nullptr, nullptr, nullptr, out_ids, out_dist, out_count);
 }
 int32_t tsh_search_sharded_after(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
                                  const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
                                  double *out_dist, int32_t *out_count) {
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, after_dist, after_id, out_ids, out_dist, out_count);
+  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, nullptr, after_dist, after_id, out_ids, out_dist, out_count);
+}
+int32_t tsh_search_sharded_masked(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
+                                  tsh_mask *mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                                  double *out_dist, int32_t *out_count) {
+  if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
+  if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return search_sharded_impl(shard, c, queries, nq, k, thr, nullptr, mask, after_dist, after_id, out_ids, out_dist, out_count);
 }
 
 }  // extern "C"
@@ -693,9 +700,11 @@ namespace {
 // like the queries), or both NULL.  A cursor call differs in three places: its groups follow the scan schedule (every
 // query is its own scan on every rank, whatever a rank's batch threshold says), its exchanges go out when the blocks are
 // final (a side-list redo rewrites a block after its kernels were enqueued), and every merge passes its queries' cursors.
+// mask_h: a mask handle in place of row_mask (tsh_search_sharded_masked), or NULL -- this rank's own, so a bad one is a
+// local failure that travels through the exchange like a bad shard handle.
 int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
-                        const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
-                        double *out_dist, int32_t *out_count) {
+                        const uint8_t *row_mask, tsh_mask *mask_h, const double *after_dist, const int64_t *after_id,
+                        int64_t *out_ids, double *out_dist, int32_t *out_count) {
   // arguments that are the same on every rank by contract are answered locally ...
   if (!c) return set_err(TSH_E_BAD_ARG, "comm is NULL");
   if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
@@ -711,6 +720,8 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
     local_rc = set_err(TSH_E_BAD_ARG, "needs a single-shard handle (tsh_index_create_shard)");
   else if (shard->shards[0]->device != c->device)
     local_rc = set_err(TSH_E_BAD_ARG, "shard and communicator sit on different devices");
+  else if (mask_h && mask_h->idx != shard)
+    local_rc = set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
   std::string local_err = g_err;
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
@@ -778,7 +789,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       const bool ahead = !after_dist && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
       scan_rc = shard_stream_begin(shard, queries + (size_t)w0 * dim, wn, k, row_mask, entries, c->d_mine, sizes[gi],
                                    /*copy_inputs=*/false, &ss, ss_tag, c->worker.get(), ahead, after_dist ? after_dist + w0 : nullptr,
-                                   after_dist ? after_id + w0 : nullptr);
+                                   after_dist ? after_id + w0 : nullptr, mask_h);
       if (scan_rc) scan_err = g_err;
     }
     auto end_stream = [&] {  // nothing of this call may still run when it returns
@@ -844,7 +855,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
         std::string again_err = local_rc != TSH_OK ? local_err : scan_err;
         if (again_rc == TSH_OK) {
           const double t0 = now_us();
-          again_rc = search_shard_impl(shard, queries + (size_t)qa * dim, gq, k, row_mask, ent, c->d_retry, nullptr,
+          again_rc = search_shard_impl(shard, queries + (size_t)qa * dim, gq, k, row_mask, mask_h, ent, c->d_retry, nullptr,
                                        after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
           c->scan_ns.fetch_add((int64_t)((now_us() - t0) * 1e3), std::memory_order_relaxed);
           if (again_rc) again_err = g_err;

@@ -3236,10 +3236,12 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double thr, int64_t *out
 }
 
 namespace {
-// tsh_search_shard; after_dist / after_id: a cursor per query (tsh_search_shard_after), or both NULL
-int32_t search_shard_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask, int32_t entries,
-                          void *d_out_blocks, void *stream, const double *after_dist, const int64_t *after_id) {
+// tsh_search_shard; after_dist / after_id: a cursor per query (tsh_search_shard_after), or both NULL; mask_h: a mask
+// handle in place of row_mask (tsh_search_shard_masked), or NULL
+int32_t search_shard_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask, tsh_mask *mask_h,
+                          int32_t entries, void *d_out_blocks, void *stream, const double *after_dist, const int64_t *after_id) {
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
   if (nq <= 0 || !queries || !d_out_blocks || k <= 0 || entries < 1)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / pointers");
   Shard *s = idx->shards[0].get();
@@ -3258,27 +3260,42 @@ int32_t search_shard_impl(tsh_index *idx, const float *queries, int32_t nq, int3
     HIPCHK(hipMemcpy(d_out_blocks, z.data(), z.size(), hipMemcpyHostToDevice));
     return TSH_OK;
   }
+  MaskSrc ms(row_mask);
+  if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
+    int rc = TSH_OK;
+    const MaskPart *mp = mask_part(mask_h, 0, s, &rc);
+    if (!mp) return rc;
+    ms = MaskSrc(mp);
+  }
   SearchOut so;
   so.d_blocks = static_cast<uint8_t *>(d_out_blocks);
   so.user_stream = static_cast<hipStream_t>(stream);
   if (after_dist) {  // a cursor call is never batched: every query is its own scan
     so.after_dist = after_dist;
     so.after_id = after_id;
-    return shard_search_blocks(s, queries, nq, k, row_mask, entries, &so, PIPE_DEPTH);
+    return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
   }
-  return shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, row_mask, entries, &so);
+  return shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, ms, entries, &so);
 }
+// the _masked entries' cursor is optional: both arrays or neither
+inline bool half_cursor(const double *after_dist, const int64_t *after_id) { return (after_dist == nullptr) != (after_id == nullptr); }
 }  // namespace
 
 int32_t tsh_search_shard(tsh_index *idx, const float *queries, int32_t nq, int32_t k,
                          const uint8_t *row_mask, int32_t entries, void *d_out_blocks, void *stream) {
-  return search_shard_impl(idx, queries, nq, k, row_mask, entries, d_out_blocks, stream, nullptr, nullptr);
+  return search_shard_impl(idx, queries, nq, k, row_mask, nullptr, entries, d_out_blocks, stream, nullptr, nullptr);
 }
 int32_t tsh_search_shard_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
                                const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks, void *stream) {
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_shard_impl(idx, queries, nq, k, row_mask, entries, d_out_blocks, stream, after_dist, after_id);
+  return search_shard_impl(idx, queries, nq, k, row_mask, nullptr, entries, d_out_blocks, stream, after_dist, after_id);
+}
+int32_t tsh_search_shard_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
+                                const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks, void *stream) {
+  if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return search_shard_impl(idx, queries, nq, k, nullptr, mask, entries, d_out_blocks, stream, after_dist, after_id);
 }
 
 // ---- progressive shard search ---------------------------------------------------------------------------------
@@ -3291,6 +3308,7 @@ struct tsh_shard_stream {
   tsh_index *idx = nullptr;
   const float *queries = nullptr;
   const uint8_t *mask = nullptr;
+  tsh_mask *mask_h = nullptr;  // ... or a mask handle (tsh_search_shard_begin_masked): the handle is kept, no bitmap is
   const double *after_dist = nullptr;  // a cursor per query (tsh_search_shard_begin_after), or both NULL
   const int64_t *after_id = nullptr;
   std::vector<float> own_queries;  // public entry points: the caller's arrays are consumed before begin returns
@@ -3374,6 +3392,13 @@ struct tsh_shard_stream {
         mask = own_mask.data();
       }
     }
+    MaskSrc ms(mask);
+    if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
+      int prc = TSH_OK;
+      const MaskPart *mp = mask_part(mask_h, 0, s, &prc);
+      if (!mp) return prc;
+      ms = MaskSrc(mp);
+    }
     const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
     if (s->rows == 0) {  // an empty shard contributes empty blocks
       std::vector<uint8_t> z(bb * (size_t)nq, 0);
@@ -3409,7 +3434,7 @@ struct tsh_shard_stream {
       so.on_enqueued = [this](int32_t q, hipEvent_t ev, hipStream_t where, uint64_t seq) { mark_enqueued(q, ev, where, seq); };
       route.store(1, std::memory_order_release);
       cv.notify_all();
-      return shard_search_blocks(s, queries, nq, k, mask, entries, &so, PIPE_DEPTH);
+      return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
     }
     route.store(2, std::memory_order_release);
     cv.notify_all();
@@ -3420,7 +3445,7 @@ struct tsh_shard_stream {
       SearchOut so;
       so.d_blocks = d_blocks + (size_t)q0 * bb;
       so.tag = tag;  // (queries the batch hands back to the single-query path carry it at once)
-      int r = shard_search_any(s, s->batch, min_nq, queries + (size_t)q0 * s->dim, gq, k, mask, entries, &so);
+      int r = shard_search_any(s, s->batch, min_nq, queries + (size_t)q0 * s->dim, gq, k, ms, entries, &so);
       if (r) return r;
       if (tag) {  // the matrix-core path's blocks get their generation now (host-synchronised: they are final)
         stamp_tag_kernel<<<(unsigned)((gq + 63) / 64), 64, 0, s->aux_stream>>>(so.d_blocks, bb, gq, tag);
@@ -3451,10 +3476,11 @@ namespace {
 int shard_stream_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
                        int32_t entries, void *d_out_blocks, int32_t step, bool copy_inputs, tsh_shard_stream **out,
                        uint32_t tag = 0, OneWorker *exec = nullptr, bool leave_overflow = false,
-                       const double *after_dist = nullptr, const int64_t *after_id = nullptr) {
+                       const double *after_dist = nullptr, const int64_t *after_id = nullptr, tsh_mask *mask_h = nullptr) {
   if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
   *out = nullptr;
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
   if (nq <= 0 || !queries || !d_out_blocks || k <= 0 || entries < 1 || step < 0)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / step / pointers");
   std::unique_ptr<tsh_shard_stream> st(new tsh_shard_stream());
@@ -3468,6 +3494,7 @@ int shard_stream_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t
   st->d_blocks = static_cast<uint8_t *>(d_out_blocks);
   st->queries = queries;
   st->mask = row_mask;
+  st->mask_h = mask_h;
   st->after_dist = after_dist;
   st->after_id = after_id;
   if (copy_inputs) {
@@ -3590,6 +3617,15 @@ int32_t tsh_search_shard_begin_after(tsh_index *idx, const float *queries, int32
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
   return shard_stream_begin(idx, queries, nq, k, row_mask, entries, d_out_blocks, step, /*copy_inputs=*/true, out, 0, nullptr, false,
                             after_dist, after_id);
+}
+int32_t tsh_search_shard_begin_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
+                                      const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks,
+                                      int32_t step, tsh_shard_stream **out) {
+  if (out) *out = nullptr;
+  if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  return shard_stream_begin(idx, queries, nq, k, nullptr, entries, d_out_blocks, step, /*copy_inputs=*/true, out, 0, nullptr, false,
+                            after_dist, after_id, mask);
 }
 int32_t tsh_search_shard_progress(tsh_shard_stream *st, int32_t want, int32_t *out_done) {
   if (!st) return set_err(TSH_E_BAD_ARG, "stream is NULL");

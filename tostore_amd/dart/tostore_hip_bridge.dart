@@ -178,6 +178,18 @@ typedef _SearchShardedAfterC = Int32 Function(Pointer<Void>, Pointer<Void>, Poin
     Double, Pointer<Uint8>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchShardedAfterD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, int, int,
     double, Pointer<Uint8>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SearchShardMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Void>,
+    Pointer<Double>, Pointer<Int64>, Int32, Pointer<Void>, Pointer<Void>);
+typedef _SearchShardMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Void>,
+    Pointer<Double>, Pointer<Int64>, int, Pointer<Void>, Pointer<Void>);
+typedef _ShardBeginMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Void>,
+    Pointer<Double>, Pointer<Int64>, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
+typedef _ShardBeginMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Void>,
+    Pointer<Double>, Pointer<Int64>, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
+typedef _SearchShardedMaskedC = Int32 Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, Int32, Int32,
+    Double, Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SearchShardedMaskedD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, int, int,
+    double, Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 
 /// `tsh_counters` (include/tostore_hip.h).  Field order and widths are checked against the header by
 /// tests/test_dart_bridge.py.
@@ -363,6 +375,9 @@ final class HipVectorBackend {
   static late final _ShardBeginAfterD _shardBeginAfter;
   static late final _MergeAfterD _mergeAfter;
   static late final _SearchShardedAfterD _searchShardedAfter;
+  static late final _SearchShardMaskedD _searchShardMasked;
+  static late final _ShardBeginMaskedD _shardBeginMasked;
+  static late final _SearchShardedMaskedD _searchShardedMasked;
   static late final _CommTimelineD _commTimeline;
   static late final _OpenNghShardD _openNghShard;
   static late final _MaskCreateD _maskCreate;
@@ -435,6 +450,12 @@ final class HipVectorBackend {
       _mergeAfter = lib.lookupFunction<_MergeAfterC, _MergeAfterD>('tsh_merge_candidates_after');
       _searchShardedAfter =
           lib.lookupFunction<_SearchShardedAfterC, _SearchShardedAfterD>('tsh_search_sharded_after');
+      _searchShardMasked =
+          lib.lookupFunction<_SearchShardMaskedC, _SearchShardMaskedD>('tsh_search_shard_masked');
+      _shardBeginMasked =
+          lib.lookupFunction<_ShardBeginMaskedC, _ShardBeginMaskedD>('tsh_search_shard_begin_masked');
+      _searchShardedMasked =
+          lib.lookupFunction<_SearchShardedMaskedC, _SearchShardedMaskedD>('tsh_search_sharded_masked');
       _commTimeline =
           lib.lookupFunction<_CommTimelineC, _CommTimelineD>('tsh_comm_get_timeline');
       _openNghShard =
@@ -1089,6 +1110,69 @@ final class HipVectorBackend {
         0;
   }
 
+  /// [searchShard] / [shardStreamBegin] with a device-resident WHERE row set in place of the bitmap pointer, and an
+  /// optional GLOBAL cursor per query (tsh_search_shard_masked, tsh_search_shard_begin_masked): the library reads
+  /// the mask's device words and list in place -- no per-call slice, count, list or copy of a bitmap on this rank.
+  /// `mask`: made by [createMask] on THIS backend from the same GLOBAL bitmap every rank uses (null = no filter); it
+  /// must stay undisposed until the call returns -- for the progressive form until [shardStreamEnd].  A disposed
+  /// mask is refused (false / nullptr, with a warning): it must not become "no filter".  `afterDistances` /
+  /// `afterNodeIds`: both (nq each, [searchShardAfter]'s semantics) or neither.  Blocks, overflow protocol,
+  /// [shardStreamProgress] / [shardStreamEnd] and the merge are the pointer forms'.
+  bool searchShardMasked(Pointer<Float> queries, int nq, int topK, HipRowMask? mask, int entries,
+      Pointer<Void> deviceBlocks, {List<double>? afterDistances, List<int>? afterNodeIds}) {
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchShardMasked with a disposed HipRowMask', label: 'HipVectorBackend');
+      return false;
+    }
+    if ((afterDistances == null) != (afterNodeIds == null)) return false;
+    if (afterDistances != null && (afterDistances.length != nq || afterNodeIds!.length != nq)) return false;
+    Pointer<Double> ad = nullptr;
+    Pointer<Int64> ai = nullptr;
+    try {
+      if (afterDistances != null) {
+        ad = calloc<Double>(nq);
+        ai = calloc<Int64>(nq);
+        ad.asTypedList(nq).setAll(0, afterDistances);
+        ai.asTypedList(nq).setAll(0, afterNodeIds!);
+      }
+      return _searchShardMasked(_handle, queries, nq, topK, mask?._mask ?? nullptr, ad, ai, entries,
+              deviceBlocks, nullptr) ==
+          0;
+    } finally {
+      if (ad != nullptr) calloc.free(ad);
+      if (ai != nullptr) calloc.free(ai);
+    }
+  }
+
+  Pointer<Void> shardStreamBeginMasked(Pointer<Float> queries, int nq, int topK, HipRowMask? mask,
+      int entries, Pointer<Void> deviceBlocks, int step,
+      {List<double>? afterDistances, List<int>? afterNodeIds}) {
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('shardStreamBeginMasked with a disposed HipRowMask', label: 'HipVectorBackend');
+      return nullptr;
+    }
+    if ((afterDistances == null) != (afterNodeIds == null)) return nullptr;
+    if (afterDistances != null && (afterDistances.length != nq || afterNodeIds!.length != nq)) return nullptr;
+    Pointer<Double> ad = nullptr;
+    Pointer<Int64> ai = nullptr;
+    final out = calloc<Pointer<Void>>();
+    try {
+      if (afterDistances != null) {  // (the cursors are copied by the call, like the queries)
+        ad = calloc<Double>(nq);
+        ai = calloc<Int64>(nq);
+        ad.asTypedList(nq).setAll(0, afterDistances);
+        ai.asTypedList(nq).setAll(0, afterNodeIds!);
+      }
+      final rc = _shardBeginMasked(_handle, queries, nq, topK, mask?._mask ?? nullptr, ad, ai, entries,
+          deviceBlocks, step, out);
+      return rc == 0 ? out.value : nullptr;
+    } finally {
+      calloc.free(out);
+      if (ad != nullptr) calloc.free(ad);
+      if (ai != nullptr) calloc.free(ai);
+    }
+  }
+
   void dispose() {
     if (_handle != nullptr) {
       _destroy(_handle);
@@ -1179,8 +1263,28 @@ final class HipShardComm {
     return _search(queries, topK, distanceThreshold, rowMask, afterDistances, afterNodeIds);
   }
 
+  /// [search] / [searchShardedAfter] with this rank's device-resident WHERE row set (tsh_search_sharded_masked):
+  /// `mask` made by [HipVectorBackend.createMask] on this rank's shard from the same GLOBAL bitmap on every rank
+  /// (null = no filter); `afterDistances` / `afterNodeIds`: both or neither.  No rank slices, counts or lists a
+  /// bitmap per call.  A disposed mask is refused before the collective is entered (null, with a warning): every
+  /// rank must refuse alike, or dispose only between calls.  A mask of another backend is this rank's own failure
+  /// inside the collective: its peers get TSH_E_PEER and the communicator stays usable.
+  List<List<NghSearchResult>>? searchShardedMasked(List<Float32List> queries, int topK, HipRowMask? mask,
+      {double? distanceThreshold, List<double>? afterDistances, List<int>? afterNodeIds}) {
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchShardedMasked with a disposed HipRowMask', label: 'HipShardComm');
+      return null;
+    }
+    if ((afterDistances == null) != (afterNodeIds == null)) return null;
+    if (afterDistances != null &&
+        (afterDistances.length != queries.length || afterNodeIds!.length != queries.length)) return null;
+    return _search(queries, topK, distanceThreshold, null, afterDistances, afterNodeIds,
+        handle: mask, viaHandle: true);
+  }
+
   List<List<NghSearchResult>>? _search(List<Float32List> queries, int topK, double? distanceThreshold,
-      Uint8List? rowMask, List<double>? afterDistances, List<int>? afterNodeIds) {
+      Uint8List? rowMask, List<double>? afterDistances, List<int>? afterNodeIds,
+      {HipRowMask? handle, bool viaHandle = false}) {
     final nq = queries.length, d = shard.dimensions;
     if (nq == 0 || topK <= 0) return [for (var i = 0; i < nq; i++) const []];
     final q = calloc<Float>(nq * d);
@@ -1205,7 +1309,10 @@ final class HipShardComm {
         ad.asTypedList(nq).setAll(0, afterDistances);
         ai.asTypedList(nq).setAll(0, afterNodeIds);
       }
-      final rc = ad != nullptr
+      final rc = viaHandle
+          ? HipVectorBackend._searchShardedMasked(shard._handle, _comm, q, nq, topK,
+              distanceThreshold ?? double.nan, handle?._mask ?? nullptr, ad, ai, ids, dist, cnt)
+          : ad != nullptr
           ? HipVectorBackend._searchShardedAfter(shard._handle, _comm, q, nq, topK,
               distanceThreshold ?? double.nan, mask, ad, ai, ids, dist, cnt)
           : HipVectorBackend._searchSharded(shard._handle, _comm, q, nq, topK,

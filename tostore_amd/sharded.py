@@ -43,6 +43,25 @@ def cursor_arrays(after, nq: int):
     return ad, ai
 
 
+def mask_forms(index, row_mask):
+    """The two forms of a WHERE row set for the sharded entries: (kept alive by the caller, row_mask pointer, tsh_mask*).
+    A HipMask goes to the *_masked entries (its handle; ValueError once it is closed), anything else is a GLOBAL keep
+    bitmap for the pointer entries (HipVectorIndex.mask_arg)."""
+    from .backend import HipMask
+
+    if isinstance(row_mask, HipMask):
+        return row_mask, None, row_mask.handle()
+    keep, mp = index.mask_arg(row_mask)
+    return keep, mp, None
+
+
+def _cursor_ptrs(cur):
+    """(after_dist, after_id) pointers of cursor_arrays' pair; (None, None) without a cursor"""
+    if cur is None:
+        return None, None
+    return cur[0].ctypes.data_as(_ffi.p_f64), cur[1].ctypes.data_as(_ffi.p_i64)
+
+
 def merge_candidate_blocks(metric: int, dim: int, queries: np.ndarray, k: int,
                            distance_threshold: Optional[float], blocks: np.ndarray, n_blocks: int,
                            entries: int, after=None):
@@ -117,11 +136,16 @@ class ShardedSearcher:
         _, mine, allb, host = cur
         return mine[: nq * bb], allb[: self.world * nq * bb], host[: self.world * nq * bb]
 
-    def _scan(self, q: np.ndarray, k: int, mp, entries: int, slot: int, cur=None):
+    def _scan(self, q: np.ndarray, k: int, mp, entries: int, slot: int, cur=None, mh=None):
         """This rank's shard: candidate blocks for the queries of one group, left in device memory.
-        cur: the queries' cursor arrays (cursor_arrays), or None."""
+        cur: the queries' cursor arrays (cursor_arrays), or None.  mh: a mask handle in place of the pointer mp
+        (tsh_search_shard_masked, with or without the cursor)."""
         mine, _, _ = self._buffers(q.shape[0], entries, slot)
-        if cur is None:
+        if mh is not None:
+            ad, ai = _cursor_ptrs(cur)
+            _ffi.check(_ffi.lib().tsh_search_shard_masked(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k),
+                                                          mh, ad, ai, entries, ctypes.c_void_p(mine.data_ptr()), None))
+        elif cur is None:
             _ffi.check(_ffi.lib().tsh_search_shard(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k), mp,
                                                    entries, ctypes.c_void_p(mine.data_ptr()), None))
         else:
@@ -154,7 +178,8 @@ class ShardedSearcher:
         """A stream of independent queries, exchanged in groups: this rank's scans of ALL the queries run as one
         pipeline on a library thread (tsh_search_shard_begin: the GPU sees no group boundaries), and the calling
         thread all-gathers and merges every group as soon as its blocks are final (collectives stay on one thread,
-        in one order on every rank).  Same results as search().  `after`: as in search()."""
+        in one order on every rank).  Same results as search().  `after`, `row_mask`: as in search() (a HipMask:
+        tsh_search_shard_begin_masked; it must stay open until this returns)."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -164,7 +189,7 @@ class ShardedSearcher:
         cnt = np.zeros(nq, dtype=np.int32)
         L = _ffi.lib()
         entries = L.tsh_default_block_entries(int(k))
-        row_mask, mp = self.index.mask_arg(row_mask)  # GLOBAL mask: one bit per row id below this shard's end
+        row_mask, mp, mh = mask_forms(self.index, row_mask)  # GLOBAL mask: one bit per row id below this shard's end
         group = max(1, int(group))
         spans = [(s, min(nq, s + group)) for s in range(0, nq, group)]
         if not spans:
@@ -179,7 +204,11 @@ class ShardedSearcher:
         mine_all = cur[1]
         st = ctypes.c_void_p()
         cursors = None if after is None else cursor_arrays(after, nq)
-        if cursors is None:
+        if mh is not None:
+            ad, ai = _cursor_ptrs(cursors)
+            _ffi.check(L.tsh_search_shard_begin_masked(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mh, ad, ai,
+                                                       entries, ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
+        elif cursors is None:
             _ffi.check(L.tsh_search_shard_begin(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mp, entries,
                                                 ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
         else:
@@ -208,7 +237,8 @@ class ShardedSearcher:
     def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, after=None):
         """`after`: a GLOBAL cursor -- one (distance, id), or one per query; the same on every rank -- behind which
         the answer starts: the next k rows past it (tsh_search_shard_after + tsh_merge_candidates_after).  A page
-        shorter than k is the last one."""
+        shorter than k is the last one.  `row_mask`: a GLOBAL keep bitmap, or a HipMask made for this rank's shard
+        from it (tsh_search_shard_masked, on the first scan and on an overflow retry alike)."""
         t = self._torch
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
@@ -216,10 +246,10 @@ class ShardedSearcher:
         nq = q.shape[0]
         L = _ffi.lib()
         entries = L.tsh_default_block_entries(int(k))
-        row_mask, mp = self.index.mask_arg(row_mask)  # GLOBAL mask: one bit per row id below this shard's end
+        row_mask, mp, mh = mask_forms(self.index, row_mask)  # GLOBAL mask: one bit per row id below this shard's end
         cur = None if after is None else cursor_arrays(after, nq)
         for _attempt in range(3):
-            self._scan(q, k, mp, entries, 0, cur)
+            self._scan(q, k, mp, entries, 0, cur, mh)
             try:
                 return self._exchange_merge(q, k, distance_threshold, entries, 0, None, after)
             except _ffi.TshError as e:
@@ -317,7 +347,8 @@ class CommSearcher:
     def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, shard=..., after=None):
         """Collective.  `shard=None` (tests) passes a NULL handle: this rank fails locally and stays in the
         collective.  `after`: a GLOBAL cursor -- one (distance, id), or one per query; the same on every rank --
-        behind which the answer starts (tsh_search_sharded_after)."""
+        behind which the answer starts (tsh_search_sharded_after).  `row_mask`: a GLOBAL keep bitmap, or a HipMask made
+        for this rank's shard from it (tsh_search_sharded_masked, with or without `after`)."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -326,9 +357,14 @@ class CommSearcher:
         dist = np.empty((nq, max(kk, 1)), dtype=np.float64)
         cnt = np.zeros(nq, dtype=np.int32)
         thr = math.nan if distance_threshold is None else float(distance_threshold)
-        row_mask, mp = self.index.mask_arg(row_mask)
+        row_mask, mp, mh = mask_forms(self.index, row_mask)
         h = self.index._h if shard is ... else shard
-        if after is None:
+        if mh is not None:
+            ad, ai = _cursor_ptrs(None if after is None else cursor_arrays(after, nq))
+            _ffi.check(_ffi.lib().tsh_search_sharded_masked(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mh,
+                                                            ad, ai, ids.ctypes.data_as(_ffi.p_i64),
+                                                            dist.ctypes.data_as(_ffi.p_f64), cnt.ctypes.data_as(_ffi.p_i32)))
+        elif after is None:
             _ffi.check(_ffi.lib().tsh_search_sharded(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp,
                                                      ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
                                                      cnt.ctypes.data_as(_ffi.p_i32)))
