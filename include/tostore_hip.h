@@ -50,7 +50,8 @@ extern "C" {
  *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS;
  *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats;
  *    tsh_search_shard_after, tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after;
- *    tsh_search_shard_masked, tsh_search_shard_begin_masked, tsh_search_sharded_masked. */
+ *    tsh_search_shard_masked, tsh_search_shard_begin_masked, tsh_search_sharded_masked;
+ *    tsh_search_count, tsh_search_count_stats. */
 
 /* status codes */
 #define TSH_OK 0
@@ -366,6 +367,7 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double distance_threshol
  * however deep it is: a pass over the scan's keys takes the rows at or before the cursor out of the select's sight,
  * and the few rows whose f32 key cannot tell are decided by their exact distances (tostore_amd/csrc/tsh_after.hip.h,
  * tsh_after_band.h).  "Everything within distance_threshold" is a loop of pages that ends at the first short page.
+ * How long that list is, without walking it: tsh_search_count below.
  * row_mask / mask: at most one of the two forms of a WHERE row set, or neither.  after_dist / after_id: nq each.
  * Works on whole-index handles, handles over several devices and shard handles (global ids).  Several queries per
  * call run as the pipeline of single-query scans, never on the batched path.  TSH_E_BAD_ARG: both masks, a NULL
@@ -387,6 +389,32 @@ int32_t tsh_search_after(tsh_index *idx, const float *queries, int32_t nq, int32
 int32_t tsh_search_submit_after(tsh_index *idx, const float *query, int32_t k, const uint8_t *row_mask, tsh_mask *mask,
                                 double after_dist, int64_t after_id, int32_t *out_ticket);
 int32_t tsh_search_after_stats(tsh_index *idx, int64_t *out);
+
+/* ---- count the rows a search would return (additive since ABI 5) --------------------------------------------------
+ * out_count[q] is the number of entries in the list tsh_search_after would return for query q with k = infinity: the
+ * row mask (pointer or handle, at most one), tombstones, gaps, quarantined rows, distance_threshold and cursor are the
+ * same.  A row counts only if it passes the threshold as the finaliser applies it (dropped iff distance >
+ * distance_threshold under IEEE >: a NaN threshold is none, a NaN distance passes any, -0.0 and +0.0 are one threshold)
+ * and, with a cursor, only if it follows (after_dist[q], after_id[q]) strictly in (double.compareTo(distance), id)
+ * order.  after_dist == after_id == NULL: no cursor, the list is tsh_search's; a cursor of -inf is "from the start";
+ * exactly one NULL is TSH_E_BAD_ARG, as are both mask forms at once and a mask handle made for another index.  So after
+ * any page, count(after = the page's last entry) is count(no cursor) minus the rows consumed so far; a caller shows
+ * "4 312 results" beside the first page, sizes the buffers of a range loop, or finds a row's position in its list.
+ * Cost: one scan, one pass over the scan's 4 B per row, and the exact distances of the few rows whose f32 key cannot
+ * tell (tostore_amd/csrc/tsh_count.hip.h, tsh_count_band.h) -- no select, no re-rank, no candidate block; the output
+ * is one integer however many rows qualify.  A count job takes the f32 tile scan or the list scan, never the exact path
+ * or the fp16 / int8 copies; several queries per call run as the pipeline of single-query scans, never on the batched
+ * path.  An empty index gives counts of 0.  Works on whole-index handles, on handles over several devices (the
+ * library sums its shards' counts) and on shard handles: there the count covers the shard's own rows under a GLOBAL
+ * mask and a GLOBAL cursor, and since the order is total across shards the caller adds the ranks' counts by whatever
+ * transport it has.  tsh_counters keeps its layout and counts a count in searches and scan_launches like any other
+ * search.  tsh_search_count_stats, summed over the shards (a count counts once per shard): */
+int32_t tsh_search_count(tsh_index *idx, const float *queries, int32_t nq, double distance_threshold,
+                         const uint8_t *row_mask, tsh_mask *mask,
+                         const double *after_dist, const int64_t *after_id, int64_t *out_count);
+/* out[0] count searches, out[1] rows sent to the side list, out[2] searches redone with a larger side list,
+ * out[3] searches answered without a device window pass (safe mode; nothing for a key to decide) */
+int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out);
 
 /* ---- row-sharded deployments (one process per GPU) ----------------------
  * Each rank scans its shard and emits, per query, one fixed-size candidate

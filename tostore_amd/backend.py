@@ -289,6 +289,40 @@ class HipVectorIndex:
         _ffi.check(_ffi.lib().tsh_search_after_stats(self._h, out))
         return {"searches": out[0], "side_rows": out[1], "redone": out[2], "no_floor": out[3]}
 
+    def search_count(self, queries, distance_threshold: Optional[float] = None, row_mask=None, after=None) -> np.ndarray:
+        """How many rows search_after() would return with k = infinity: count[nq] (int64), under the same threshold, mask
+        (None, a byte mask or a HipMask), tombstones and cursor.  after: None for the whole list -- search()'s -- or a
+        cursor as search_after() takes it; count(after = a page's last entry) is what is left past that page.  One scan
+        and a pass over its keys per query: no page is fetched."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be nq x {self.dim}")
+        nq = q.shape[0]
+        a_dist = a_id = pd = pi = None
+        if after is not None:
+            a_dist = np.ascontiguousarray(np.broadcast_to(np.asarray(after[0], dtype=np.float64).reshape(-1), (nq,)))
+            a_id = np.ascontiguousarray(np.broadcast_to(np.asarray(after[1], dtype=np.int64).reshape(-1), (nq,)))
+            pd, pi = a_dist.ctypes.data_as(_ffi.p_f64), a_id.ctypes.data_as(_ffi.p_i64)
+        cnt = np.zeros(nq, dtype=np.int64)
+        thr = math.nan if distance_threshold is None else float(distance_threshold)
+        handle, mp = None, None
+        if isinstance(row_mask, HipMask):
+            handle = row_mask.handle()
+        else:
+            row_mask, mp = self.mask_arg(row_mask)
+        _ffi.check(_ffi.lib().tsh_search_count(self._h, q.ctypes.data_as(_ffi.p_f32), nq, thr, mp, handle, pd, pi,
+                                               cnt.ctypes.data_as(_ffi.p_i64)))
+        return cnt
+
+    def search_count_stats(self) -> dict:
+        """The counts' counters, per shard search: all of them, rows sent to the side list, counts redone with a larger
+        side list, counts answered without a window pass on the device."""
+        out = (ctypes.c_int64 * 4)()
+        _ffi.check(_ffi.lib().tsh_search_count_stats(self._h, out))
+        return {"searches": out[0], "side_rows": out[1], "redone": out[2], "no_window": out[3]}
+
     # -- asynchronous single-query form (several queries in flight) -----------------
     def submit(self, query, k: int, row_mask=None, after=None) -> tuple:
         """after: a (distance, id) cursor -- the ticket answers search_after() instead of search()."""

@@ -33,6 +33,8 @@
 #include "../../include/tostore_hip.h"
 #include "tsh_after.hip.h"
 #include "tsh_after_band.h"
+#include "tsh_count.hip.h"
+#include "tsh_count_band.h"
 #include "tsh_batch.hip.h"
 #include "tsh_batch_f16.hip.h"
 #include "tsh_exact.hip.h"
@@ -270,6 +272,23 @@ inline int32_t finalize_query(int metric, int dim, const float *query, int32_t k
   return finalize_query(metric, dim, query, k, thr, lists.data(), lists.size(), out_ids, out_dist, nullptr, after);
 }
 
+// A count's share of the finaliser (tsh_search_count): how many of the entries pass the threshold and follow the cursor
+// -- finalize_query's distances and predicate (count_passes, tsh_count_band.h), no order, no cut
+int64_t count_entries(int metric, int dim, const float *query, double thr, const EntryList *lists, size_t n_lists, const Cursor *after) {
+  const double sqrt_mag_a = metric != TSH_METRIC_COSINE ? 0.0 : std::sqrt(query_mag_a(query, dim));
+  static thread_local std::vector<double> dist;
+  const bool from_start = !after || after->from_start();
+  const Hit cur = after ? after->hit() : Hit{0, 0};
+  int64_t n = 0;
+  for (size_t l = 0; l < n_lists; ++l) {
+    if (dist.size() < lists[l].second) dist.resize(lists[l].second);
+    final_distances(metric, lists[l].first, lists[l].second, sqrt_mag_a, dist.data());
+    for (uint32_t i = 0; i < lists[l].second; ++i)
+      if (count_passes(thr, from_start, cur.key, cur.id, dist[i], lists[l].first[i].id)) ++n;
+  }
+  return n;
+}
+
 // ---- kernel dispatch ---------------------------------------------------------
 inline int pick_nch(int d4) {
   int need = (d4 + 63) / 64;
@@ -322,7 +341,8 @@ struct Ctx {
   int64_t i8_tiles = 0;
   // cursor searches (tsh_after.hip.h): the side list of the rows the floor pass could not decide, its two count words
   // (side_flip: the one the next cursor job counts in -- the job before it left it at zero) and, pinned + mapped, their
-  // count and entries: [0].id = count, [1 ..] the entries
+  // count and entries: [0].id = count, [1 ..] the entries.  Count jobs (tsh_count.hip.h) use the same list and words, and a
+  // third word, d_side_cnt[2], for the rows their window pass counted (zero between jobs)
   uint32_t *d_side_rows = nullptr, *d_side_cnt = nullptr;
   BlockEntry *h_side = nullptr, *h_side_dev = nullptr;
   int64_t side_cap = 0;
@@ -488,6 +508,9 @@ struct Shard {
   // cursor searches (tsh_search_after_stats): all of them, rows their floor passes sent to the side list, searches redone
   // with a larger side list, searches answered without a floor pass (safe mode, a +inf / NaN cursor)
   std::atomic<int64_t> c_after{0}, c_after_side{0}, c_after_redone{0}, c_after_nofloor{0};
+  // counts (tsh_search_count_stats): all of them, rows their window passes sent to the side list, counts redone with a
+  // larger side list, counts answered without a window pass on the device
+  std::atomic<int64_t> c_count{0}, c_count_side{0}, c_count_redone{0}, c_count_nowindow{0};
   int cus = 0;  // compute units of the shard's device (grid of the persistent key kernels)
   std::atomic<int> f16_strikes{0};      // batched calls in a row whose fp16 bands overflowed many candidate lists
   std::atomic<int> f16_denied_calls{0};  // auto key-kernel choice: bf16x3 instead of fp16 for this many more batched calls
@@ -1142,6 +1165,14 @@ struct Job {
   Cursor after;
   AfterFloor floor;
   int side_word = 0;  // which of the context's two count words this job counts in
+  // a count job (JobReq::count): no select, no re-rank, no block.  windowed: the window pass and the side re-rank run
+  // (tsh_count.hip.h; not in safe mode, where the job is a plain search whose wide-band pass hands every live row's exact
+  // sums to the finaliser); after_skip: no row inside the model can count (CountWindow::skip), no scan runs.  A windowed
+  // job leaves the rows it counted on the device in `certain` and a side list like a cursor job's, redone the same way
+  bool counting = false, windowed = false;
+  double count_thr = 0;
+  CountWindow window;
+  int64_t certain = 0;
   const float *redo_query = nullptr;  // the caller's query (a ticket's own copy): valid until the job is finished
   std::vector<uint64_t> redo_words;   // a ticket's copy of a pointer mask's words (JobReq::mask_dies), else empty
 };
@@ -1215,7 +1246,7 @@ int ctx_reserve_list(Ctx *c, int64_t padded) {
 // the side list of a cursor job (tsh_after.hip.h): room for `want` undecided rows
 int ctx_reserve_side(Ctx *c, int64_t want) {
   if (!c->d_side_cnt) {
-    HIPCHK(hipMalloc(&c->d_side_cnt, 2 * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&c->d_side_cnt, 3 * sizeof(uint32_t)));
     c->side_dirty = true;
   }
   if (want <= c->side_cap) return TSH_OK;
@@ -1548,6 +1579,8 @@ struct JobReq {
   bool no_i8 = false;             // the redo of an int8 scan whose survivor list overflowed (with no_f16: f32)
   const Cursor *after = nullptr;  // a cursor search: only rows past it are wanted
   int64_t side_want = 0;          // ... redone after its side list overflowed: room for this many rows
+  bool count = false;             // a count (tsh_search_count): how many rows pass count_thr and follow `after`, if given
+  double count_thr = 0;           // ... its threshold (NaN: none)
   bool mask_dies = false;         // ... enqueued for a ticket: a pointer mask's words and list are gone before the job is finished
 };
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
@@ -1802,6 +1835,19 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     TSH_LAUNCH_EV(exact_pick_kernel, (unsigned)((xp.n_entries + 255) / 256), 256, ts, none, done, xp);
   } else if (j->route.exact || i8) {
     TSH_LAUNCH_EV(exact_select_kernel, 1, 1024, ts, none, done, j->xsel);
+  } else if (j->windowed) {
+    // a count job: the window pass counts the rows certainly in the list (C1), the rows it could not decide get their
+    // exact sums (C2) -- tsh_count.hip.h.  No select, no re-rank
+    const uint32_t side_cap = (uint32_t)c->side_cap;
+    uint32_t *const side_count = c->d_side_cnt + j->side_word;
+    const CountWindow &w = j->window;
+    const CountWindowArgs wa{c->d_keys, c->d_gmin, j->d_list, c->d_side_rows, side_count, c->d_side_cnt + 2, ka.se.n_tiles, side_cap,
+                             w.in_lo, w.in_hi, w.out_lo, w.out_hi};
+    count_window_kernel<<<(unsigned)((ka.se.n_tiles + 4 * COUNT_WAVE_TILES - 1) / (4 * COUNT_WAVE_TILES)), 256, 0, ts>>>(wa);
+    const CountSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->d_side_cnt + 2, c->h_side_dev,
+                           s->ld, s->row_base, s->dim, s->metric, side_cap};
+    // (the side re-rank's grid: one workgroup per row up to the re-rank's own 1024)
+    TSH_LAUNCH_EV(count_side_kernel, std::min(side_cap, 1024u), 64, ts, none, done, sd);
   } else {
     // a cursor job: the floor pass takes the rows at or before the cursor out of the select's sight (A1), and the rows
     // it could not decide get their exact sums behind the re-rank (A2) -- tsh_after.hip.h
@@ -1877,12 +1923,24 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   j->has_after = rq.after != nullptr;
   j->after_redone = rq.side_want > 0;
   if (rq.after) j->after = *rq.after;
-  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after);
+  j->counting = rq.count;
+  j->count_thr = rq.count_thr;
+  j->certain = 0;
+  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after || rq.count);
   // A cursor inside the error model gets its floor in the scan's key space (tsh_after_band.h); "from the start" has
   // none; a +inf or NaN cursor can only be followed by quarantined rows -- every row the scan offers has a finite
   // distance -- so no scan runs at all.  Safe mode: no floor, the finaliser filters.
-  j->floored = j->after_skip = false;
-  if (j->has_after && !r.band.force_all) {
+  // A count inside the error model gets its window there (tsh_count_band.h), or no scan at all where no scanned row can
+  // count.  Safe mode: a plain search job whose every live row reaches the finaliser with its exact sums.
+  j->floored = j->after_skip = j->windowed = false;
+  if (rq.count) {
+    if (!r.band.force_all) {
+      j->window = count_window(s->metric, s->dim, r.band.eps_rel, r.band.delta_abs,
+                               s->metric == TSH_METRIC_COSINE ? query_mag_a(rq.query, s->dim) : 0.0, j->has_after, j->after.dist, rq.count_thr);
+      j->after_skip = j->window.skip;
+      j->windowed = !j->window.skip;
+    }
+  } else if (j->has_after && !r.band.force_all) {
     if (!(j->after.dist < INFINITY)) {
       j->after_skip = true;
     } else {
@@ -1895,10 +1953,10 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
   if (j->after_skip) return enqueue_after_skip(s, j, rq, q);
-  if (j->floored) {
+  if (j->floored || j->windowed) {
     if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(rq.side_want, AFTER_SIDE_CAP), c->side_cap)))) return rc;
-    if (c->side_dirty) {  // (a context's first cursor job, or one after a job that failed on its way)
-      HIPCHK(hipMemsetAsync(c->d_side_cnt, 0, 2 * sizeof(uint32_t), s->aux_stream));
+    if (c->side_dirty) {  // (a context's first cursor or count job, or one after a job that failed on its way)
+      HIPCHK(hipMemsetAsync(c->d_side_cnt, 0, 3 * sizeof(uint32_t), s->aux_stream));
       HIPCHK(hipStreamSynchronize(s->aux_stream));
     }
     c->side_dirty = true;  // until this job is seen finished (job_finish)
@@ -2126,7 +2184,7 @@ int redo_overflowed_scan(Shard *s, Job *j) {
   return TSH_OK;
 }
 
-// A finished cursor job whose floor pass found more undecided rows than its side list holds (ties by the thousand) is
+// A finished cursor job whose floor pass (or count job whose window pass) found more undecided rows than its side list holds (ties by the thousand) is
 // redone once with a list sized to the count it reported: the same scan over the same rows finds the same count.
 int redo_after_side(Shard *s, Job *j) {
   Ctx *c = j->c;
@@ -2134,7 +2192,7 @@ int redo_after_side(Shard *s, Job *j) {
   const int64_t n = c->h_side[0].id;
   if (n <= c->side_cap) return TSH_OK;
   if (j->after_redone) return set_err(TSH_E_HIP, "a cursor search's side list overflowed twice (%lld rows): internal error", (long long)n);
-  s->c_after_redone++;
+  (j->counting ? s->c_count_redone : s->c_after_redone)++;
   const Cursor cur = j->after;
   JobReq rq(j->redo_query, j->k, j->entries);
   rq.mask = j->redo_mask;
@@ -2142,7 +2200,9 @@ int redo_after_side(Shard *s, Job *j) {
   rq.dev_target = j->dev_target;  // (Job::leave_overflow stays with the job)
   rq.last_of_call = true;
   rq.tag = j->tag;
-  rq.after = &cur;
+  rq.after = j->has_after ? &cur : nullptr;
+  rq.count = j->counting;
+  rq.count_thr = j->count_thr;
   rq.side_want = round_up(n, 1024);
   int rc = job_enqueue(s, j, rq);
   if (j->counted) {
@@ -2170,7 +2230,7 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     int rc = redo_overflowed_scan(s, j);
     if (rc) return rc;
   }
-  if (j->floored) {
+  if (j->floored || j->windowed) {
     int rc = redo_after_side(s, j);
     if (rc) return rc;
   }
@@ -2184,6 +2244,10 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     j->timed = false;
   }
   BlockHeader *h = reinterpret_cast<BlockHeader *>(c->h_block);
+  if (j->windowed) {  // (no kernel of a windowed count wrote the block: it is empty, the rows are in `certain` and the side list)
+    memset(h, 0, sizeof *h);
+    h->entries = (uint32_t)j->entries;
+  }
 #ifdef TSH_PROBES
   if (j->route.exact && probe_env("TSH_X2_TRACE"))
     fprintf(stderr, "[x2] keys %.2f select %.2f entries %.2f us, %u histogram rounds, %u ranked, %u out adds %.2f scan %.2f\n", h->tau_key * 0.01,
@@ -2224,18 +2288,22 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     extra->clear();
     for (uint32_t i : j->quar_sel) extra->push_back(c->h_quar[i]);
   }
-  if (j->has_after) {
+  if (j->counting) {
+    s->c_count++;
+    if (!j->windowed) s->c_count_nowindow++;
+  } else if (j->has_after) {
     s->c_after++;
     if (j->after_skip || (j->route.band.force_all && !j->after.from_start())) s->c_after_nofloor++;
   }
   if (j->floored && j->dev_target) {  // (shard mode: the side rows' entries are in the device block already)
     s->c_after_side += c->h_side[0].id;
-  } else if (j->floored) {  // the rows the floor pass could not decide join the candidates too
+  } else if (j->floored || j->windowed) {  // the rows the floor / window pass could not decide join the candidates too
     if (!extra) return set_err(TSH_E_BAD_ARG, "no room for the side list's entries");
     if (j->quar_sel.empty()) extra->clear();
     const uint32_t side_n = (uint32_t)c->h_side[0].id;
     extra->insert(extra->end(), c->h_side + 1, c->h_side + 1 + side_n);
-    s->c_after_side += side_n;
+    (j->windowed ? s->c_count_side : s->c_after_side) += side_n;
+    if (j->windowed) j->certain = (int64_t)c->h_side[0].s0;
   }
   s->c_searches++;
   return TSH_OK;
@@ -2272,6 +2340,10 @@ struct SearchOut {
   // single-query pipeline, host or device mode: a cursor per query (tsh_search_after, tsh_search_shard_after), or NULL
   const double *after_dist = nullptr;
   const int64_t *after_id = nullptr;
+  // ... host mode, a count per query (tsh_search_count): count_out[q] = the rows of this shard that pass count_thr and
+  // follow the query's cursor, if any.  No block leaves the shard (h_blocks NULL); spill / extra are needed
+  int64_t *count_out = nullptr;
+  double count_thr = 0;
 };
 
 // One submitting thread's share of a multi-query call: queries [q0, q1) of the call, at most
@@ -2318,6 +2390,8 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
         cur.id = out->after_id[q];
         rq.after = &cur;
       }
+      rq.count = out->count_out != nullptr;
+      rq.count_thr = out->count_thr;
       rc = job_enqueue(s, &j, rq);
       if (rc) {
         release_all();
@@ -2336,6 +2410,20 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       return rc;
     }
     if (out->h_blocks) memcpy(out->h_blocks + (size_t)q * bb, j.c->h_block, bb);
+    if (out->count_out) {  // the rows counted on the device, and whatever reached the host with its exact sums
+      const BlockHeader *h = reinterpret_cast<const BlockHeader *>(j.c->h_block);
+      const EntryList two[2] = {sp && !sp->empty() ? EntryList{sp->data(), (uint32_t)sp->size()}
+                                                   : EntryList{reinterpret_cast<const BlockEntry *>(j.c->h_block + sizeof(BlockHeader)),
+                                                               std::min(h->count, h->entries)},
+                                {ex ? ex->data() : nullptr, ex ? (uint32_t)ex->size() : 0u}};
+      Cursor cur;
+      if (out->after_dist) {
+        cur.dist = out->after_dist[q];
+        cur.id = out->after_id[q];
+      }
+      out->count_out[q] = j.certain + count_entries(s->metric, s->dim, queries + (size_t)q * s->dim, out->count_thr, two, 2,
+                                                    out->after_dist ? &cur : nullptr);
+    }
     ctx_release(s, j.c);
     j.c = nullptr;
     ++finished;
@@ -3001,6 +3089,86 @@ int32_t tsh_search_after_stats(tsh_index *idx, int64_t *out) {
     out[1] += sp->c_after_side.load();
     out[2] += sp->c_after_redone.load();
     out[3] += sp->c_after_nofloor.load();
+  }
+  return TSH_OK;
+}
+
+// ---- count: how many rows tsh_search_after's list holds ----------------------------------------------------------------
+int32_t tsh_search_count(tsh_index *idx, const float *queries, int32_t nq, double thr, const uint8_t *row_mask, tsh_mask *mask_h,
+                         const double *after_dist, const int64_t *after_id, int64_t *out_count) {
+  if (row_mask && mask_h) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if ((after_dist == nullptr) != (after_id == nullptr)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
+  if (nq == 0) return TSH_OK;
+  if (!queries || !out_count) return set_err(TSH_E_BAD_ARG, "queries / out_count is NULL");
+  for (int32_t q = 0; q < nq; ++q) out_count[q] = 0;
+  const size_t ns = idx->shards.size();
+  // (the block of a count job: used in safe mode only, where the job is a search for one row whose wide-band pass
+  // spills every live row)
+  const int32_t k = 1, entries = tsh_default_block_entries(k);
+  std::vector<std::vector<int64_t>> counts(ns);
+  std::vector<std::vector<std::vector<BlockEntry>>> spills(ns), extras(ns);
+  std::vector<int> rcs(ns, TSH_OK);
+  std::vector<std::string> errs(ns);
+  auto run = [&](size_t g) {
+    Shard *s = idx->shards[g].get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    if (s->rows == 0) return;
+    counts[g].assign((size_t)nq, 0);
+    spills[g].resize((size_t)nq);
+    extras[g].resize((size_t)nq);
+    SearchOut so;
+    so.spill = &spills[g];
+    so.extra = &extras[g];
+    so.after_dist = after_dist;
+    so.after_id = after_id;
+    so.count_out = counts[g].data();
+    so.count_thr = thr;
+    MaskSrc ms(row_mask);
+    if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
+      const MaskPart *mp = mask_part(mask_h, g, s, &rcs[g]);
+      if (!mp) {
+        errs[g] = g_err;
+        return;
+      }
+      ms = MaskSrc(mp);
+    }
+    // (the pipeline of single-query scans, never the batched path)
+    rcs[g] = shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
+    if (rcs[g]) errs[g] = g_err;
+  };
+  if (ns == 1) {
+    run(0);
+  } else {
+    const std::function<void(size_t)> frun = run;
+    if (!idx->workers || !idx->workers->run(frun)) {  // the workers are busy with a concurrent call: own threads
+      std::vector<std::thread> th;
+      for (size_t g = 1; g < ns; ++g) th.emplace_back(run, g);
+      run(0);
+      for (auto &t : th) t.join();
+    }
+  }
+  for (size_t g = 0; g < ns; ++g)
+    if (rcs[g]) {
+      g_err = errs[g];
+      return rcs[g];
+    }
+  for (size_t g = 0; g < ns; ++g)
+    for (size_t q = 0; q < counts[g].size(); ++q) out_count[q] += counts[g][q];
+  return TSH_OK;
+}
+
+int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  for (auto &sp : idx->shards) {
+    out[0] += sp->c_count.load();
+    out[1] += sp->c_count_side.load();
+    out[2] += sp->c_count_redone.load();
+    out[3] += sp->c_count_nowindow.load();
   }
   return TSH_OK;
 }

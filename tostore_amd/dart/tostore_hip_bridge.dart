@@ -116,6 +116,12 @@ typedef _SubmitAfterD = int Function(Pointer<Void>, Pointer<Float>, int, Pointer
     double, int, Pointer<Int32>);
 typedef _SearchAfterStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
 typedef _SearchAfterStatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchCountC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Double>, Pointer<Int64>, Pointer<Int64>);
+typedef _SearchCountD = int Function(Pointer<Void>, Pointer<Float>, int, double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Double>, Pointer<Int64>, Pointer<Int64>);
+typedef _SearchCountStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchCountStatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
@@ -356,6 +362,8 @@ final class HipVectorBackend {
   static late final _SearchAfterD _searchAfter;
   static late final _SubmitAfterD _submitAfter;
   static late final _SearchAfterStatsD _searchAfterStats;
+  static late final _SearchCountD _searchCount;
+  static late final _SearchCountStatsD _searchCountStats;
   static late final _ProbeScanI8D _probeScanI8;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
@@ -425,6 +433,9 @@ final class HipVectorBackend {
       _submitAfter = lib.lookupFunction<_SubmitAfterC, _SubmitAfterD>('tsh_search_submit_after');
       _searchAfterStats =
           lib.lookupFunction<_SearchAfterStatsC, _SearchAfterStatsD>('tsh_search_after_stats');
+      _searchCount = lib.lookupFunction<_SearchCountC, _SearchCountD>('tsh_search_count');
+      _searchCountStats =
+          lib.lookupFunction<_SearchCountStatsC, _SearchCountStatsD>('tsh_search_count_stats');
       _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
@@ -946,6 +957,63 @@ final class HipVectorBackend {
     try {
       if (_searchAfterStats(_handle, o) != 0) return null;
       return {'searches': o[0], 'sideRows': o[1], 'redone': o[2], 'noFloor': o[3]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
+  /// How many rows [searchAfter] would return with topK = infinity (tsh_search_count; no reference counterpart):
+  /// the length of the list under the same threshold, mask, tombstones and cursor.  Without `afterDistance` the list
+  /// is [search]'s; with it (and `afterNodeId`) only the rows strictly past that cursor count, so after any page
+  /// `searchCount` of its last entry is what is left.  One scan and a pass over its keys: no page is fetched.
+  /// Null on any native failure.
+  int? searchCount(Float32List query,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask, double? afterDistance, int afterNodeId = 0}) {
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchCount with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (size == 0) return 0;
+    final q = calloc<Float>(dimensions);
+    final cnt = calloc<Int64>();
+    Pointer<Double> aDist = nullptr;
+    Pointer<Int64> aId = nullptr;
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      if (afterDistance != null) {
+        aDist = calloc<Double>();
+        aId = calloc<Int64>();
+        aDist.value = afterDistance;
+        aId.value = afterNodeId;
+      }
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _searchCount(_handle, q, 1, distanceThreshold ?? double.nan, maskBytes,
+          mask != null ? mask._mask : nullptr, aDist, aId, cnt);
+      if (rc != 0) {
+        Logger.warn('tsh_search_count failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return cnt.value;
+    } finally {
+      calloc.free(q);
+      calloc.free(cnt);
+      if (aDist != nullptr) calloc.free(aDist);
+      if (aId != nullptr) calloc.free(aId);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+  }
+
+  /// The counts' counters (tsh_search_count_stats), per shard search: all of them, rows their window passes sent to
+  /// the side list, counts redone with a larger side list, counts answered without a window pass on the device.
+  Map<String, int>? searchCountStats() {
+    final o = calloc<Int64>(4);
+    try {
+      if (_searchCountStats(_handle, o) != 0) return null;
+      return {'searches': o[0], 'sideRows': o[1], 'redone': o[2], 'noWindow': o[3]};
     } finally {
       calloc.free(o);
     }
