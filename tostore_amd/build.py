@@ -22,13 +22,13 @@ CSRC = os.path.join(_HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 OUT = os.path.join(_HERE, "libtostore_hip.so")
 _HDR = os.path.join("..", "..", "include", "tostore_hip.h")
-_KERN = ["tsh_kernels.hip.h", "tsh_scan_tile.inc.h", "tsh_batch.hip.h", "tsh_launch.h", "tsh_scan_overlap.h", _HDR]
+_KERN = ["tsh_kernels.hip.h", "tsh_block.h", "tsh_scan_tile.inc.h", "tsh_batch.hip.h", "tsh_launch.h", "tsh_scan_overlap.h", _HDR]
 # translation unit -> what it includes
 UNITS = {
     "tsh_scan_tu.hip": _KERN,
     "tsh_batch_tu.hip": _KERN + ["tsh_batch_f16.hip.h", "tsh_batch_f16pp.hip.h"],
     "tsh_lib.hip": _KERN + ["tsh_batch_f16.hip.h", "tsh_batch_f16pp.hip.h", "tsh_exact.hip.h", "tsh_mask.hip.h", "tsh_host_sync.h", "tsh_pq.hip.h", "tsh_scan_f16_band.h", "tsh_scan_i8_band.h", "tsh_scan_i8.hip.h",
-                            "tsh_after.hip.h", "tsh_after_band.h", "tsh_count.hip.h", "tsh_count_band.h",
+                            "tsh_after.hip.h", "tsh_after_band.h", "tsh_count.hip.h", "tsh_count_band.h", "tsh_finalize.h",
                             "tsh_host_batch.inl.h", "tsh_host_coldstart.inl.h", "tsh_host_pq.inl.h",
                             "tsh_host_comm.inl.h"],
 }

@@ -366,12 +366,11 @@ int comm_exchange_enqueue(tsh_comm *c, const uint8_t *d_blocks, int32_t gq, int3
 // enqueued: comm_exchange_enqueue has run for this group already (stream-ordered behind the group's block writers);
 // then a rank whose scans failed cannot mark its blocks any more -- its peers see that from the blocks' generation
 // (tag: what BlockHeader.pad[1] of every block of this group must say; 0 = blocks of a synchronous shard search).
-// after_dist / after_id: the cursors of the group's queries (tsh_search_sharded_after), or both NULL.
+// after: the cursors of the group's queries (tsh_search_sharded_after), or none.
 // Collective; returns the same verdict class on every rank (own error / TSH_E_PEER / TSH_OK + need).
 int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int local_rc, const float *queries, int32_t gq,
                         int32_t k, double thr, int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count,
-                        GroupOut *go, bool enqueued = false, uint32_t tag = 0, const double *after_dist = nullptr,
-                        const int64_t *after_id = nullptr) {
+                        GroupOut *go, bool enqueued = false, uint32_t tag = 0, Cursors after = Cursors()) {
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries), W = (size_t)c->world, mine = bb * (size_t)gq;
   const bool whole = merge_whole(W, (size_t)gq);  // (same on every rank: W and gq are)
   const int32_t slice_q = whole ? gq : (int32_t)(((size_t)gq + W - 1) / W);
@@ -462,21 +461,13 @@ int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int lo
           big.resize(W);
           lp = big.data();
         }
-        for (size_t w = 0; w < W; ++w) {
-          const uint8_t *p = slice_base + w * slice_pitch + (size_t)i * bb;
-          lp[w] = {reinterpret_cast<const BlockEntry *>(p + sizeof(BlockHeader)),
-                   reinterpret_cast<const BlockHeader *>(p)->count};
-        }
+        for (size_t w = 0; w < W; ++w) lp[w] = block_list(slice_base + w * slice_pitch + (size_t)i * bb);  // (count <= entries: no `need`)
         uint8_t *r = recs + (size_t)i * rec;
         int64_t *ids = reinterpret_cast<int64_t *>(r);
         double *dd = reinterpret_cast<double *>(r + (size_t)k * 8);
         int32_t *cnt = reinterpret_cast<int32_t *>(r + (size_t)k * 16);
         Cursor cur;  // (this rank's slice and the whole group alike: the cursor of query a + i)
-        if (after_dist) {
-          cur.dist = after_dist[a + i];
-          cur.id = after_id[a + i];
-        }
-        cnt[0] = finalize_query(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, ids, dd, nullptr, after_dist ? &cur : nullptr);
+        cnt[0] = finalize_query(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, ids, dd, nullptr, after.at(a + i, &cur));
         cnt[1] = 0;
       });
     }
@@ -579,8 +570,7 @@ int comm_check_create(const void *id_or_fn, int32_t world, int32_t rank, int32_t
 }
 
 int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
-                        const uint8_t *row_mask, tsh_mask *mask_h, const double *after_dist, const int64_t *after_id,
-                        int64_t *out_ids, double *out_dist, int32_t *out_count);
+                        const CallMask &mask, Cursors after, int64_t *out_ids, double *out_dist, int32_t *out_count);
 
 }  // namespace
 
@@ -675,36 +665,35 @@ int32_t tsh_comm_get_timeline(tsh_comm *c, tsh_comm_timeline *out, int32_t reset
 
 int32_t tsh_search_sharded(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
                            const uint8_t *row_mask, int64_t *out_ids, double *out_dist, int32_t *out_count) {
-  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, nullptr, nullptr, nullptr, out_ids, out_dist, out_count);
+  return search_sharded_impl(shard, c, queries, nq, k, thr, CallMask{row_mask, nullptr}, Cursors(), out_ids, out_dist, out_count);
 }
 int32_t tsh_search_sharded_after(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
                                  const uint8_t *row_mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
                                  double *out_dist, int32_t *out_count) {
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_sharded_impl(shard, c, queries, nq, k, thr, row_mask, nullptr, after_dist, after_id, out_ids, out_dist, out_count);
+  return search_sharded_impl(shard, c, queries, nq, k, thr, CallMask{row_mask, nullptr}, Cursors{after_dist, after_id}, out_ids, out_dist, out_count);
 }
 int32_t tsh_search_sharded_masked(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
                                   tsh_mask *mask, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
                                   double *out_dist, int32_t *out_count) {
   if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
   if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_sharded_impl(shard, c, queries, nq, k, thr, nullptr, mask, after_dist, after_id, out_ids, out_dist, out_count);
+  return search_sharded_impl(shard, c, queries, nq, k, thr, CallMask{nullptr, mask}, Cursors{after_dist, after_id}, out_ids, out_dist, out_count);
 }
 
 }  // extern "C"
 
 namespace {
 
-// tsh_search_sharded; after_dist / after_id: a global cursor per query (tsh_search_sharded_after: the same on every rank,
-// like the queries), or both NULL.  A cursor call differs in three places: its groups follow the scan schedule (every
+// tsh_search_sharded; after: a global cursor per query (tsh_search_sharded_after: the same on every rank,
+// like the queries), or none.  A cursor call differs in three places: its groups follow the scan schedule (every
 // query is its own scan on every rank, whatever a rank's batch threshold says), its exchanges go out when the blocks are
 // final (a side-list redo rewrites a block after its kernels were enqueued), and every merge passes its queries' cursors.
-// mask_h: a mask handle in place of row_mask (tsh_search_sharded_masked), or NULL -- this rank's own, so a bad one is a
+// mask.handle: a mask handle in place of the bitmap (tsh_search_sharded_masked), or NULL -- this rank's own, so a bad one is a
 // local failure that travels through the exchange like a bad shard handle.
 int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
-                        const uint8_t *row_mask, tsh_mask *mask_h, const double *after_dist, const int64_t *after_id,
-                        int64_t *out_ids, double *out_dist, int32_t *out_count) {
+                        const CallMask &mask, Cursors after, int64_t *out_ids, double *out_dist, int32_t *out_count) {
   // arguments that are the same on every rank by contract are answered locally ...
   if (!c) return set_err(TSH_E_BAD_ARG, "comm is NULL");
   if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
@@ -720,7 +709,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
     local_rc = set_err(TSH_E_BAD_ARG, "needs a single-shard handle (tsh_index_create_shard)");
   else if (shard->shards[0]->device != c->device)
     local_rc = set_err(TSH_E_BAD_ARG, "shard and communicator sit on different devices");
-  else if (mask_h && mask_h->idx != shard)
+  else if (mask.handle && mask.handle->idx != shard)
     local_rc = set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
   std::string local_err = g_err;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -765,7 +754,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
     for (int32_t q = 0; q < nq; q += Gmax) sizes.push_back(std::min(Gmax, nq - q));
   } else {
     // (a cursor call: the scan schedule -- the argument is the same on every rank, which no rank's own batch flag is)
-    sharded_schedule(nq, (double)c->scan_bytes_hint / 6.5e6, &sizes, after_dist ? false : c->batch_hint);
+    sharded_schedule(nq, (double)c->scan_bytes_hint / 6.5e6, &sizes, after ? false : c->batch_hint);
   }
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
   size_t gi = 0;  // next group
@@ -786,10 +775,12 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       // (launched ahead, a group's all-gather may read a block while its rank's host still looks at it: such a
       // block is never rewritten in place -- Job::leave_overflow)
       // (never a cursor call: "enqueued" is not "final" where a side list may be redone)
-      const bool ahead = !after_dist && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
-      scan_rc = shard_stream_begin(shard, queries + (size_t)w0 * dim, wn, k, row_mask, entries, c->d_mine, sizes[gi],
-                                   /*copy_inputs=*/false, &ss, ss_tag, c->worker.get(), ahead, after_dist ? after_dist + w0 : nullptr,
-                                   after_dist ? after_id + w0 : nullptr, mask_h);
+      ShardStreamOpts opt;
+      opt.step = sizes[gi];
+      opt.tag = ss_tag;
+      opt.exec = c->worker.get();
+      opt.leave_overflow = !after && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
+      scan_rc = shard_stream_begin(shard, ShardSearchReq{queries + (size_t)w0 * dim, wn, k, entries, mask, after.from(w0), c->d_mine}, opt, &ss);
       if (scan_rc) scan_err = g_err;
     }
     auto end_stream = [&] {  // nothing of this call may still run when it returns
@@ -805,14 +796,14 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       // behind their block writers (comm_exchange_enqueue): the collective's launch costs the host tens of
       // microseconds, which would otherwise follow the last block
       bool enqueued = false;
-      if (ss && scan_rc == TSH_OK && !after_dist && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire)) {
+      if (ss && scan_rc == TSH_OK && !after && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire)) {
         const double t_e = now_us();
-        hipEvent_t after[MAX_CTX];
-        const int n_after = shard_stream_enqueued(ss, q0 + gq, after, MAX_CTX);
+        hipEvent_t behind[MAX_CTX];  // the block writers' events
+        const int n_after = shard_stream_enqueued(ss, q0 + gq, behind, MAX_CTX);
         if (n_after > 0) {
           tl.wait_scan_us += now_us() - t_e;
           const double t_l = now_us();
-          rc = comm_exchange_enqueue(c, c->d_mine + (size_t)q0 * bb, gq, entries, after, n_after);
+          rc = comm_exchange_enqueue(c, c->d_mine + (size_t)q0 * bb, gq, entries, behind, n_after);
           tl.pre_enqueue_us += now_us() - t_l;
           if (rc) {
             std::string keep = g_err;
@@ -834,7 +825,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       GroupOut go;
       rc = comm_exchange_group(c, shard, c->d_mine + (size_t)q0 * bb, scan_rc, queries + (size_t)qa * dim, gq, k, thr,
                                entries, out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, enqueued,
-                               ss_tag, after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
+                               ss_tag, after.from(qa));
       tl.groups++;
       for (int attempt = 0; rc == TSH_OK && go.need > 0; ++attempt) {
         // ties made a block overflow: every rank saw the same verdict and redoes this group with larger blocks, in a
@@ -855,8 +846,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
         std::string again_err = local_rc != TSH_OK ? local_err : scan_err;
         if (again_rc == TSH_OK) {
           const double t0 = now_us();
-          again_rc = search_shard_impl(shard, queries + (size_t)qa * dim, gq, k, row_mask, mask_h, ent, c->d_retry, nullptr,
-                                       after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
+          again_rc = search_shard_impl(shard, ShardSearchReq{queries + (size_t)qa * dim, gq, k, ent, mask, after.from(qa), c->d_retry}, nullptr);
           c->scan_ns.fetch_add((int64_t)((now_us() - t0) * 1e3), std::memory_order_relaxed);
           if (again_rc) again_err = g_err;
         }
@@ -864,8 +854,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
         if (again_rc) g_err = again_err;
         go = GroupOut();
         rc = comm_exchange_group(c, shard, c->d_retry, again_rc, queries + (size_t)qa * dim, gq, k, thr, ent,
-                                 out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, false, 0,
-                                 after_dist ? after_dist + qa : nullptr, after_dist ? after_id + qa : nullptr);
+                                 out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, false, 0, after.from(qa));
         tl.groups++;
       }
       if (rc) {

@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tsh_block.h"
+
 namespace tsh {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -577,33 +579,7 @@ __global__ void __launch_bounds__(256, 4) scan_packed_kernel(ScanArgsQ aq) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// candidate block written by K2/K3/K4 and shipped to the host (and all-gathered
-// between ranks): 64-byte header + entries x {int64 id, f64 s0, f64 s1}
-struct BlockHeader {
-  uint32_t count;      // candidates found (may exceed `entries`: overflow)
-  uint32_t entries;    // capacity of this block
-  uint32_t tau_key;    // k-th smallest tile minimum
-  uint32_t band_key;   // tau widened by the f32 error band
-  uint32_t tiles_hit;  // tiles re-read by K2
-  uint32_t flags;      // bit0: K2 list overflow (K3 fallback needed)
-  uint32_t k;
-  uint32_t metric;
-  int64_t row_base;
-  int64_t shard_rows;
-  uint32_t pad[4];     // [0]: a failed rank's status (FLAG_RANK_ERROR); [1]: the block's generation (sharded calls)
-};
-static_assert(sizeof(BlockHeader) == 64, "header is 64 bytes");
-struct BlockEntry {
-  int64_t id;
-  double s0;  // L2: sum (q-v)^2   IP: sum q*v   cosine: sum q*v
-  double s1;  // cosine: sum v*v   else 0
-};
-static_assert(sizeof(BlockEntry) == 24, "entry is 24 bytes");
-constexpr uint32_t FLAG_LIST_OVERFLOW = 1u;
-constexpr uint32_t FLAG_TAU_REFINED = 2u;  // informational: select step (f) ran
-constexpr uint32_t FLAG_TAU_UNVERIFIED = 4u;  // batched path: the estimated filter threshold was too tight (set with
-                                              // FLAG_LIST_OVERFLOW: the query is redone by the single-query path)
+// (the candidate block K2/K3/K4 write -- BlockHeader, BlockEntry, FLAG_* -- is in tsh_block.h: the host reads it too)
 
 struct SelectArgs {
   const uint32_t *gmin;

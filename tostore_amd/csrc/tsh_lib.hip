@@ -38,6 +38,7 @@
 #include "tsh_batch.hip.h"
 #include "tsh_batch_f16.hip.h"
 #include "tsh_exact.hip.h"
+#include "tsh_finalize.h"
 #include "tsh_host_sync.h"
 #include "tsh_kernels.hip.h"
 #include "tsh_launch.h"
@@ -90,204 +91,7 @@ constexpr float BIG_ABS = 1.0e15f;    // beyond this f32 squares can overflow
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// ---- Dart double.compareTo ([external] Dart SDK): NaN greatest (and equal to itself), -0 < +0 ------
-// double.compareTo as an integer order: key(a) < key(b)  <=>  dart_compare(a, b) < 0, equal keys <=> compareTo == 0
-// (every NaN maps to the one largest key; -0.0 sorts just below +0.0).  Sorting (key, id) pairs with integer
-// compares is what the finaliser does for every query.
-// (the function itself lives in tsh_after_band.h, host only, where tests/cpp/after_band_test.cpp holds it to the order)
-inline uint64_t dart_order_key(double d) { return after_order_key(d); }
-struct Hit {
-  uint64_t key;  // dart_order_key(distance)
-  int64_t id;
-};
-inline bool hit_less(const Hit &a, const Hit &b) { return a.key != b.key ? a.key < b.key : a.id < b.id; }
-// The cursor of a search-after (tsh_search_after): the last (distance, id) the caller saw.  A row follows it iff its
-// (order key, id) is strictly greater
-struct Cursor {
-  double dist = 0;
-  int64_t id = 0;
-  Hit hit() const { return Hit{dart_order_key(dist), id}; }
-  bool from_start() const { return dist == -INFINITY; }  // "-inf with any id": nothing is at or before it
-};
-// Ascending by (key, id).  A query's candidates are k plus a band's worth of rows whose distances share their
-// leading bits, and std::sort spends 3-4 us on 127 of them (two thirds of a query's finalisation, mostly
-// mispredicted branches): one counting pass over 512 buckets of the key RANGE (a shift, so the bucket is monotone in
-// the key) leaves runs of a few entries to put in order -- 1 us.  Ties, NaNs or a wild range only mean longer runs.
-inline void sort_hits(Hit *h, size_t n) {
-  constexpr int BITS = 9, NB = 1 << BITS;
-  if (n < 24 || n > 60000) {
-    std::sort(h, h + n, hit_less);
-    return;
-  }
-  static thread_local std::vector<Hit> tmp;
-  static thread_local std::vector<uint16_t> bucket;
-  if (tmp.size() < n) {
-    tmp.resize(n);
-    bucket.resize(n);
-  }
-  uint64_t kmin = ~0ull, kmax = 0;
-  for (size_t i = 0; i < n; ++i) {
-    kmin = std::min(kmin, h[i].key);
-    kmax = std::max(kmax, h[i].key);
-  }
-  const uint64_t range = kmax - kmin;
-  const int shift = range < (uint64_t)NB ? 0 : (64 - __builtin_clzll(range)) - BITS;  // (range >> shift) < NB
-  uint16_t pos[NB + 1];
-  memset(pos, 0, sizeof(pos));
-  for (size_t i = 0; i < n; ++i) {
-    const uint16_t b = (uint16_t)((h[i].key - kmin) >> shift);
-    bucket[i] = b;
-    pos[b + 1]++;
-  }
-  for (int b = 0; b < NB; ++b) pos[b + 1] += pos[b];
-  for (size_t i = 0; i < n; ++i) tmp[pos[bucket[i]]++] = h[i];
-  size_t start = 0;
-  for (size_t i = 1; i <= n; ++i) {
-    if (i < n && ((tmp[i].key - kmin) >> shift) == ((tmp[start].key - kmin) >> shift)) continue;
-    const size_t len = i - start;  // a bucket's run
-    if (len > 12) {
-      std::sort(tmp.begin() + start, tmp.begin() + i, hit_less);
-    } else {
-      for (size_t a = start + 1; a < i; ++a) {
-        const Hit x = tmp[a];
-        size_t j = a;
-        for (; j > start && hit_less(x, tmp[j - 1]); --j) tmp[j] = tmp[j - 1];
-        tmp[j] = x;
-      }
-    }
-    start = i;
-  }
-  memcpy(h, tmp.data(), n * sizeof(Hit));
-}
-// the distance an order key stands for (every NaN comes back as the one quiet NaN)
-inline double dart_order_key_to_double(uint64_t key) {
-  if (key == ~0ull) return std::nan("");
-  const uint64_t b = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-  double d;
-  memcpy(&d, &b, 8);
-  return d;
-}
-
-// Final per-candidate arithmetic of ngh_graph_engine.dart:908-946 given the exact f64 sums (L2 :926 sqrt(s0);
-// IP :914 -s0; cosine :944-945,:916 1 - s0 / (sqrt(mag_a) * sqrt(s1)), similarity 0 when the denominator is not
-// positive), mag_a = sum q[i]*q[i] accumulated in element order --
-// over a whole list: a plain loop over arrays, so the compiler's vector square roots and
-// divisions (IEEE-exact, like the scalar ones; no contraction: -ffp-contract=off) do four or eight at a time on
-// hosts that have AVX2 / AVX-512 -- the square root and the division were a third of a query's finalisation.
-#define TSH_FINAL_KEYS_BODY                                                                   \
-  for (uint32_t i = 0; i < n; ++i) {                                                          \
-    const double s0 = e[i].s0, s1 = e[i].s1;                                                  \
-    double d;                                                                                 \
-    if (metric == TSH_METRIC_L2) {                                                            \
-      d = std::sqrt(s0);                                                                      \
-    } else if (metric == TSH_METRIC_IP) {                                                     \
-      d = -s0;                                                                                \
-    } else {                                                                                  \
-      const double denom = sqrt_mag_a * std::sqrt(s1);                                        \
-      const double sim = denom > 0 ? s0 / denom : 0;                                          \
-      d = 1.0 - sim;                                                                          \
-    }                                                                                         \
-    dist[i] = d;                                                                              \
-  }
-#if defined(__x86_64__)
-__attribute__((target("avx2"))) void final_distances_avx2(int metric, const BlockEntry *e, uint32_t n, double sqrt_mag_a,
-                                                          double *dist) {
-  TSH_FINAL_KEYS_BODY
-}
-#endif
-void final_distances_base(int metric, const BlockEntry *e, uint32_t n, double sqrt_mag_a, double *dist) {
-  TSH_FINAL_KEYS_BODY
-}
-#undef TSH_FINAL_KEYS_BODY
-inline void final_distances(int metric, const BlockEntry *e, uint32_t n, double sqrt_mag_a, double *dist) {
-#if defined(__x86_64__)
-  static const bool avx2 = __builtin_cpu_supports("avx2");
-  if (avx2) return final_distances_avx2(metric, e, n, sqrt_mag_a, dist);
-#endif
-  final_distances_base(metric, e, n, sqrt_mag_a, dist);
-}
-
-double query_mag_a(const float *q, int dim) {
-#pragma clang fp contract(off)
-  double m = 0;
-  for (int i = 0; i < dim; ++i) m = m + (double)q[i] * (double)q[i];
-  return m;
-}
-
-// threshold + order + cut of ngh_graph_engine.dart:127,133-134 over candidate
-// entries from any number of blocks.  mag_a: query_mag_a(query) when the caller has it already (the batched path
-// computes it while it prepares the queries), else nullptr.  after: a cursor search's cursor -- entries at or before it
-// are dropped first, wherever they came from -- else nullptr.
-typedef std::pair<const BlockEntry *, uint32_t> EntryList;
-int32_t finalize_query(int metric, int dim, const float *query, int32_t k, double thr, const EntryList *lists_p,
-                       size_t n_lists, int64_t *out_ids, double *out_dist, const double *mag_a_known = nullptr,
-                       const Cursor *after = nullptr) {
-  struct {
-    const EntryList *b, *e;
-    const EntryList *begin() const { return b; }
-    const EntryList *end() const { return e; }
-  } lists{lists_p, lists_p + n_lists};
-  const double mag_a = metric != TSH_METRIC_COSINE ? 0.0 : (mag_a_known ? *mag_a_known : query_mag_a(query, dim));
-  const double sqrt_mag_a = std::sqrt(mag_a);
-  static thread_local std::vector<Hit> hits;  // (one allocation per thread, not per query)
-  static thread_local std::vector<double> dist;
-  hits.clear();
-  size_t total = 0;
-  for (auto &l : lists) total += l.second;
-  hits.reserve(total);
-  const bool has_thr = !std::isnan(thr);
-  if (after && after->from_start()) after = nullptr;
-  const Hit cur = after ? after->hit() : Hit{0, 0};
-  for (auto &l : lists) {
-    if (dist.size() < l.second) dist.resize(l.second);
-    final_distances(metric, l.first, l.second, sqrt_mag_a, dist.data());
-    for (uint32_t i = 0; i < l.second; ++i) {
-      const double d = dist[i];
-      const Hit h{dart_order_key(d), l.first[i].id};
-      if (after && !after_follows(cur.key, cur.id, h.key, h.id)) continue;
-      if (has_thr && d > thr) continue;
-      hits.push_back(h);
-    }
-  }
-  size_t r = std::min<size_t>(hits.size(), (size_t)std::max(k, 0));
-  if (hits.size() <= 4 * r) {  // the usual case (k + a band's worth of candidates): one sort is cheapest
-    sort_hits(hits.data(), hits.size());
-  } else {
-    std::nth_element(hits.begin(), hits.begin() + r, hits.end(), hit_less);
-    std::sort(hits.begin(), hits.begin() + r, hit_less);
-  }
-  for (size_t i = 0; i < r; ++i) {
-    out_ids[i] = hits[i].id;
-    out_dist[i] = dart_order_key_to_double(hits[i].key);
-  }
-  for (size_t i = r; i < (size_t)std::max(k, 0); ++i) {  // unused slots read as "no row" (callers need not pre-fill)
-    out_ids[i] = -1;
-    out_dist[i] = std::nan("");
-  }
-  return (int32_t)r;
-}
-inline int32_t finalize_query(int metric, int dim, const float *query, int32_t k, double thr,
-                              const std::vector<EntryList> &lists, int64_t *out_ids, double *out_dist,
-                              const Cursor *after = nullptr) {
-  return finalize_query(metric, dim, query, k, thr, lists.data(), lists.size(), out_ids, out_dist, nullptr, after);
-}
-
-// A count's share of the finaliser (tsh_search_count): how many of the entries pass the threshold and follow the cursor
-// -- finalize_query's distances and predicate (count_passes, tsh_count_band.h), no order, no cut
-int64_t count_entries(int metric, int dim, const float *query, double thr, const EntryList *lists, size_t n_lists, const Cursor *after) {
-  const double sqrt_mag_a = metric != TSH_METRIC_COSINE ? 0.0 : std::sqrt(query_mag_a(query, dim));
-  static thread_local std::vector<double> dist;
-  const bool from_start = !after || after->from_start();
-  const Hit cur = after ? after->hit() : Hit{0, 0};
-  int64_t n = 0;
-  for (size_t l = 0; l < n_lists; ++l) {
-    if (dist.size() < lists[l].second) dist.resize(lists[l].second);
-    final_distances(metric, lists[l].first, lists[l].second, sqrt_mag_a, dist.data());
-    for (uint32_t i = 0; i < lists[l].second; ++i)
-      if (count_passes(thr, from_start, cur.key, cur.id, dist[i], lists[l].first[i].id)) ++n;
-  }
-  return n;
-}
+// (the finaliser -- Hit, Cursor, Cursors, sort_hits, finalize_query, count_entries -- is in tsh_finalize.h: host only, CPU-tested)
 
 // ---- kernel dispatch ---------------------------------------------------------
 inline int pick_nch(int d4) {
@@ -2309,6 +2113,31 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   return TSH_OK;
 }
 
+// An enqueued job that will not be finished (something else of its call failed): settled -- its kernels have run out and
+// it no longer counts in Shard::inflight -- and then abandoned, its context back in the pool
+inline void job_settle(Shard *s, Job *j) {
+  if (!j->counted) return;
+  hipEventSynchronize(j->c->ev_done);
+  s->inflight.fetch_sub(1);
+  j->counted = false;
+}
+inline void job_abandon(Shard *s, Job *j) {
+  if (!j->c) return;
+  job_settle(s, j);
+  ctx_release(s, j->c);
+  j->c = nullptr;
+}
+
+// One shard's candidates of one query, as the finaliser takes them: the spill if the wide-band pass made one, else the
+// block's own entries, then the extra entries (quarantined rows, a side list) if there are any.  -> lists written
+inline size_t shard_lists(const uint8_t *block, const std::vector<BlockEntry> *spill, const std::vector<BlockEntry> *extra,
+                          EntryList out[2]) {
+  size_t n = 0;
+  out[n++] = spill && !spill->empty() ? EntryList{spill->data(), (uint32_t)spill->size()} : block_list(block);
+  if (extra && !extra->empty()) out[n++] = EntryList{extra->data(), (uint32_t)extra->size()};
+  return n;
+}
+
 struct SearchOut {
   uint8_t *h_blocks = nullptr;  // host mode: nq blocks (caller memory)
   std::vector<std::vector<BlockEntry>> *spill = nullptr;
@@ -2337,9 +2166,8 @@ struct SearchOut {
   std::function<void(int32_t q, hipEvent_t done, hipStream_t where, uint64_t seq)> on_enqueued;
   uint32_t tag = 0;  // generation stamped into the blocks' headers (BlockHeader.pad[1])
   bool leave_overflow = false;  // device mode: see Job::leave_overflow
-  // single-query pipeline, host or device mode: a cursor per query (tsh_search_after, tsh_search_shard_after), or NULL
-  const double *after_dist = nullptr;
-  const int64_t *after_id = nullptr;
+  // single-query pipeline, host or device mode: a cursor per query (tsh_search_after, tsh_search_shard_after), or none
+  Cursors after;
   // ... host mode, a count per query (tsh_search_count): count_out[q] = the rows of this shard that pass count_thr and
   // follow the query's cursor, if any.  No block leaves the shard (h_blocks NULL); spill / extra are needed
   int64_t *count_out = nullptr;
@@ -2359,14 +2187,7 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
   int rc = TSH_OK;
   int32_t submitted = 0, finished = 0;
   auto release_all = [&]() {
-    for (auto &j : jobs)
-      if (j.c) {
-        if (j.counted) hipEventSynchronize(j.c->ev_done);
-        if (j.counted) s->inflight.fetch_sub(1);
-        j.counted = false;
-        ctx_release(s, j.c);
-        j.c = nullptr;
-      }
+    for (auto &j : jobs) job_abandon(s, &j);
   };
   while (finished < cnt) {
     while (submitted < cnt && submitted - finished < depth) {
@@ -2385,11 +2206,7 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       rq.last_of_call = cnt > 1 && submitted == cnt - 1;
       rq.tag = out->tag;
       Cursor cur;
-      if (out->after_dist) {
-        cur.dist = out->after_dist[q];
-        cur.id = out->after_id[q];
-        rq.after = &cur;
-      }
+      rq.after = out->after.at(q, &cur);
       rq.count = out->count_out != nullptr;
       rq.count_thr = out->count_thr;
       rc = job_enqueue(s, &j, rq);
@@ -2411,18 +2228,11 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
     }
     if (out->h_blocks) memcpy(out->h_blocks + (size_t)q * bb, j.c->h_block, bb);
     if (out->count_out) {  // the rows counted on the device, and whatever reached the host with its exact sums
-      const BlockHeader *h = reinterpret_cast<const BlockHeader *>(j.c->h_block);
-      const EntryList two[2] = {sp && !sp->empty() ? EntryList{sp->data(), (uint32_t)sp->size()}
-                                                   : EntryList{reinterpret_cast<const BlockEntry *>(j.c->h_block + sizeof(BlockHeader)),
-                                                               std::min(h->count, h->entries)},
-                                {ex ? ex->data() : nullptr, ex ? (uint32_t)ex->size() : 0u}};
+      EntryList two[2];
+      const size_t n_lists = shard_lists(j.c->h_block, sp, ex, two);
       Cursor cur;
-      if (out->after_dist) {
-        cur.dist = out->after_dist[q];
-        cur.id = out->after_id[q];
-      }
-      out->count_out[q] = j.certain + count_entries(s->metric, s->dim, queries + (size_t)q * s->dim, out->count_thr, two, 2,
-                                                    out->after_dist ? &cur : nullptr);
+      out->count_out[q] = j.certain + count_entries(s->metric, s->dim, queries + (size_t)q * s->dim, out->count_thr, two, n_lists,
+                                                    out->after.at(q, &cur));
     }
     ctx_release(s, j.c);
     j.c = nullptr;
@@ -2749,6 +2559,87 @@ const MaskPart *mask_part(tsh_mask *m, size_t g, Shard *s, int *rc) {
   return p;
 }
 
+// The mask of a call, as the entries get it: the caller's global bitmap, or a mask handle, or neither
+struct CallMask {
+  const uint8_t *bytes = nullptr;
+  tsh_mask *handle = nullptr;
+};
+// ... and what shard g's searches take of it: the handle's part for this shard -- resident, rebuilt here if the shard grew
+// since -- else the pointer form.  Caller holds s->mu shared and has checked that the handle was made for this index
+inline int call_mask_for_shard(const CallMask &m, size_t g, Shard *s, MaskSrc *out) {
+  *out = MaskSrc(m.bytes);
+  if (!m.handle) return TSH_OK;
+  int rc = TSH_OK;
+  const MaskPart *mp = mask_part(m.handle, g, s, &rc);
+  if (!mp) return rc;
+  *out = MaskSrc(mp);
+  return TSH_OK;
+}
+
+// What the shard-level entries are asked (tsh_search_shard*, tsh_search_shard_begin*, the sharded search's windows, groups
+// and retries): nq queries, the call's mask, a cursor per query or none, nq blocks of `entries` entries on the device.  A
+// further per-query input is added here and in Cursors
+struct ShardSearchReq {
+  const float *queries = nullptr;
+  int32_t nq = 0, k = 0, entries = 0;
+  CallMask mask;
+  Cursors after;
+  uint8_t *d_blocks = nullptr;
+};
+// ... and how a progressive one (shard_stream_begin) is to run
+struct ShardStreamOpts {
+  int32_t step = 0;            // matrix-core route: queries per batched call (0: all in one)
+  bool copy_inputs = false;    // public entry points: the caller's arrays are consumed before begin returns
+  uint32_t tag = 0;            // generation the blocks carry (BlockHeader.pad[1])
+  OneWorker *exec = nullptr;   // the caller's persistent thread in place of the search's own (tsh_search_sharded: starting a
+                               // thread costs a 20-query call on a 125 k-row shard 30-40 us before its first scan is enqueued)
+  bool leave_overflow = false;  // the caller enqueues its exchange ahead of the blocks (Job::leave_overflow)
+};
+
+// fn(g) -> status, for every shard of the handle side by side: one shard inline, else the handle's workers.  -> the first
+// failing shard's status, with that shard's error text in g_err
+template <typename F>
+int for_each_shard(tsh_index *idx, F fn) {
+  const size_t ns = idx->shards.size();
+  if (ns == 1) return fn((size_t)0);
+  std::vector<int> rcs(ns, TSH_OK);
+  std::vector<std::string> errs(ns);
+  auto run = [&](size_t g) {
+    rcs[g] = fn(g);
+    if (rcs[g]) errs[g] = g_err;
+  };
+  const std::function<void(size_t)> frun = run;
+  if (!idx->workers || !idx->workers->run(frun)) {  // the workers are busy with a concurrent call: own threads
+    std::vector<std::thread> th;
+    for (size_t g = 1; g < ns; ++g) th.emplace_back(run, g);
+    run(0);
+    for (auto &t : th) t.join();
+  }
+  for (size_t g = 0; g < ns; ++g)
+    if (rcs[g]) {
+      g_err = errs[g];
+      return rcs[g];
+    }
+  return TSH_OK;
+}
+
+// nq empty blocks (an empty shard's contribution to a shard-level search), written to the device
+int write_empty_blocks(Shard *s, int32_t nq, int32_t k, int32_t entries, uint32_t tag, uint8_t *d_blocks) {
+  HIPCHK(hipSetDevice(s->device));
+  const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
+  std::vector<uint8_t> z(bb * (size_t)nq, 0);
+  for (int32_t q = 0; q < nq; ++q) {
+    BlockHeader *h = reinterpret_cast<BlockHeader *>(z.data() + (size_t)q * bb);
+    h->entries = (uint32_t)entries;
+    h->k = (uint32_t)k;
+    h->metric = (uint32_t)s->metric;
+    h->row_base = s->row_base;
+    h->pad[1] = tag;
+  }
+  HIPCHK(hipMemcpy(d_blocks, z.data(), z.size(), hipMemcpyHostToDevice));
+  return TSH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2925,12 +2816,11 @@ int32_t tsh_default_block_entries(int32_t k) {
   return (int32_t)std::min<int64_t>(e, 1 << 20);
 }
 
-// after_dist / after_id: a cursor per query (tsh_search_after), or both NULL
-static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr,
-                           const uint8_t *row_mask, tsh_mask *mask_h, int64_t *out_ids, double *out_dist,
-                           int32_t *out_count, const double *after_dist = nullptr, const int64_t *after_id = nullptr) {
+// after: a cursor per query (tsh_search_after), or none
+static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const CallMask &mask,
+                           int64_t *out_ids, double *out_dist, int32_t *out_count, Cursors after = Cursors()) {
   if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
-  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (mask.handle && mask.handle->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
   if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
   if (nq == 0) return TSH_OK;
   if (!queries || !out_count) return set_err(TSH_E_BAD_ARG, "queries / out_count is NULL");
@@ -2954,15 +2844,13 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
     }
   } give_back{idx, &blocks, &block_caps};
   std::vector<std::vector<std::vector<BlockEntry>>> spills(ns), extras(ns);
-  std::vector<int> rcs(ns, TSH_OK);
-  std::vector<std::string> errs(ns);
   std::vector<char> active(ns, 0);
   std::vector<char> finalized((size_t)nq, 0);  // done early by the batched path's chunk callback
 
-  auto run = [&](size_t g) {
+  int rc = for_each_shard(idx, [&](size_t g) -> int {
     Shard *s = idx->shards[g].get();
     std::shared_lock<RwLock> sl = share(idx, s);
-    if (s->rows == 0) return;
+    if (s->rows == 0) return TSH_OK;
     active[g] = 1;
     blocks[g] = idx->take_blocks(bb * (size_t)nq, &block_caps[g]);
     spills[g].resize((size_t)nq);
@@ -2971,24 +2859,19 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
     so.h_blocks = blocks[g].get();
     so.spill = &spills[g];
     so.extra = &extras[g];
-    so.after_dist = after_dist;
-    so.after_id = after_id;
-    if (ns == 1 && !after_dist)  // batched path: finalise a chunk of queries while the GPU still works on the next one
+    so.after = after;
+    if (ns == 1 && !after)  // batched path: finalise a chunk of queries while the GPU still works on the next one
       so.on_chunk = [&](int32_t q0, int32_t q1, const char *skip, const uint8_t *base, const double *mag_a) {
         parallel_for_range(q0, q1, [&](int32_t q) {
           if (skip[q]) return;
-          const uint8_t *b = base + (size_t)q * bb;
-          const BlockHeader *h = reinterpret_cast<const BlockHeader *>(b);
-          const std::vector<BlockEntry> &ex = extras[0][(size_t)q];
-          const EntryList two[2] = {
-              {reinterpret_cast<const BlockEntry *>(b + sizeof(BlockHeader)), std::min(h->count, h->entries)},
-              {ex.data(), (uint32_t)ex.size()}};
+          EntryList two[2];
+          const size_t n_lists = shard_lists(base + (size_t)q * bb, nullptr, &extras[0][(size_t)q], two);
           out_count[q] = finalize_query(idx->metric, idx->dim, queries + (size_t)q * idx->dim, k, thr, two,
-                                        ex.empty() ? 1 : 2, out_ids + (size_t)q * k, out_dist + (size_t)q * k, mag_a + q);
+                                        n_lists, out_ids + (size_t)q * k, out_dist + (size_t)q * k, mag_a + q);
           finalized[(size_t)q] = 1;
         });
       };
-    if (ns == 1 && !after_dist) {
+    if (ns == 1 && !after) {
       so.fin_thr = thr;
       so.on_final = [&](int32_t q0, int32_t q1, const char *skip, const int64_t *ids, const double *dist, const int32_t *cnt) {
         parallel_for_range(q0, q1, [&](int32_t q) {
@@ -3000,62 +2883,29 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
         });
       };
     }
-    MaskSrc ms(row_mask);
-    if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
-      const MaskPart *mp = mask_part(mask_h, g, s, &rcs[g]);
-      if (!mp) {
-        errs[g] = g_err;
-        return;
-      }
-      ms = MaskSrc(mp);
-    }
+    MaskSrc ms;
+    int mrc = call_mask_for_shard(mask, g, s, &ms);
+    if (mrc) return mrc;
     // (cursor searches: the pipeline of single-query scans, never the batched path)
-    rcs[g] = after_dist ? shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH)
-                        : shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, ms, entries, &so);
-    if (rcs[g]) errs[g] = g_err;
-  };
-  if (ns == 1) {
-    run(0);
-  } else {
-    const std::function<void(size_t)> frun = run;
-    if (!idx->workers || !idx->workers->run(frun)) {  // the workers are busy with a concurrent call: own threads
-      std::vector<std::thread> th;
-      for (size_t g = 1; g < ns; ++g) th.emplace_back(run, g);
-      run(0);
-      for (auto &t : th) t.join();
-    }
-  }
-  for (size_t g = 0; g < ns; ++g)
-    if (rcs[g]) {
-      g_err = errs[g];
-      return rcs[g];
-    }
+    return after ? shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH)
+                 : shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, ms, entries, &so);
+  });
+  if (rc) return rc;
   const double t_shards = now_us();
   // (the batched path's chunk callback has usually done everything: waking the pool for nothing cost 30-50 us)
   const bool all_done = std::find(finalized.begin(), finalized.end(), (char)0) == finalized.end();
   if (!all_done) parallel_for(nq, [&](int32_t q) {
     if (finalized[(size_t)q]) return;
-    std::vector<std::pair<const BlockEntry *, uint32_t>> lists;
+    std::vector<EntryList> lists;
     for (size_t g = 0; g < ns; ++g) {
       if (!active[g]) continue;
-      if (!spills[g][(size_t)q].empty()) {
-        lists.push_back({spills[g][(size_t)q].data(), (uint32_t)spills[g][(size_t)q].size()});
-      } else {
-        const uint8_t *b = blocks[g].get() + (size_t)q * bb;
-        const BlockHeader *h = reinterpret_cast<const BlockHeader *>(b);
-        lists.push_back({reinterpret_cast<const BlockEntry *>(b + sizeof(BlockHeader)),
-                         std::min(h->count, h->entries)});
-      }
-      const std::vector<BlockEntry> &ex = extras[g][(size_t)q];
-      if (!ex.empty()) lists.push_back({ex.data(), (uint32_t)ex.size()});
+      EntryList two[2];
+      const size_t n_lists = shard_lists(blocks[g].get() + (size_t)q * bb, &spills[g][(size_t)q], &extras[g][(size_t)q], two);
+      lists.insert(lists.end(), two, two + n_lists);
     }
     Cursor cur;
-    if (after_dist) {
-      cur.dist = after_dist[q];
-      cur.id = after_id[q];
-    }
     out_count[q] = finalize_query(idx->metric, idx->dim, queries + (size_t)q * idx->dim, k, thr, lists,
-                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k, after_dist ? &cur : nullptr);
+                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k, after.at(q, &cur));
   });
   if (trace_batch() && nq >= 64)
     fprintf(stderr, "[tsh search] nq=%d shards %.0f us, finalize %.0f us\n", nq, t_shards - t_in, now_us() - t_shards);
@@ -3064,12 +2914,12 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
 
 int32_t tsh_search(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr,
                    const uint8_t *row_mask, int64_t *out_ids, double *out_dist, int32_t *out_count) {
-  return search_impl(idx, queries, nq, k, thr, row_mask, nullptr, out_ids, out_dist, out_count);
+  return search_impl(idx, queries, nq, k, thr, CallMask{row_mask, nullptr}, out_ids, out_dist, out_count);
 }
 
 int32_t tsh_search_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, tsh_mask *mask,
                           int64_t *out_ids, double *out_dist, int32_t *out_count) {
-  return search_impl(idx, queries, nq, k, thr, nullptr, mask, out_ids, out_dist, out_count);
+  return search_impl(idx, queries, nq, k, thr, CallMask{nullptr, mask}, out_ids, out_dist, out_count);
 }
 
 int32_t tsh_search_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const uint8_t *row_mask,
@@ -3078,7 +2928,7 @@ int32_t tsh_search_after(tsh_index *idx, const float *queries, int32_t nq, int32
   if (row_mask && mask) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_impl(idx, queries, nq, k, thr, row_mask, mask, out_ids, out_dist, out_count, after_dist, after_id);
+  return search_impl(idx, queries, nq, k, thr, CallMask{row_mask, mask}, out_ids, out_dist, out_count, Cursors{after_dist, after_id});
 }
 
 int32_t tsh_search_after_stats(tsh_index *idx, int64_t *out) {
@@ -3097,7 +2947,7 @@ int32_t tsh_search_after_stats(tsh_index *idx, int64_t *out) {
 int32_t tsh_search_count(tsh_index *idx, const float *queries, int32_t nq, double thr, const uint8_t *row_mask, tsh_mask *mask_h,
                          const double *after_dist, const int64_t *after_id, int64_t *out_count) {
   if (row_mask && mask_h) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
-  if ((after_dist == nullptr) != (after_id == nullptr)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
+  if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
   if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
   if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
@@ -3111,51 +2961,26 @@ int32_t tsh_search_count(tsh_index *idx, const float *queries, int32_t nq, doubl
   const int32_t k = 1, entries = tsh_default_block_entries(k);
   std::vector<std::vector<int64_t>> counts(ns);
   std::vector<std::vector<std::vector<BlockEntry>>> spills(ns), extras(ns);
-  std::vector<int> rcs(ns, TSH_OK);
-  std::vector<std::string> errs(ns);
-  auto run = [&](size_t g) {
+  int rc = for_each_shard(idx, [&](size_t g) -> int {
     Shard *s = idx->shards[g].get();
     std::shared_lock<RwLock> sl = share(idx, s);
-    if (s->rows == 0) return;
+    if (s->rows == 0) return TSH_OK;
     counts[g].assign((size_t)nq, 0);
     spills[g].resize((size_t)nq);
     extras[g].resize((size_t)nq);
     SearchOut so;
     so.spill = &spills[g];
     so.extra = &extras[g];
-    so.after_dist = after_dist;
-    so.after_id = after_id;
+    so.after = Cursors{after_dist, after_id};
     so.count_out = counts[g].data();
     so.count_thr = thr;
-    MaskSrc ms(row_mask);
-    if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
-      const MaskPart *mp = mask_part(mask_h, g, s, &rcs[g]);
-      if (!mp) {
-        errs[g] = g_err;
-        return;
-      }
-      ms = MaskSrc(mp);
-    }
+    MaskSrc ms;
+    int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
+    if (mrc) return mrc;
     // (the pipeline of single-query scans, never the batched path)
-    rcs[g] = shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
-    if (rcs[g]) errs[g] = g_err;
-  };
-  if (ns == 1) {
-    run(0);
-  } else {
-    const std::function<void(size_t)> frun = run;
-    if (!idx->workers || !idx->workers->run(frun)) {  // the workers are busy with a concurrent call: own threads
-      std::vector<std::thread> th;
-      for (size_t g = 1; g < ns; ++g) th.emplace_back(run, g);
-      run(0);
-      for (auto &t : th) t.join();
-    }
-  }
-  for (size_t g = 0; g < ns; ++g)
-    if (rcs[g]) {
-      g_err = errs[g];
-      return rcs[g];
-    }
+    return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
+  });
+  if (rc) return rc;
   for (size_t g = 0; g < ns; ++g)
     for (size_t q = 0; q < counts[g].size(); ++q) out_count[q] += counts[g][q];
   return TSH_OK;
@@ -3283,12 +3108,9 @@ static int32_t submit_impl(tsh_index *idx, const float *query, int32_t k, const 
     t->jobs[g].c = c;
     std::vector<uint64_t> words;
     std::vector<uint32_t> list_ids;  // (job_enqueue copies what it keeps of either before it returns)
-    MaskSrc src(row_mask);
-    if (mask_h) {
-      const MaskPart *mp = mask_part(mask_h, g, s, &rc);
-      if (!mp) break;
-      src = MaskSrc(mp);
-    }
+    MaskSrc src;
+    rc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &src);
+    if (rc) break;
     JobReq rq(t->query.data(), k, t->entries);  // (the ticket's copy: a cursor job may be redone from it at the wait)
     rq.mask = resolve_mask(s, src, k, t->entries, &words, &list_ids);
     rq.after = after;
@@ -3297,12 +3119,7 @@ static int32_t submit_impl(tsh_index *idx, const float *query, int32_t k, const 
   }
   if (rc != TSH_OK) {
     std::string keep = g_err;
-    for (size_t g = 0; g < idx->shards.size(); ++g)
-      if (t->jobs[g].c) {
-        if (t->jobs[g].counted) hipEventSynchronize(t->jobs[g].c->ev_done);
-        if (t->jobs[g].counted) idx->shards[g]->inflight.fetch_sub(1);
-        ctx_release(idx->shards[g].get(), t->jobs[g].c);
-      }
+    for (size_t g = 0; g < idx->shards.size(); ++g) job_abandon(idx->shards[g].get(), &t->jobs[g]);
     g_err = keep;
     return rc;
   }
@@ -3335,9 +3152,7 @@ int32_t tsh_search_submit_after(tsh_index *idx, const float *query, int32_t k, c
   if (row_mask && mask) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
   Cursor cur;
-  cur.dist = after_dist;
-  cur.id = after_id;
-  return submit_impl(idx, query, k, row_mask, mask, out_ticket, &cur);
+  return submit_impl(idx, query, k, row_mask, mask, out_ticket, Cursors{&after_dist, &after_id}.at(0, &cur));
 }
 
 int32_t tsh_search_ready(tsh_index *idx, int32_t ticket) {
@@ -3370,7 +3185,7 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double thr, int64_t *out
   *out_count = 0;
   int rc = TSH_OK;
   std::vector<std::vector<BlockEntry>> spills(idx->shards.size()), extras(idx->shards.size());
-  std::vector<std::pair<const BlockEntry *, uint32_t>> lists;
+  std::vector<EntryList> lists;
   for (size_t g = 0; g < idx->shards.size(); ++g) {
     Job &j = t->jobs[g];
     if (!j.c) continue;
@@ -3378,92 +3193,65 @@ int32_t tsh_search_wait(tsh_index *idx, int32_t ticket, double thr, int64_t *out
     if (rc == TSH_OK) {
       rc = job_finish(s, &j, &spills[g], &extras[g]);
     } else {
-      if (j.counted) hipEventSynchronize(j.c->ev_done);
-      if (j.counted) s->inflight.fetch_sub(1);
-      j.counted = false;
+      job_settle(s, &j);
     }
     if (rc == TSH_OK) {
-      if (!spills[g].empty()) {
-        lists.push_back({spills[g].data(), (uint32_t)spills[g].size()});
-      } else {
-        const BlockHeader *h = reinterpret_cast<const BlockHeader *>(j.c->h_block);
-        lists.push_back({reinterpret_cast<const BlockEntry *>(j.c->h_block + sizeof(BlockHeader)),
-                         std::min(h->count, h->entries)});
-      }
-      if (!extras[g].empty()) lists.push_back({extras[g].data(), (uint32_t)extras[g].size()});
+      EntryList two[2];
+      const size_t n_lists = shard_lists(j.c->h_block, &spills[g], &extras[g], two);
+      lists.insert(lists.end(), two, two + n_lists);
     }
   }
   if (rc == TSH_OK)
     *out_count = finalize_query(idx->metric, idx->dim, t->query.data(), t->k, thr, lists, out_ids, out_dist,
                                 t->has_after ? &t->after : nullptr);
   std::string keep = g_err;
-  for (size_t g = 0; g < idx->shards.size(); ++g)
-    if (t->jobs[g].c) ctx_release(idx->shards[g].get(), t->jobs[g].c);
+  for (size_t g = 0; g < idx->shards.size(); ++g)  // (after the finaliser has read the blocks: they are the contexts')
+    job_abandon(idx->shards[g].get(), &t->jobs[g]);
   g_err = keep;
   return rc;
 }
 
 namespace {
-// tsh_search_shard; after_dist / after_id: a cursor per query (tsh_search_shard_after), or both NULL; mask_h: a mask
-// handle in place of row_mask (tsh_search_shard_masked), or NULL
-int32_t search_shard_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask, tsh_mask *mask_h,
-                          int32_t entries, void *d_out_blocks, void *stream, const double *after_dist, const int64_t *after_id) {
+// tsh_search_shard and its kin; r.after: a cursor per query (tsh_search_shard_after), or none; r.mask: the caller's bitmap,
+// or a mask handle in its place (tsh_search_shard_masked)
+int32_t search_shard_impl(tsh_index *idx, const ShardSearchReq &r, void *stream) {
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
-  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
-  if (nq <= 0 || !queries || !d_out_blocks || k <= 0 || entries < 1)
+  if (r.mask.handle && r.mask.handle->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (r.nq <= 0 || !r.queries || !r.d_blocks || r.k <= 0 || r.entries < 1)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / pointers");
   Shard *s = idx->shards[0].get();
   std::shared_lock<RwLock> sl = share(idx, s);
-  size_t bb = (size_t)tsh_candidate_block_bytes(entries);
-  if (s->rows == 0) {  // an empty shard contributes empty blocks
-    HIPCHK(hipSetDevice(s->device));
-    std::vector<uint8_t> z(bb * (size_t)nq, 0);
-    for (int32_t q = 0; q < nq; ++q) {
-      BlockHeader *h = reinterpret_cast<BlockHeader *>(z.data() + (size_t)q * bb);
-      h->entries = (uint32_t)entries;
-      h->k = (uint32_t)k;
-      h->metric = (uint32_t)s->metric;
-      h->row_base = s->row_base;
-    }
-    HIPCHK(hipMemcpy(d_out_blocks, z.data(), z.size(), hipMemcpyHostToDevice));
-    return TSH_OK;
-  }
-  MaskSrc ms(row_mask);
-  if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
-    int rc = TSH_OK;
-    const MaskPart *mp = mask_part(mask_h, 0, s, &rc);
-    if (!mp) return rc;
-    ms = MaskSrc(mp);
-  }
+  if (s->rows == 0) return write_empty_blocks(s, r.nq, r.k, r.entries, 0, r.d_blocks);  // an empty shard contributes empty blocks
+  MaskSrc ms;
+  int rc = call_mask_for_shard(r.mask, 0, s, &ms);
+  if (rc) return rc;
   SearchOut so;
-  so.d_blocks = static_cast<uint8_t *>(d_out_blocks);
+  so.d_blocks = r.d_blocks;
   so.user_stream = static_cast<hipStream_t>(stream);
-  if (after_dist) {  // a cursor call is never batched: every query is its own scan
-    so.after_dist = after_dist;
-    so.after_id = after_id;
-    return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
-  }
-  return shard_search_any(s, s->batch, idx->batch_min_nq.load(), queries, nq, k, ms, entries, &so);
+  so.after = r.after;
+  if (r.after)  // a cursor call is never batched: every query is its own scan
+    return shard_search_blocks(s, r.queries, r.nq, r.k, ms, r.entries, &so, PIPE_DEPTH);
+  return shard_search_any(s, s->batch, idx->batch_min_nq.load(), r.queries, r.nq, r.k, ms, r.entries, &so);
 }
-// the _masked entries' cursor is optional: both arrays or neither
-inline bool half_cursor(const double *after_dist, const int64_t *after_id) { return (after_dist == nullptr) != (after_id == nullptr); }
 }  // namespace
 
 int32_t tsh_search_shard(tsh_index *idx, const float *queries, int32_t nq, int32_t k,
                          const uint8_t *row_mask, int32_t entries, void *d_out_blocks, void *stream) {
-  return search_shard_impl(idx, queries, nq, k, row_mask, nullptr, entries, d_out_blocks, stream, nullptr, nullptr);
+  return search_shard_impl(idx, ShardSearchReq{queries, nq, k, entries, {row_mask, nullptr}, {}, static_cast<uint8_t *>(d_out_blocks)}, stream);
 }
 int32_t tsh_search_shard_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
                                const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks, void *stream) {
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_shard_impl(idx, queries, nq, k, row_mask, nullptr, entries, d_out_blocks, stream, after_dist, after_id);
+  return search_shard_impl(
+      idx, ShardSearchReq{queries, nq, k, entries, {row_mask, nullptr}, {after_dist, after_id}, static_cast<uint8_t *>(d_out_blocks)}, stream);
 }
 int32_t tsh_search_shard_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
                                 const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks, void *stream) {
   if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return search_shard_impl(idx, queries, nq, k, nullptr, mask, entries, d_out_blocks, stream, after_dist, after_id);
+  return search_shard_impl(
+      idx, ShardSearchReq{queries, nq, k, entries, {nullptr, mask}, {after_dist, after_id}, static_cast<uint8_t *>(d_out_blocks)}, stream);
 }
 
 // ---- progressive shard search ---------------------------------------------------------------------------------
@@ -3474,17 +3262,12 @@ int32_t tsh_search_shard_masked(tsh_index *idx, const float *queries, int32_t nq
 // do not exist for the GPU -- and the caller is told how many LEADING queries' blocks are final.
 struct tsh_shard_stream {
   tsh_index *idx = nullptr;
-  const float *queries = nullptr;
-  const uint8_t *mask = nullptr;
-  tsh_mask *mask_h = nullptr;  // ... or a mask handle (tsh_search_shard_begin_masked): the handle is kept, no bitmap is
-  const double *after_dist = nullptr;  // a cursor per query (tsh_search_shard_begin_after), or both NULL
-  const int64_t *after_id = nullptr;
-  std::vector<float> own_queries;  // public entry points: the caller's arrays are consumed before begin returns
+  ShardSearchReq req;  // (a mask handle is kept as it is, no bitmap is copied)
+  ShardStreamOpts opt;
+  std::vector<float> own_queries;  // opt.copy_inputs: req points into these
   std::vector<uint8_t> own_mask;
   std::vector<double> own_after_dist;
   std::vector<int64_t> own_after_id;
-  int32_t nq = 0, k = 0, entries = 0, step = 0;
-  uint8_t *d_blocks = nullptr;
   std::mutex mu;
   std::condition_variable cv;
   std::vector<char> done_q;  // single-query route: query q's block is final
@@ -3501,14 +3284,10 @@ struct tsh_shard_stream {
   int32_t enq = 0;
   std::atomic<int32_t> enq_seen{0};
   std::atomic<int> route{0};  // 0 not decided yet, 1 every query its own scan (events exist), 2 anything else
-  uint32_t tag = 0;           // generation the blocks carry (BlockHeader.pad[1])
-  bool leave_overflow = false;  // the caller enqueues its exchange ahead of the blocks (Job::leave_overflow)
   int rc = TSH_OK;
   std::string err;
   double busy_us = 0;  // worker: first enqueue to last block
-  std::thread th;              // the search's own thread ...
-  OneWorker *exec = nullptr;   // ... or the caller's persistent one (tsh_search_sharded: starting a thread costs a
-                               // 20-query call on a 125 k-row shard 30-40 us before its first scan is enqueued)
+  std::thread th;      // the search's own thread (unless opt.exec)
 
   void publish(int32_t upto) {  // queries [0, upto) are final
     {
@@ -3526,7 +3305,7 @@ struct tsh_shard_stream {
       st_q[(size_t)q] = where;
       seq_q[(size_t)q] = seq;
       enq_q[(size_t)q] = 1;
-      while (enq < nq && enq_q[(size_t)enq]) {
+      while (enq < req.nq && enq_q[(size_t)enq]) {
         ++enq;
         moved = true;
       }
@@ -3539,7 +3318,7 @@ struct tsh_shard_stream {
     {
       std::lock_guard<std::mutex> lk(mu);
       done_q[(size_t)q] = 1;
-      while (done < nq && done_q[(size_t)done]) {
+      while (done < req.nq && done_q[(size_t)done]) {
         ++done;
         moved = true;
       }
@@ -3557,52 +3336,40 @@ struct tsh_shard_stream {
       const size_t need = (size_t)((s->row_base + s->rows + 7) / 8);
       if (own_mask.size() < need) {
         own_mask.resize(need, 0);
-        mask = own_mask.data();
+        req.mask.bytes = own_mask.data();
       }
     }
-    MaskSrc ms(mask);
-    if (mask_h) {  // the handle's part for this shard: resident, rebuilt here if the shard grew since
-      int prc = TSH_OK;
-      const MaskPart *mp = mask_part(mask_h, 0, s, &prc);
-      if (!mp) return prc;
-      ms = MaskSrc(mp);
-    }
+    MaskSrc ms;
+    int mrc = call_mask_for_shard(req.mask, 0, s, &ms);
+    if (mrc) return mrc;
+    const int32_t nq = req.nq, k = req.k, entries = req.entries;
     const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
     if (s->rows == 0) {  // an empty shard contributes empty blocks
-      std::vector<uint8_t> z(bb * (size_t)nq, 0);
-      for (int32_t q = 0; q < nq; ++q) {
-        BlockHeader *h = reinterpret_cast<BlockHeader *>(z.data() + (size_t)q * bb);
-        h->entries = (uint32_t)entries;
-        h->k = (uint32_t)k;
-        h->metric = (uint32_t)s->metric;
-        h->row_base = s->row_base;
-        h->pad[1] = tag;
-      }
       route.store(2, std::memory_order_release);
-      HIPCHK(hipMemcpy(d_blocks, z.data(), z.size(), hipMemcpyHostToDevice));
+      int erc = write_empty_blocks(s, nq, k, entries, opt.tag, req.d_blocks);
+      if (erc) return erc;
       publish(nq);
       return TSH_OK;
     }
     const int32_t min_nq = idx->batch_min_nq.load();
-    const int32_t st = step > 0 ? std::min(step, nq) : nq;
+    const int32_t st = opt.step > 0 ? std::min(opt.step, nq) : nq;
     // (a cursor call is never batched, whatever step or the handle's batch threshold say)
-    if (after_dist || !shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
+    if (req.after || !shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
       done_q.assign((size_t)nq, 0);
       enq_q.assign((size_t)nq, 0);
       ev_q.assign((size_t)nq, nullptr);
       st_q.assign((size_t)nq, nullptr);
       seq_q.assign((size_t)nq, 0);
       SearchOut so;
-      so.d_blocks = d_blocks;
-      so.tag = tag;
-      so.leave_overflow = leave_overflow;
-      so.after_dist = after_dist;
-      so.after_id = after_id;
+      so.d_blocks = req.d_blocks;
+      so.tag = opt.tag;
+      so.leave_overflow = opt.leave_overflow;
+      so.after = req.after;
       so.on_done = [this](int32_t q) { mark(q); };
       so.on_enqueued = [this](int32_t q, hipEvent_t ev, hipStream_t where, uint64_t seq) { mark_enqueued(q, ev, where, seq); };
       route.store(1, std::memory_order_release);
       cv.notify_all();
-      return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
+      return shard_search_blocks(s, req.queries, nq, k, ms, entries, &so, PIPE_DEPTH);
     }
     route.store(2, std::memory_order_release);
     cv.notify_all();
@@ -3611,12 +3378,12 @@ struct tsh_shard_stream {
     for (int32_t q0 = 0; q0 < nq; q0 += st) {
       const int32_t gq = std::min(st, nq - q0);
       SearchOut so;
-      so.d_blocks = d_blocks + (size_t)q0 * bb;
-      so.tag = tag;  // (queries the batch hands back to the single-query path carry it at once)
-      int r = shard_search_any(s, s->batch, min_nq, queries + (size_t)q0 * s->dim, gq, k, ms, entries, &so);
+      so.d_blocks = req.d_blocks + (size_t)q0 * bb;
+      so.tag = opt.tag;  // (queries the batch hands back to the single-query path carry it at once)
+      int r = shard_search_any(s, s->batch, min_nq, req.queries + (size_t)q0 * s->dim, gq, k, ms, entries, &so);
       if (r) return r;
-      if (tag) {  // the matrix-core path's blocks get their generation now (host-synchronised: they are final)
-        stamp_tag_kernel<<<(unsigned)((gq + 63) / 64), 64, 0, s->aux_stream>>>(so.d_blocks, bb, gq, tag);
+      if (opt.tag) {  // the matrix-core path's blocks get their generation now (host-synchronised: they are final)
+        stamp_tag_kernel<<<(unsigned)((gq + 63) / 64), 64, 0, s->aux_stream>>>(so.d_blocks, bb, gq, opt.tag);
         HIPCHK(hipStreamSynchronize(s->aux_stream));
       }
       publish(q0 + gq);
@@ -3641,54 +3408,39 @@ struct tsh_shard_stream {
 };
 
 namespace {
-int shard_stream_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
-                       int32_t entries, void *d_out_blocks, int32_t step, bool copy_inputs, tsh_shard_stream **out,
-                       uint32_t tag = 0, OneWorker *exec = nullptr, bool leave_overflow = false,
-                       const double *after_dist = nullptr, const int64_t *after_id = nullptr, tsh_mask *mask_h = nullptr) {
+int shard_stream_begin(tsh_index *idx, const ShardSearchReq &r, const ShardStreamOpts &opt, tsh_shard_stream **out) {
   if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
   *out = nullptr;
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
-  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
-  if (nq <= 0 || !queries || !d_out_blocks || k <= 0 || entries < 1 || step < 0)
+  if (r.mask.handle && r.mask.handle->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (r.nq <= 0 || !r.queries || !r.d_blocks || r.k <= 0 || r.entries < 1 || opt.step < 0)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / step / pointers");
   std::unique_ptr<tsh_shard_stream> st(new tsh_shard_stream());
   st->idx = idx;
-  st->nq = nq;
-  st->k = k;
-  st->entries = entries;
-  st->step = step;
-  st->tag = tag;
-  st->leave_overflow = leave_overflow;
-  st->d_blocks = static_cast<uint8_t *>(d_out_blocks);
-  st->queries = queries;
-  st->mask = row_mask;
-  st->mask_h = mask_h;
-  st->after_dist = after_dist;
-  st->after_id = after_id;
-  if (copy_inputs) {
+  st->req = r;
+  st->opt = opt;
+  if (opt.copy_inputs) {
     Shard *s = idx->shards[0].get();
-    st->own_queries.assign(queries, queries + (size_t)nq * (size_t)s->dim);
-    st->queries = st->own_queries.data();
-    if (after_dist) {
-      st->own_after_dist.assign(after_dist, after_dist + nq);
-      st->own_after_id.assign(after_id, after_id + nq);
-      st->after_dist = st->own_after_dist.data();
-      st->after_id = st->own_after_id.data();
+    st->own_queries.assign(r.queries, r.queries + (size_t)r.nq * (size_t)s->dim);
+    st->req.queries = st->own_queries.data();
+    if (r.after) {
+      st->own_after_dist.assign(r.after.dist, r.after.dist + r.nq);
+      st->own_after_id.assign(r.after.id, r.after.id + r.nq);
+      st->req.after = Cursors{st->own_after_dist.data(), st->own_after_id.data()};
     }
-    if (row_mask) {
+    if (r.mask.bytes) {
       int64_t bits;
       {
         std::shared_lock<RwLock> sl = share(idx, s);
         bits = s->row_base + s->rows;  // the mask is global: one bit per row id below this shard's end
       }
-      st->own_mask.assign(row_mask, row_mask + (size_t)((bits + 7) / 8));
-      st->mask = st->own_mask.data();
+      st->own_mask.assign(r.mask.bytes, r.mask.bytes + (size_t)((bits + 7) / 8));
+      st->req.mask.bytes = st->own_mask.data();
     }
   }
   tsh_shard_stream *p = st.get();
-  if (exec) {
-    st->exec = exec;
-    exec->post([p] { p->run(); });
+  if (opt.exec) {
+    opt.exec->post([p] { p->run(); });
   } else {
     try {
       st->th = std::thread([p] { p->run(); });
@@ -3707,7 +3459,7 @@ int shard_stream_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t
 // (An event may meanwhile belong to a LATER query of the same pipeline -- its context was reused: waiting for it
 // then waits a little longer than needed, never too short.)
 int shard_stream_enqueued(tsh_shard_stream *st, int32_t want, hipEvent_t *after, int max) {
-  want = std::min(want, st->nq);
+  want = std::min(want, st->req.nq);
   if (!blocking_wait()) {
     const double t_end = now_us() + 3000.0;
     while (st->enq_seen.load(std::memory_order_acquire) < want && st->route.load(std::memory_order_acquire) != 2 &&
@@ -3744,7 +3496,7 @@ int shard_stream_enqueued(tsh_shard_stream *st, int32_t want, hipEvent_t *after,
 
 // blocks until min(want, nq) leading queries are final, or the search has ended; -> its status so far
 int shard_stream_progress(tsh_shard_stream *st, int32_t want, int32_t *out_done) {
-  want = std::min(want, st->nq);
+  want = std::min(want, st->req.nq);
   if (!blocking_wait()) {
     // the caller has nothing else to do and (blocking_wait: at least three CPUs per rank) a core to do it on: poll for
     // a few milliseconds before sleeping -- being woken through the condition variable costs 20-50 us, on the last
@@ -3763,7 +3515,7 @@ int shard_stream_progress(tsh_shard_stream *st, int32_t want, int32_t *out_done)
 }
 
 int shard_stream_end(tsh_shard_stream *st, double *busy_us = nullptr) {
-  if (st->exec) st->exec->wait();
+  if (st->opt.exec) st->opt.exec->wait();
   else if (st->th.joinable()) st->th.join();
   const int rc = st->rc;
   if (rc) g_err = st->err;
@@ -3773,9 +3525,11 @@ int shard_stream_end(tsh_shard_stream *st, double *busy_us = nullptr) {
 }
 }  // namespace
 
+// (the public entries: the caller's arrays are copied, the search runs on a thread of its own)
 int32_t tsh_search_shard_begin(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
                                int32_t entries, void *d_out_blocks, int32_t step, tsh_shard_stream **out) {
-  return shard_stream_begin(idx, queries, nq, k, row_mask, entries, d_out_blocks, step, /*copy_inputs=*/true, out);
+  return shard_stream_begin(idx, ShardSearchReq{queries, nq, k, entries, {row_mask, nullptr}, {}, static_cast<uint8_t *>(d_out_blocks)},
+                            ShardStreamOpts{step, /*copy_inputs=*/true}, out);
 }
 int32_t tsh_search_shard_begin_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
                                      const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks,
@@ -3783,8 +3537,9 @@ int32_t tsh_search_shard_begin_after(tsh_index *idx, const float *queries, int32
   if (out) *out = nullptr;
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return shard_stream_begin(idx, queries, nq, k, row_mask, entries, d_out_blocks, step, /*copy_inputs=*/true, out, 0, nullptr, false,
-                            after_dist, after_id);
+  return shard_stream_begin(
+      idx, ShardSearchReq{queries, nq, k, entries, {row_mask, nullptr}, {after_dist, after_id}, static_cast<uint8_t *>(d_out_blocks)},
+      ShardStreamOpts{step, /*copy_inputs=*/true}, out);
 }
 int32_t tsh_search_shard_begin_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
                                       const double *after_dist, const int64_t *after_id, int32_t entries, void *d_out_blocks,
@@ -3792,8 +3547,9 @@ int32_t tsh_search_shard_begin_masked(tsh_index *idx, const float *queries, int3
   if (out) *out = nullptr;
   if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
-  return shard_stream_begin(idx, queries, nq, k, nullptr, entries, d_out_blocks, step, /*copy_inputs=*/true, out, 0, nullptr, false,
-                            after_dist, after_id, mask);
+  return shard_stream_begin(
+      idx, ShardSearchReq{queries, nq, k, entries, {nullptr, mask}, {after_dist, after_id}, static_cast<uint8_t *>(d_out_blocks)},
+      ShardStreamOpts{step, /*copy_inputs=*/true}, out);
 }
 int32_t tsh_search_shard_progress(tsh_shard_stream *st, int32_t want, int32_t *out_done) {
   if (!st) return set_err(TSH_E_BAD_ARG, "stream is NULL");
@@ -3805,9 +3561,9 @@ int32_t tsh_search_shard_end(tsh_shard_stream *st) {
 }
 
 namespace {
-// tsh_merge_candidates; after_dist / after_id: a cursor per query (tsh_merge_candidates_after), or both NULL
+// tsh_merge_candidates; after: a cursor per query (tsh_merge_candidates_after), or none
 int32_t merge_candidates_impl(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k, double thr,
-                              const double *after_dist, const int64_t *after_id, const void *blocks, int32_t n_blocks,
+                              Cursors after, const void *blocks, int32_t n_blocks,
                               int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count, int32_t *needed_entries) {
   if (metric < 0 || metric > 2 || dim <= 0 || nq < 0 || n_blocks < 0 || entries < 0)
     return set_err(TSH_E_BAD_ARG, "bad metric / dim / nq / n_blocks / entries");
@@ -3832,19 +3588,11 @@ int32_t merge_candidates_impl(int32_t metric, int32_t dim, const float *queries,
     return set_err(TSH_E_OVERFLOW, "a candidate block needs %u entries (have %d)", need, entries);
   }
   parallel_for(nq, [&](int32_t q) {
-    std::vector<std::pair<const BlockEntry *, uint32_t>> lists;
-    for (int32_t b = 0; b < n_blocks; ++b) {
-      const uint8_t *p = base + ((size_t)b * nq + q) * bb;
-      const BlockHeader *h = reinterpret_cast<const BlockHeader *>(p);
-      lists.push_back({reinterpret_cast<const BlockEntry *>(p + sizeof(BlockHeader)), h->count});
-    }
+    std::vector<EntryList> lists;
+    for (int32_t b = 0; b < n_blocks; ++b) lists.push_back(block_list(base + ((size_t)b * nq + q) * bb));  // (count <= entries: see above)
     Cursor cur;
-    if (after_dist) {
-      cur.dist = after_dist[q];
-      cur.id = after_id[q];
-    }
     out_count[q] = finalize_query(metric, dim, queries + (size_t)q * dim, k, thr, lists,
-                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k, after_dist ? &cur : nullptr);
+                                  out_ids + (size_t)q * k, out_dist + (size_t)q * k, after.at(q, &cur));
   });
   return TSH_OK;
 }
@@ -3854,7 +3602,7 @@ int32_t tsh_merge_candidates(int32_t metric, int32_t dim, const float *queries, 
                              double thr, const void *blocks, int32_t n_blocks, int32_t entries,
                              int64_t *out_ids, double *out_dist, int32_t *out_count,
                              int32_t *needed_entries) {
-  return merge_candidates_impl(metric, dim, queries, nq, k, thr, nullptr, nullptr, blocks, n_blocks, entries, out_ids, out_dist,
+  return merge_candidates_impl(metric, dim, queries, nq, k, thr, Cursors(), blocks, n_blocks, entries, out_ids, out_dist,
                                out_count, needed_entries);
 }
 int32_t tsh_merge_candidates_after(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k, double thr,
@@ -3862,7 +3610,7 @@ int32_t tsh_merge_candidates_after(int32_t metric, int32_t dim, const float *que
                                    int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count,
                                    int32_t *needed_entries) {
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
-  return merge_candidates_impl(metric, dim, queries, nq, k, thr, after_dist, after_id, blocks, n_blocks, entries, out_ids, out_dist,
+  return merge_candidates_impl(metric, dim, queries, nq, k, thr, Cursors{after_dist, after_id}, blocks, n_blocks, entries, out_ids, out_dist,
                                out_count, needed_entries);
 }
 
