@@ -455,8 +455,8 @@ class HipVectorIndex:
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_BATCH_GROUP, 1 if on else 0))
 
     def set_batch_kernel(self, kind: int) -> None:
-        """Batched pre-filter keys: 0 f32 MFMA, 1 bf16x3, 2 f16, 3 auto (default: f16 for cosine, bf16x3
-        otherwise).  Results are identical."""
+        """Batched pre-filter keys: 0 f32 MFMA, 1 bf16x3, 2 f16, 3 auto (default: f16, but bf16x3 for an L2
+        index whose norms spread too far or whose fp16 candidate lists kept overflowing).  Results are identical."""
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_BATCH_KERNEL, int(kind)))
 
     def bench_batch(self, queries, k: int, iters: int = 3):

@@ -1,6 +1,6 @@
-// tsh_batch_f16pp.hip.h -- the fp16 pre-filter key kernel of the batched path, third generation ("ping-pong").
-// Same contract, operand planes ("plane32") and list protocol as batch_score_f16_kernel (tsh_batch_f16.hip.h);
-// what changed is who does what when:
+// tsh_batch_f16pp.hip.h -- the fp16 pre-filter key kernel of the batched path ("ping-pong"; the third generation, and
+// the only one left).  Contract, operand planes ("plane32"), DMA helpers and list protocol: tsh_batch_f16.hip.h.  Who
+// does what when:
 //
 //   * the two waves that share a SIMD never multiply at the same time.  Waves 0-3 (group 0: the upper half of the
 //     tile's queries) and waves 4-7 (group 1: the lower half; wave w + 4 sits on wave w's SIMD) run the same
@@ -20,7 +20,7 @@
 //     so "this row passes" is the accumulator's sign: a 32 x 32 block is tested with eight v_max3_i32 and one
 //     compare, and only blocks with a survivor (3.7 of a wave's eight per tile at k = 100) are looked at register by
 //     register (epilogue, below).  The key stored for a survivor is (seed - acc) * scale; the error model's
-//     accumulation term doubles (the chain now carries |theta| <= |q| max|v| as well: tsh_host_batch.inl.h,
+//     accumulation term doubles (the chain now carries |theta| <= |q| max|v| as well: tsh_batch_plan.h,
 //     batch_delta2).  Thresholds are capped at the largest key a row can have (BatchArgs::kmax), so an "everything
 //     passes" threshold stays finite.  The dense (sample) pass starts at zero.
 //   * L2 (round 4): key = |q|^2 + |v|^2 - 2 q.v <= thr  <=>  dot_acc - |v|^2 / (2 s) - (|q|^2 - thr) / (2 s) >= 0

@@ -1,4 +1,4 @@
-// tsh_batch_tu.hip -- the batched path's key kernels (f32 MFMA, bf16x3, f16: tsh_batch.hip.h, tsh_batch_f16.hip.h)
+// tsh_batch_tu.hip -- the batched path's key kernels (f32 MFMA, bf16x3, f16: tsh_batch.hip.h, tsh_batch_f16pp.hip.h)
 // and their launcher.  A translation unit of its own: these kernels are the ones that get tuned, and they
 // compile in parallel with the rest of the library.
 #include <hip/hip_runtime.h>
@@ -25,24 +25,10 @@ template <int METRIC>
 void launch_batch_score_bf16(const BatchArgs &a, bool dense, hipStream_t st, int cus) {
   int grid = a.q_tiles * a.n_tiles;
   if (grid <= 0) return;
-  if (a.dot_scale != 0.f) {  // f16 variant: tsh_batch_f16.hip.h (persistent: one 8-wave workgroup per CU)
+  if (a.dot_scale != 0.f) {  // f16 variant: tsh_batch_f16pp.hip.h (persistent: one 8-wave workgroup per CU)
     const int pgrid = std::min(grid, cus > 0 ? cus : 256);  // (cus: the launching shard's device, DeviceStreams::cus)
-    // Third generation (ping-pong phases, tsh_batch_f16pp.hip.h) for every metric; L2's per-row term rides in the
-    // accumulators' start values since round 4.  Probe builds (-DTSH_PROBES) carry the second generation beside it,
-    // TSH_F16_GEN=2 selects it there (tools/r4_ab_l2.sh)
-#ifdef TSH_PROBES
-    static const bool gen2 = getenv("TSH_F16_GEN") != nullptr && getenv("TSH_F16_GEN")[0] == '2';
-    if (gen2) {
-      if (a.tile_m == 256) {
-        if (dense) batch_score_f16_kernel<METRIC, true, 4><<<pgrid, 512, 0, st>>>(a);
-        else batch_score_f16_kernel<METRIC, false, 4><<<pgrid, 512, 0, st>>>(a);
-      } else {
-        if (dense) batch_score_f16_kernel<METRIC, true, 2><<<pgrid, 512, 0, st>>>(a);
-        else batch_score_f16_kernel<METRIC, false, 2><<<pgrid, 512, 0, st>>>(a);
-      }
-      return;
-    }
-#endif
+    // The ping-pong kernel (tsh_batch_f16pp.hip.h) for every metric; L2's per-row term rides in the accumulators'
+    // start values since round 4.
     if (a.tile_m == 256) {
       if (dense) batch_score_f16pp_kernel<METRIC, true, 4><<<pgrid, 512, 0, st>>>(a);
       else batch_score_f16pp_kernel<METRIC, false, 4><<<pgrid, 512, 0, st>>>(a);

@@ -503,7 +503,7 @@ inline int32_t sharded_group_max(int32_t nq) {
   return std::max(nq, 1);
 }
 // Does a call of nq queries go to the matrix cores on shards whose single-query scan takes scan_us?  The schedule's
-// copy of shard_takes_batch's cost model (tsh_host_batch.inl.h: 0.30 ms + a pass over the fp16 copy at ~4 TB/s per 128
+// copy of shard_takes_batch's cost model (tsh_batch_plan.h: 0.30 ms + a pass over the fp16 copy at ~4 TB/s per 128
 // queries, against a pipelined scan at ~6.6 TB/s + 25 us per query), in terms of what every rank knows.
 inline bool sharded_call_batches(int32_t nq, double scan_us) {
   if (nq < 2) return false;

@@ -37,6 +37,7 @@
 #include "tsh_count_band.h"
 #include "tsh_batch.hip.h"
 #include "tsh_batch_f16.hip.h"
+#include "tsh_batch_plan.h"
 #include "tsh_exact.hip.h"
 #include "tsh_finalize.h"
 #include "tsh_host_sync.h"
@@ -87,9 +88,7 @@ constexpr int F16_DENIAL_CALLS = 256; // batched calls a shard stays off fp16 ke
 constexpr uint32_t QUARANTINE_MAX = 1024;  // quarantined rows per shard; beyond that the shard goes to safe mode
 constexpr int SUBMIT_THREADS = 1;     // host threads that submit a multi-query call (more did not help: the pipeline is GPU-bound)
 constexpr int MAX_DIM_SCAN = 4096;    // register-resident query (NCH <= 16; the reference's f32 pages hold d <= 4073)
-constexpr float BIG_ABS = 1.0e15f;    // beyond this f32 squares can overflow
-
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+// (BIG_ABS, round_up: tsh_batch_plan.h)
 
 // (the finaliser -- Hit, Cursor, Cursors, sort_hits, finalize_query, count_entries -- is in tsh_finalize.h: host only, CPU-tested)
 
@@ -335,7 +334,7 @@ struct Shard {
   u32x4 *d_split = nullptr;
   int64_t split_cap = 0;    // rows allocated
   int64_t split_valid = 0;  // rows [0, split_valid) are converted
-  int batch_kernel = 3;     // TSH_OPT_BATCH_KERNEL: 0 f32 MFMA, 1 bf16x3, 2 f16, 3 auto (cosine: f16, else bf16x3)
+  int batch_kernel = 3;     // TSH_OPT_BATCH_KERNEL: 0 f32 MFMA, 1 bf16x3, 2 f16, 3 auto (f16_keys_fit, tsh_batch_plan.h: fp16 unless an L2 shard's norms spread too far)
   // TSH_OPT_BATCH_HUB: the hub rows' bound beside the sample's (fp16 keys, L2 / inner product).  OFF by default: measured
   // on the bench's L2 corpus (norms U(0.5, 2), 1 M x 768, 1024 queries; same box, alternating, tools/r6_hub_ab.sh) it cuts
   // the key passes 1510-1536 -> 1463-1468 us -- the 4096 shortest rows reach |v| <= 0.506, the bound lets ~300 rows per query
@@ -3952,7 +3951,7 @@ int32_t tsh_probe_batch_keys(tsh_index *idx, const float *queries, int32_t nq, i
   std::lock_guard<std::mutex> lk(b->mu);
   if (b->last_sample != s->rows || b->last_nq != nq) return set_err(TSH_E_BUSY, "another batched call ran in between");
   HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipMemcpy2D(out_keys, (size_t)s->rows * 4, b->d_dense, (size_t)b->last_sample * 4, (size_t)s->rows * 4, (size_t)nq,
+  HIPCHK(hipMemcpy2D(out_keys, (size_t)s->rows * 4, b->dense.d, (size_t)b->last_sample * 4, (size_t)s->rows * 4, (size_t)nq,
                      hipMemcpyDeviceToHost));
   if (s->split_grouped && s->batch_kernel_last.load() == 2) {  // a norm-grouped plane: the keys came out by plane position
     std::vector<uint32_t> perm((size_t)s->rows);
@@ -3965,7 +3964,8 @@ int32_t tsh_probe_batch_keys(tsh_index *idx, const float *queries, int32_t nq, i
     }
   }
   // one bound for every row of the query: the shared part + the per-row part at the longest row
-  const float *d2 = b->h_qaux + b->last_nq_pad, *al = b->h_qaux + 5 * (size_t)b->last_nq_pad;
+  const QAux aux{b->qaux.h, (size_t)b->last_nq_pad};
+  const float *d2 = aux.delta2(), *al = aux.alpha();
   for (int32_t q = 0; q < nq; ++q) {
     const double v = (double)d2[q] + 2.0 * (double)al[q] * (double)s->max_norm * (1.0 + 1e-6);
     out_delta2[q] = (float)v;
@@ -3980,8 +3980,9 @@ int32_t tsh_probe_batch_row_band(tsh_index *idx, int32_t nq, float *out_alpha2, 
   std::shared_lock<RwLock> sl = share(idx, s);
   BatchCtx *b = s->batch;
   std::lock_guard<std::mutex> lk(b->mu);
-  if (b->last_nq != nq || !b->h_qaux) return set_err(TSH_E_BUSY, "no batched call of that many queries to report on");
-  const float *d2 = b->h_qaux + b->last_nq_pad, *al = b->h_qaux + 5 * (size_t)b->last_nq_pad;
+  if (b->last_nq != nq || !b->qaux.h) return set_err(TSH_E_BUSY, "no batched call of that many queries to report on");
+  const QAux aux{b->qaux.h, (size_t)b->last_nq_pad};
+  const float *d2 = aux.delta2(), *al = aux.alpha();
   for (int32_t q = 0; q < nq; ++q) {
     out_alpha2[q] = 2.f * al[q];
     out_beta2[q] = d2[q];
