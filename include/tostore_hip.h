@@ -51,7 +51,8 @@ extern "C" {
  *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats;
  *    tsh_search_shard_after, tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after;
  *    tsh_search_shard_masked, tsh_search_shard_begin_masked, tsh_search_sharded_masked;
- *    tsh_search_count, tsh_search_count_stats. */
+ *    tsh_search_count, tsh_search_count_stats;
+ *    tsh_groups_create, tsh_groups_set, tsh_groups_destroy, tsh_search_grouped, tsh_search_grouped_stats. */
 
 /* status codes */
 #define TSH_OK 0
@@ -415,6 +416,62 @@ int32_t tsh_search_count(tsh_index *idx, const float *queries, int32_t nq, doubl
 /* out[0] count searches, out[1] rows sent to the side list, out[2] searches redone with a larger side list,
  * out[3] searches answered without a device window pass (safe mode; nothing for a key to decide) */
 int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out);
+
+/* ---- grouped search: the nearest row of each of the k nearest groups (additive since ABI 5) -----------------------
+ * The rows of a vector table are chunks of documents, frames of videos, variants of products; the answer wanted is
+ * "the 10 nearest documents", each shown by its best chunk.  Let L be the list tsh_search would return for the query
+ * with k = infinity: the same row mask (pointer or handle, at most one), tombstones, gaps, quarantined rows and
+ * distance_threshold, ordered by Dart double.compareTo on the distance with ties by row id.  Every row belongs to a
+ * group: its entry in the groups handle's array; a row whose entry is negative, or which lies beyond the array, is
+ * UNGROUPED -- a group of its own.  G is L with every entry removed whose group occurred earlier in L, and
+ * tsh_search_grouped returns the first k entries of G: ids and distances bit for bit those of L; out_group[i] (nullable)
+ * is the entry's group, -1 for an ungrouped row; unused slots read id -1, distance NaN, group -1.  So with every row
+ * ungrouped, or every row in a group of its own, the answer is tsh_search's; with all rows in one group it is L's first
+ * entry; and a group is represented by its best row that SURVIVES mask, tombstones and threshold -- a group with no
+ * surviving row does not appear.
+ *
+ * A groups handle holds the array: group_of[i] is the group of GLOBAL row id i, >= 0 and < n_groups, or negative.
+ * tsh_groups_set extends or overwrites the entries [first_row_id, first_row_id + n): the append feed's companion.
+ * Lifetime: a groups handle belongs to the index it was made for and works with any kind of handle -- a whole index,
+ *   several devices (groups may span the shards: the finaliser's step runs once over all of them), a shard with global
+ *   ids.  tsh_index_destroy orphans it, it is not left dangling: later use answers TSH_E_BAD_ARG, and
+ *   tsh_groups_destroy then frees only the handle itself.  The two destroys may come in either order.
+ * Threads: any number of searches may share one handle.  tsh_groups_set takes the index lock the way an append does
+ *   and waits for the searches that use the handle.
+ * Limits: n_groups <= 1 << 26 (every query context that runs a grouped search keeps 8 B per group on the device).
+ *   TSH_E_BAD_ARG answers a larger table, an id at or above n_groups, both mask forms at once, a mask or groups handle
+ *   made for another index, and a NULL `groups`.
+ * Trivial cases: k <= 0 or an empty index returns TSH_OK with counts of 0.
+ * Several queries per call run as the pipeline of single-query scans, never on the batched path.
+ * A shard handle answers for its own rows; the ranks' answers merge by concatenating them, ordering, dropping repeated
+ *   groups and cutting to k, which is exact: a winning group's best row is the best of its group on the rank that holds
+ *   it, and fewer than k groups beat it there.
+ * Cost: a grouped search takes the f32 tile scan or the list scan -- never the exact path, the fp16 / int8 copies or the
+ *   batched path --, three passes over the scan's 4 B per row around the unchanged select and re-rank, and the exact
+ *   distances of the few rows that are not their group's nearest by f32 key but may be exactly
+ *   (tostore_amd/csrc/tsh_group.hip.h, tsh_group_rule.h).  On big shards, whose plain tsh_search reads the int8 copy
+ *   (a quarter of the bytes), one grouped search therefore costs several plain searches -- measured on 1 M x 768, L2,
+ *   64-query calls: 446 us per query against 118, a factor of 3.8, the ratio of the two scans' bytes; against the
+ *   caller's loop of tsh_search_after pages until k groups were seen (984 us at k = 10, 1258 at k = 100, 2 to 4 pages) it
+ *   is 0.45 resp. 0.35, and it costs what tsh_search_count costs ("Grouped search";
+ *   profiles/search_grouped_ab.json).
+ * The next step would bring, none of it here: a cursor, so that groups can be paged.  More than one row per group.  A
+ *   ticket form (tsh_search_submit_grouped).  The tsh_search_shard* and tsh_search_sharded* entries.  A count of groups.
+ * tsh_counters keeps its layout; a grouped search counts in searches and scan_launches like any other search.
+ * The handle is a tsh_groups * (typedef below).  In the prototypes it travels as `void *`, and tsh_groups_create's
+ * `out` -- the address of the caller's tsh_groups * (a tsh_groups **) -- as `void *` too: the bindings' prototype tables
+ * (tests/test_dart_bridge.py) know a closed list of C types, every opaque handle is a pointer to them anyway, and an
+ * additive entry does not widen that list.  C callers pass their tsh_groups * and its address as they are. */
+typedef struct tsh_groups tsh_groups;
+int32_t tsh_groups_create(tsh_index *idx, const int32_t *group_of, int64_t n, int32_t n_groups, void *out);
+int32_t tsh_groups_set(void *groups, int64_t first_row_id, int64_t n, const int32_t *group_of);
+int32_t tsh_groups_destroy(void *groups);
+int32_t tsh_search_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double distance_threshold,
+                           const uint8_t *row_mask, tsh_mask *mask, void *groups, int64_t *out_ids,
+                           double *out_dist, int32_t *out_group, int32_t *out_count);
+/* out[0] grouped searches, out[1] rows sent to the side list, out[2] searches redone with a larger side list,
+ * out[3] searches answered without the device group passes (safe mode); summed over the shards */
+int32_t tsh_search_grouped_stats(tsh_index *idx, int64_t *out);
 
 /* ---- row-sharded deployments (one process per GPU) ----------------------
  * Each rank scans its shard and emits, per query, one fixed-size candidate

@@ -82,6 +82,51 @@ class HipMask:
             pass
 
 
+class HipGroups:
+    """The group of every row (`tsh_groups*`, include/tostore_hip.h), for `HipVectorIndex.search_grouped`: entry i of
+    `group_of` (int32) is the group of GLOBAL row id i -- a document, a video, a product --, at least 0 and below
+    `n_groups`, or negative for a row that stands for itself.  Rows beyond the array are ungrouped; `set()` extends or
+    overwrites a range, as the append feed does for the rows.  An index that is closed first closes its groups, and a
+    closed handle is refused by every search (ValueError)."""
+
+    def __init__(self, index: "HipVectorIndex", group_of, n_groups: int):
+        g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
+        self._h = ctypes.c_void_p()
+        self.index = index
+        self.n_groups = int(n_groups)
+        _ffi.check(_ffi.lib().tsh_groups_create(index._h, g.ctypes.data_as(_ffi.p_i32), g.shape[0], self.n_groups,
+                                                ctypes.byref(self._h)))
+        index._live_masks().add(self)
+
+    def handle(self):
+        """The `tsh_groups*` to pass to the library; ValueError once the handle (or its index) was closed."""
+        if not self._h:
+            raise ValueError("the groups handle is closed (or its index was)")
+        return self._h
+
+    def set(self, first_row_id: int, group_of) -> None:
+        """Entries [first_row_id, first_row_id + len(group_of)) of the array, extended where it was shorter."""
+        g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
+        _ffi.check(_ffi.lib().tsh_groups_set(self.handle(), int(first_row_id), g.shape[0], g.ctypes.data_as(_ffi.p_i32)))
+
+    def close(self) -> None:
+        if self._h:
+            _ffi.lib().tsh_groups_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipVectorIndex:
     """Owner of one `tsh_index*`.  Destroy exactly once (close / context manager)."""
 
@@ -125,8 +170,13 @@ class HipVectorIndex:
         """A device-resident row set for many searches (bit i of `bits`, LSB first, keeps GLOBAL row id i)."""
         return HipMask(self, bits)
 
+    def make_groups(self, group_of, n_groups: int) -> "HipGroups":
+        """The rows' groups for search_grouped (entry i of `group_of`: the group of GLOBAL row id i, negative: none)."""
+        return HipGroups(self, group_of, n_groups)
+
     def _live_masks(self) -> "weakref.WeakSet":
-        """The masks made for this index and not yet closed: close() closes them before it destroys the index."""
+        """The masks and groups handles made for this index and not yet closed: close() closes them before it destroys
+        the index."""
         s = self.__dict__.get("_masks")
         if s is None:
             s = self._masks = weakref.WeakSet()
@@ -322,6 +372,40 @@ class HipVectorIndex:
         out = (ctypes.c_int64 * 4)()
         _ffi.check(_ffi.lib().tsh_search_count_stats(self._h, out))
         return {"searches": out[0], "side_rows": out[1], "redone": out[2], "no_window": out[3]}
+
+    def search_grouped(self, queries, k: int, groups: "HipGroups", distance_threshold: Optional[float] = None, row_mask=None):
+        """The nearest row of each of the k nearest groups: (ids[nq,k], dist[nq,k], group[nq,k], count[nq]).  The list
+        search() would return with k = infinity, every entry dropped whose group occurred earlier in it, cut to k; group
+        is -1 for a row that stands for itself.  row_mask: None, a byte mask or a HipMask."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be nq x {self.dim}")
+        if not isinstance(groups, HipGroups):
+            raise TypeError("groups must be a HipGroups (HipVectorIndex.make_groups)")
+        nq, kk = q.shape[0], max(int(k), 0)
+        ids = np.empty((nq, max(kk, 1)), dtype=np.int64)
+        dist = np.empty((nq, max(kk, 1)), dtype=np.float64)
+        grp = np.empty((nq, max(kk, 1)), dtype=np.int32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        thr = math.nan if distance_threshold is None else float(distance_threshold)
+        handle, mp = None, None
+        if isinstance(row_mask, HipMask):
+            handle = row_mask.handle()
+        else:
+            row_mask, mp = self.mask_arg(row_mask)
+        _ffi.check(_ffi.lib().tsh_search_grouped(self._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp, handle, groups.handle(),
+                                                 ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                 grp.ctypes.data_as(_ffi.p_i32), cnt.ctypes.data_as(_ffi.p_i32)))
+        return ids[:, :kk], dist[:, :kk], grp[:, :kk], cnt
+
+    def search_grouped_stats(self) -> dict:
+        """The grouped searches' counters, per shard search: all of them, rows sent to the side list, searches redone with a
+        larger side list, searches answered without the group passes on the device (safe mode)."""
+        out = (ctypes.c_int64 * 4)()
+        _ffi.check(_ffi.lib().tsh_search_grouped_stats(self._h, out))
+        return {"searches": out[0], "side_rows": out[1], "redone": out[2], "no_device_passes": out[3]}
 
     # -- asynchronous single-query form (several queries in flight) -----------------
     def submit(self, query, k: int, row_mask=None, after=None) -> tuple:

@@ -35,6 +35,7 @@
 #include "tsh_after_band.h"
 #include "tsh_count.hip.h"
 #include "tsh_count_band.h"
+#include "tsh_group.hip.h"
 #include "tsh_batch.hip.h"
 #include "tsh_batch_f16.hip.h"
 #include "tsh_batch_plan.h"
@@ -151,6 +152,12 @@ struct Ctx {
   int64_t side_cap = 0;
   int side_flip = 0;
   bool side_dirty = false;  // a cursor job is out, or one failed on the way: the count words are cleared before the next
+  // grouped searches (tsh_group.hip.h): the heads array and its tile minima (sized like d_keys / d_gmin) and the head table,
+  // a 64-bit word per group -- reserved by the context's first grouped job, cleared in front of every one
+  uint32_t *d_heads = nullptr, *d_hmin = nullptr;
+  int64_t heads_tiles = 0;
+  unsigned long long *d_gm = nullptr;
+  int64_t gm_cap = 0;
   int64_t bytes = 0;
 };
 
@@ -314,6 +321,9 @@ struct Shard {
   // counts (tsh_search_count_stats): all of them, rows their window passes sent to the side list, counts redone with a
   // larger side list, counts answered without a window pass on the device
   std::atomic<int64_t> c_count{0}, c_count_side{0}, c_count_redone{0}, c_count_nowindow{0};
+  // grouped searches (tsh_search_grouped_stats): all of them, rows their side passes sent to the side list, searches redone
+  // with a larger side list, searches answered without the device group passes (safe mode)
+  std::atomic<int64_t> c_grouped{0}, c_grouped_side{0}, c_grouped_redone{0}, c_grouped_nodev{0};
   int cus = 0;  // compute units of the shard's device (grid of the persistent key kernels)
   std::atomic<int> f16_strikes{0};      // batched calls in a row whose fp16 bands overflowed many candidate lists
   std::atomic<int> f16_denied_calls{0};  // auto key-kernel choice: bf16x3 instead of fp16 for this many more batched calls
@@ -704,6 +714,9 @@ void ctx_free_all(Ctx *c) {
   hipFree(c->d_side_rows);
   hipFree(c->d_side_cnt);
   hipHostFree(c->h_side);
+  hipFree(c->d_heads);
+  hipFree(c->d_hmin);
+  hipFree(c->d_gm);
 }
 
 int ctx_prepare(Shard *s, Ctx *c, int32_t entries, bool need_mask) {
@@ -927,6 +940,18 @@ struct ShardMask {
   bool listed() const { return list.ids || list.d_ids; }
 };
 
+// ---- groups handles (tsh_groups_create, include/tostore_hip.h): one shard's part ---------------------------------------
+// The caller's group array sliced to this shard's rows on the device: entry r = the group of local row r, for the rows
+// the shard had when the part was built (rows beyond the caller's array: -1).  A search that finds the shard grown, or
+// the array changed by tsh_groups_set (built_rows = -1), rebuilds it first (groups_part).
+struct GroupPart {
+  int device = 0;
+  std::atomic<int64_t> built_rows{-1};
+  int32_t *d_group = nullptr;
+  int64_t cap = 0;
+  int32_t n_groups = 0;
+};
+
 // One query in flight on one context.  Its three kernels (scan, select,
 // rerank) are enqueued back to back on the shard's single in-order pipeline
 // stream with NO copy and NO cross-stream dependency between them: the query
@@ -976,6 +1001,11 @@ struct Job {
   double count_thr = 0;
   CountWindow window;
   int64_t certain = 0;
+  // a grouped job (JobReq::groups): the group passes run around select and re-rank (grouped; tsh_group.hip.h) and leave a
+  // side list like a cursor job's, redone the same way -- or, in safe mode, a plain search job whose every live row
+  // reaches the finaliser (grouping without grouped)
+  bool grouping = false, grouped = false;
+  const GroupPart *gpart = nullptr;
   const float *redo_query = nullptr;  // the caller's query (a ticket's own copy): valid until the job is finished
   std::vector<uint64_t> redo_words;   // a ticket's copy of a pointer mask's words (JobReq::mask_dies), else empty
 };
@@ -1064,6 +1094,33 @@ int ctx_reserve_side(Ctx *c, int64_t want) {
   HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_side_dev), c->h_side, 0));
   c->side_cap = want;
   c->bytes += want * 4;
+  return TSH_OK;
+}
+
+// what a grouped job adds to its context (tsh_group.hip.h): the heads array and its minima, as many tiles as the context's
+// keys have, and a head table of n_groups words
+int ctx_reserve_group(Ctx *c, int64_t n_groups) {
+  if (c->tiles_cap > c->heads_tiles) {
+    hipFree(c->d_heads);
+    hipFree(c->d_hmin);
+    c->d_heads = c->d_hmin = nullptr;
+    c->bytes -= c->heads_tiles * 65 * 4;
+    c->heads_tiles = 0;
+    HIPCHK(hipMalloc(&c->d_heads, (size_t)c->tiles_cap * 64 * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&c->d_hmin, (size_t)c->tiles_cap * sizeof(uint32_t)));
+    c->heads_tiles = c->tiles_cap;
+    c->bytes += c->heads_tiles * 65 * 4;
+  }
+  if (n_groups > c->gm_cap) {
+    hipFree(c->d_gm);
+    c->d_gm = nullptr;
+    c->bytes -= c->gm_cap * 8;
+    c->gm_cap = 0;
+    const int64_t want = round_up(n_groups + n_groups / 8, 1024);
+    HIPCHK(hipMalloc(&c->d_gm, (size_t)want * 8));
+    c->gm_cap = want;
+    c->bytes += want * 8;
+  }
   return TSH_OK;
 }
 
@@ -1384,6 +1441,7 @@ struct JobReq {
   int64_t side_want = 0;          // ... redone after its side list overflowed: room for this many rows
   bool count = false;             // a count (tsh_search_count): how many rows pass count_thr and follow `after`, if given
   double count_thr = 0;           // ... its threshold (NaN: none)
+  const GroupPart *groups = nullptr;  // a grouped search (tsh_search_grouped): this shard's part of the groups handle
   bool mask_dies = false;         // ... enqueued for a ticket: a pointer mask's words and list are gone before the job is finished
 };
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
@@ -1651,6 +1709,26 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
                            s->ld, s->row_base, s->dim, s->metric, side_cap};
     // (the side re-rank's grid: one workgroup per row up to the re-rank's own 1024)
     TSH_LAUNCH_EV(count_side_kernel, std::min(side_cap, 1024u), 64, ts, none, done, sd);
+  } else if (j->grouped) {
+    // a grouped job: the head table cleared, every group's head found (G1), one head per group left for the select (G2);
+    // behind the re-rank the rows that may still be their group's best (G3) get their exact sums by the cursor jobs' side
+    // re-rank -- tsh_group.hip.h
+    const GroupPart *gp = j->gpart;
+    const int32_t n_tiles = ka.se.n_tiles;
+    const unsigned tgrid = (unsigned)((n_tiles + 3) / 4);
+    const uint32_t side_cap = (uint32_t)c->side_cap;
+    uint32_t *const side_count = c->d_side_cnt + j->side_word;
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
+    if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
+    group_min_kernel<<<tgrid, 256, 0, ts>>>(ga);
+    group_heads_kernel<<<tgrid, 256, 0, ts>>>(ga);
+    launch_select(ka.se, n_tiles, ts);
+    TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, none, ka.ra);
+    const GroupSideArgs gs{ga, ka.se.hdr, c->d_side_rows, side_count, side_cap, ka.se.eps_rel, ka.se.delta_abs};
+    group_side_kernel<<<tgrid, 256, 0, ts>>>(gs);
+    const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
+                           s->dim, s->metric, side_cap};
+    TSH_LAUNCH_EV(after_side_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, ts, none, done, sd);
   } else {
     // a cursor job: the floor pass takes the rows at or before the cursor out of the select's sight (A1), and the rows
     // it could not decide get their exact sums behind the re-rank (A2) -- tsh_after.hip.h
@@ -1729,13 +1807,18 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   j->counting = rq.count;
   j->count_thr = rq.count_thr;
   j->certain = 0;
-  const Route &r = j->route = choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after || rq.count);
+  j->grouping = rq.groups != nullptr;
+  j->gpart = rq.groups;
+  const Route &r = j->route =
+      choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after || rq.count || j->grouping);
   // A cursor inside the error model gets its floor in the scan's key space (tsh_after_band.h); "from the start" has
   // none; a +inf or NaN cursor can only be followed by quarantined rows -- every row the scan offers has a finite
   // distance -- so no scan runs at all.  Safe mode: no floor, the finaliser filters.
   // A count inside the error model gets its window there (tsh_count_band.h), or no scan at all where no scanned row can
   // count.  Safe mode: a plain search job whose every live row reaches the finaliser with its exact sums.
+  // A grouped search inside the error model gets its group passes (tsh_group.hip.h); safe mode: a plain search job.
   j->floored = j->after_skip = j->windowed = false;
+  j->grouped = j->grouping && !r.band.force_all;
   if (rq.count) {
     if (!r.band.force_all) {
       j->window = count_window(s->metric, s->dim, r.band.eps_rel, r.band.delta_abs,
@@ -1756,7 +1839,8 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
   if (j->after_skip) return enqueue_after_skip(s, j, rq, q);
-  if (j->floored || j->windowed) {
+  if (j->grouped && (rc = ctx_reserve_group(c, rq.groups->n_groups))) return rc;
+  if (j->floored || j->windowed || j->grouped) {
     if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(rq.side_want, AFTER_SIDE_CAP), c->side_cap)))) return rc;
     if (c->side_dirty) {  // (a context's first cursor or count job, or one after a job that failed on its way)
       HIPCHK(hipMemsetAsync(c->d_side_cnt, 0, 3 * sizeof(uint32_t), s->aux_stream));
@@ -1801,6 +1885,10 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
     j->redo_mask.part = rq.mask.part;
   }
   fill_job_args(s, j, rq, q, &ka);
+  if (j->grouped) {  // select and re-rank see one head per group
+    ka.se.gmin = c->d_hmin;
+    ka.se.keys = c->d_heads;
+  }
   // with other queries already in flight -- or the caller about to submit more (the first query of a multi-query
   // call: left alone it kept its select + re-rank on the pipeline stream, in front of the call's third scan) -- the
   // tail moves to the reserved CUs; a lone query keeps everything in order on one stream (no hand-off latency)
@@ -1881,6 +1969,8 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
   }
   int fgrid = (int)std::min<int64_t>((n_keys + 255) / 256, 4096);
   const Band &band = j->route.band;
+  // (a grouped job: the wide band is taken over the heads -- one key per group -- as the select was)
+  const uint32_t *const f_keys = j->grouped ? c->d_heads : c->d_keys, *const f_gmin = j->grouped ? c->d_hmin : c->d_gmin;
   if (band_key >= KEY_NAN && !band.force_all && j->k < n_keys) {
     // K2 could not bound the k-th key (k beyond its tile-minimum scheme, or fewer than k live tiles and a full
     // list): find the exact k-th smallest key with a 4-pass radix select over all keys -- 4 small kernels and
@@ -1891,7 +1981,7 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
     bool found = true;
     for (int shift = 24; shift >= 0 && found; shift -= 8) {
       HIPCHK(hipMemsetAsync(c->d_hist, 0, sizeof hist, st));
-      radix_hist_kernel<<<fgrid, 256, 0, st>>>(c->d_keys, c->d_gmin, n_keys, prefix, shift, c->d_hist);
+      radix_hist_kernel<<<fgrid, 256, 0, st>>>(f_keys, f_gmin, n_keys, prefix, shift, c->d_hist);
       HIPCHK(hipMemcpyAsync(hist, c->d_hist, sizeof hist, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       uint64_t cum = 0;
@@ -1910,7 +2000,7 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
     if (found) band_key = h_band_of(prefix, band.eps_rel, band.delta_abs);
   }
   HIPCHK(hipMemsetAsync(c->d_big_count, 0, 4, st));
-  filter_kernel<<<fgrid, 256, 0, st>>>(c->d_keys, c->d_gmin, n_keys, band_key, c->d_big_rows, c->d_big_count,
+  filter_kernel<<<fgrid, 256, 0, st>>>(f_keys, f_gmin, n_keys, band_key, c->d_big_rows, c->d_big_count,
                                       (uint32_t)c->big_cap, list);
   uint32_t count = 0;
   HIPCHK(hipMemcpyAsync(&count, c->d_big_count, 4, hipMemcpyDeviceToHost, st));
@@ -1995,7 +2085,7 @@ int redo_after_side(Shard *s, Job *j) {
   const int64_t n = c->h_side[0].id;
   if (n <= c->side_cap) return TSH_OK;
   if (j->after_redone) return set_err(TSH_E_HIP, "a cursor search's side list overflowed twice (%lld rows): internal error", (long long)n);
-  (j->counting ? s->c_count_redone : s->c_after_redone)++;
+  (j->grouping ? s->c_grouped_redone : j->counting ? s->c_count_redone : s->c_after_redone)++;
   const Cursor cur = j->after;
   JobReq rq(j->redo_query, j->k, j->entries);
   rq.mask = j->redo_mask;
@@ -2006,6 +2096,7 @@ int redo_after_side(Shard *s, Job *j) {
   rq.after = j->has_after ? &cur : nullptr;
   rq.count = j->counting;
   rq.count_thr = j->count_thr;
+  rq.groups = j->gpart;
   rq.side_want = round_up(n, 1024);
   int rc = job_enqueue(s, j, rq);
   if (j->counted) {
@@ -2033,7 +2124,7 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     int rc = redo_overflowed_scan(s, j);
     if (rc) return rc;
   }
-  if (j->floored || j->windowed) {
+  if (j->floored || j->windowed || j->grouped) {
     int rc = redo_after_side(s, j);
     if (rc) return rc;
   }
@@ -2091,7 +2182,10 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     extra->clear();
     for (uint32_t i : j->quar_sel) extra->push_back(c->h_quar[i]);
   }
-  if (j->counting) {
+  if (j->grouping) {
+    s->c_grouped++;
+    if (!j->grouped) s->c_grouped_nodev++;
+  } else if (j->counting) {
     s->c_count++;
     if (!j->windowed) s->c_count_nowindow++;
   } else if (j->has_after) {
@@ -2100,12 +2194,12 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   }
   if (j->floored && j->dev_target) {  // (shard mode: the side rows' entries are in the device block already)
     s->c_after_side += c->h_side[0].id;
-  } else if (j->floored || j->windowed) {  // the rows the floor / window pass could not decide join the candidates too
+  } else if (j->floored || j->windowed || j->grouped) {  // the rows the floor / window / side pass could not decide join the candidates too
     if (!extra) return set_err(TSH_E_BAD_ARG, "no room for the side list's entries");
     if (j->quar_sel.empty()) extra->clear();
     const uint32_t side_n = (uint32_t)c->h_side[0].id;
     extra->insert(extra->end(), c->h_side + 1, c->h_side + 1 + side_n);
-    (j->windowed ? s->c_count_side : s->c_after_side) += side_n;
+    (j->grouped ? s->c_grouped_side : j->windowed ? s->c_count_side : s->c_after_side) += side_n;
     if (j->windowed) j->certain = (int64_t)c->h_side[0].s0;
   }
   s->c_searches++;
@@ -2171,6 +2265,8 @@ struct SearchOut {
   // follow the query's cursor, if any.  No block leaves the shard (h_blocks NULL); spill / extra are needed
   int64_t *count_out = nullptr;
   double count_thr = 0;
+  // ... host mode, a grouped search (tsh_search_grouped): this shard's part of the groups handle
+  const GroupPart *groups = nullptr;
 };
 
 // One submitting thread's share of a multi-query call: queries [q0, q1) of the call, at most
@@ -2208,6 +2304,7 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       rq.after = out->after.at(q, &cur);
       rq.count = out->count_out != nullptr;
       rq.count_thr = out->count_thr;
+      rq.groups = out->groups;
       rc = job_enqueue(s, &j, rq);
       if (rc) {
         release_all();
@@ -2306,6 +2403,7 @@ struct tsh_index {
   std::atomic<int> tickets_open{0};  // submitted, not yet waited for: each holds one context per shard
   std::atomic<int32_t> batch_min_nq{1};  // 0 never, 1 by estimated cost, n >= 2: from n queries per call on
   std::vector<tsh_mask *> masks;  // live mask handles made for this index (guarded by g_mask_mu): orphaned by destroy
+  std::vector<struct tsh_groups *> groups;  // ... and live groups handles, the same way
   std::unique_ptr<ShardWorkers> workers;  // multi-device handles: one persistent host thread per further shard
   // result-block buffers of multi-query calls, kept between calls: a fresh 6 MB allocation per call spends
   // ~0.3 ms in page faults when it is first written
@@ -2447,6 +2545,16 @@ struct tsh_mask {
   std::vector<std::unique_ptr<MaskPart>> parts;  // one per shard of the index
 };
 
+// ---- groups handles -------------------------------------------------------------------------------------------
+struct tsh_groups {
+  tsh_index *idx = nullptr;       // nullptr: orphaned -- its index was destroyed first (parts freed then)
+  std::vector<int32_t> group_of;  // the caller's array by GLOBAL row id (its own copy: the finaliser reads it, 4 B per row)
+  int32_t n_groups = 0;
+  std::shared_mutex use_mu;  // searches: shared, for the whole call; tsh_groups_set: exclusive
+  std::mutex mu;             // builds / rebuilds of the parts
+  std::vector<std::unique_ptr<GroupPart>> parts;  // one per shard of the index
+};
+
 namespace {
 
 // Settles a mask's destroy against its index's (either may come first, from any thread): index -> masks lists, every
@@ -2572,6 +2680,62 @@ inline int call_mask_for_shard(const CallMask &m, size_t g, Shard *s, MaskSrc *o
   const MaskPart *mp = mask_part(m.handle, g, s, &rc);
   if (!mp) return rc;
   *out = MaskSrc(mp);
+  return TSH_OK;
+}
+
+void groups_part_free(GroupPart *p) {
+  if (hipSetDevice(p->device) != hipSuccess) return;
+  hipFree(p->d_group);
+  p->d_group = nullptr;
+  p->cap = 0;
+  p->built_rows.store(-1);
+}
+
+// (Re)builds one shard's part for the rows the shard has now: the slice of the handle's array, -1 beyond it.  Caller holds
+// s->mu shared, g->use_mu (shared or exclusive) and g->mu
+int groups_build_part(tsh_groups *g, GroupPart *p, Shard *s) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  p->n_groups = g->n_groups;
+  const int64_t rows = s->rows;
+  if (rows > p->cap) {
+    hipFree(p->d_group);
+    p->d_group = nullptr;
+    p->cap = 0;
+    const int64_t want = round_up(rows + rows / 8, 1024);
+    HIPCHK(hipMalloc(&p->d_group, (size_t)want * sizeof(int32_t)));
+    p->cap = want;
+  }
+  if (rows > 0) {
+    std::vector<int32_t> slice((size_t)rows, -1);
+    const int64_t have = std::min<int64_t>(rows, std::max<int64_t>((int64_t)g->group_of.size() - s->row_base, 0));
+    if (have > 0) memcpy(slice.data(), g->group_of.data() + s->row_base, (size_t)have * sizeof(int32_t));
+    HIPCHK(hipMemcpyAsync(p->d_group, slice.data(), (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s->aux_stream));
+    HIPCHK(hipStreamSynchronize(s->aux_stream));
+  }
+  p->built_rows.store(rows, std::memory_order_release);
+  return TSH_OK;
+}
+
+// shard g's part of a groups handle, current for the rows the shard has (caller holds s->mu shared and h->use_mu shared);
+// nullptr + *rc on failure.  As mask_part: appends take the shard exclusively, tsh_groups_set the handle, so no search
+// reads the buffer while it is rebuilt
+const GroupPart *groups_part(tsh_groups *h, size_t g, Shard *s, int *rc) {
+  *rc = TSH_OK;
+  GroupPart *p = h->parts[g].get();
+  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
+    *rc = groups_build_part(h, p, s);
+    if (*rc) return nullptr;
+  }
+  return p;
+}
+
+// group ids of a caller's array: negative (ungrouped) or below n_groups
+int check_group_ids(const int32_t *group_of, int64_t n, int32_t n_groups) {
+  for (int64_t i = 0; i < n; ++i)
+    if (group_of[i] >= n_groups) return set_err(TSH_E_BAD_ARG, "group_of[%lld] = %d is not below n_groups %d", (long long)i, group_of[i], n_groups);
   return TSH_OK;
 }
 
@@ -2726,6 +2890,11 @@ int32_t tsh_index_destroy(tsh_index *idx) {
       m->idx = nullptr;
     }
     idx->masks.clear();
+    for (tsh_groups *g : idx->groups) {  // groups handles the same way
+      for (auto &p : g->parts) groups_part_free(p.get());
+      g->idx = nullptr;
+    }
+    idx->groups.clear();
   }
   idx->workers.reset();  // joins the shard threads
   for (auto &s : idx->shards) {
@@ -2993,6 +3162,156 @@ int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out) {
     out[1] += sp->c_count_side.load();
     out[2] += sp->c_count_redone.load();
     out[3] += sp->c_count_nowindow.load();
+  }
+  return TSH_OK;
+}
+
+// ---- grouped search: the nearest row of each of the k nearest groups (tsh_group_rule.h) --------------------------------
+// (the handle travels as void *, and create's out as the address of one: see the header)
+int32_t tsh_groups_create(tsh_index *idx, const int32_t *group_of, int64_t n, int32_t n_groups, void *out_p) {
+  tsh_groups **out = static_cast<tsh_groups **>(out_p);
+  if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (n_groups < 0 || n_groups > GROUP_MAX_GROUPS) return set_err(TSH_E_BAD_ARG, "n_groups %d outside [0, %d]", n_groups, GROUP_MAX_GROUPS);
+  if (n < 0 || (n > 0 && !group_of)) return set_err(TSH_E_BAD_ARG, "group_of is NULL / n < 0");
+  int rc = check_group_ids(group_of, n, n_groups);
+  if (rc) return rc;
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  std::unique_ptr<tsh_groups> g(new tsh_groups());
+  g->idx = idx;
+  g->n_groups = n_groups;
+  try {
+    g->group_of.assign(group_of, group_of + n);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)n);
+  }
+  for (size_t i = 0; i < idx->shards.size(); ++i) g->parts.emplace_back(new GroupPart());
+  {
+    std::lock_guard<std::mutex> lk(g->mu);
+    for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
+      Shard *s = idx->shards[i].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      rc = groups_build_part(g.get(), g->parts[i].get(), s);
+    }
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    for (auto &p : g->parts) groups_part_free(p.get());
+    g_err = keep;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->groups.push_back(g.get());
+  }
+  *out = g.release();
+  return TSH_OK;
+}
+
+int32_t tsh_groups_set(void *groups, int64_t first_row_id, int64_t n, const int32_t *group_of) {
+  tsh_groups *g = static_cast<tsh_groups *>(groups);
+  if (!g) return set_err(TSH_E_BAD_ARG, "groups is NULL");
+  if (first_row_id < 0 || n < 0 || (n > 0 && !group_of)) return set_err(TSH_E_BAD_ARG, "group_of is NULL / negative row range");
+  std::lock_guard<std::mutex> hold(g_mask_mu);  // (the index cannot be destroyed under the call)
+  tsh_index *idx = g->idx;
+  if (!idx) return set_err(TSH_E_BAD_ARG, "the groups handle's index was destroyed");
+  int rc = check_group_ids(group_of, n, g->n_groups);
+  if (rc) return rc;
+  if (n == 0) return TSH_OK;
+  std::lock_guard<std::mutex> lk(idx->mu);  // as an append does
+  std::unique_lock<std::shared_mutex> xl(g->use_mu);
+  try {
+    if ((int64_t)g->group_of.size() < first_row_id + n) g->group_of.resize((size_t)(first_row_id + n), -1);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)(first_row_id + n));
+  }
+  memcpy(g->group_of.data() + first_row_id, group_of, (size_t)n * sizeof(int32_t));
+  for (auto &p : g->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next search of each shard
+  return TSH_OK;
+}
+
+int32_t tsh_groups_destroy(void *groups_p) {
+  tsh_groups *g = static_cast<tsh_groups *>(groups_p);
+  if (!g) return TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    if (tsh_index *idx = g->idx) {  // (an orphan's parts went with its index)
+      idx->groups.erase(std::remove(idx->groups.begin(), idx->groups.end(), g), idx->groups.end());
+      for (auto &p : g->parts) groups_part_free(p.get());
+    }
+  }
+  delete g;
+  return TSH_OK;
+}
+
+int32_t tsh_search_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const uint8_t *row_mask,
+                           tsh_mask *mask_h, void *groups_p, int64_t *out_ids, double *out_dist, int32_t *out_group,
+                           int32_t *out_count) {
+  tsh_groups *groups = static_cast<tsh_groups *>(groups_p);
+  if (row_mask && mask_h) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!groups) return set_err(TSH_E_BAD_ARG, "groups is NULL");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (groups->idx != idx) return set_err(TSH_E_BAD_ARG, "the groups handle was made for another index (or its index was destroyed)");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
+  if (nq == 0) return TSH_OK;
+  if (!queries || !out_count) return set_err(TSH_E_BAD_ARG, "queries / out_count is NULL");
+  for (int32_t q = 0; q < nq; ++q) out_count[q] = 0;
+  if (k <= 0) return TSH_OK;
+  if (!out_ids || !out_dist) return set_err(TSH_E_BAD_ARG, "out_ids / out_dist is NULL");
+  std::shared_lock<std::shared_mutex> use(groups->use_mu);  // the array stays as it is until the finaliser has read it
+  const size_t ns = idx->shards.size();
+  const int32_t entries = tsh_default_block_entries(k);
+  const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
+  std::vector<std::unique_ptr<uint8_t[]>> blocks(ns);
+  std::vector<std::vector<std::vector<BlockEntry>>> spills(ns), extras(ns);
+  int rc = for_each_shard(idx, [&](size_t g) -> int {
+    Shard *s = idx->shards[g].get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    if (s->rows == 0) return TSH_OK;
+    blocks[g].reset(new uint8_t[bb * (size_t)nq]);
+    spills[g].resize((size_t)nq);
+    extras[g].resize((size_t)nq);
+    SearchOut so;
+    so.h_blocks = blocks[g].get();
+    so.spill = &spills[g];
+    so.extra = &extras[g];
+    int prc = TSH_OK;
+    so.groups = groups_part(groups, g, s, &prc);
+    if (!so.groups) return prc;
+    MaskSrc ms;
+    int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
+    if (mrc) return mrc;
+    // (the pipeline of single-query scans, never the batched path)
+    return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
+  });
+  if (rc) return rc;
+  // groups span shards: the finaliser's step runs once per query over every shard's entries
+  const GroupTable table{groups->group_of.data(), (int64_t)groups->group_of.size()};
+  parallel_for(nq, [&](int32_t q) {
+    std::vector<EntryList> lists;
+    for (size_t g = 0; g < ns; ++g) {
+      if (!blocks[g]) continue;
+      EntryList two[2];
+      const size_t n_lists = shard_lists(blocks[g].get() + (size_t)q * bb, &spills[g][(size_t)q], &extras[g][(size_t)q], two);
+      lists.insert(lists.end(), two, two + n_lists);
+    }
+    out_count[q] = finalize_grouped(idx->metric, idx->dim, queries + (size_t)q * idx->dim, k, thr, lists.data(), lists.size(), table,
+                                    out_ids + (size_t)q * k, out_dist + (size_t)q * k, out_group ? out_group + (size_t)q * k : nullptr);
+  });
+  return TSH_OK;
+}
+
+int32_t tsh_search_grouped_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  for (auto &sp : idx->shards) {
+    out[0] += sp->c_grouped.load();
+    out[1] += sp->c_grouped_side.load();
+    out[2] += sp->c_grouped_redone.load();
+    out[3] += sp->c_grouped_nodev.load();
   }
   return TSH_OK;
 }

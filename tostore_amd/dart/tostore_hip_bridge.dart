@@ -122,6 +122,19 @@ typedef _SearchCountD = int Function(Pointer<Void>, Pointer<Float>, int, double,
     Pointer<Double>, Pointer<Int64>, Pointer<Int64>);
 typedef _SearchCountStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
 typedef _SearchCountStatsD = int Function(Pointer<Void>, Pointer<Int64>);
+// (the last argument is the address of the handle to fill: the header declares it void *)
+typedef _GroupsCreateC = Int32 Function(Pointer<Void>, Pointer<Int32>, Int64, Int32, Pointer<Void>);
+typedef _GroupsCreateD = int Function(Pointer<Void>, Pointer<Int32>, int, int, Pointer<Void>);
+typedef _GroupsSetC = Int32 Function(Pointer<Void>, Int64, Int64, Pointer<Int32>);
+typedef _GroupsSetD = int Function(Pointer<Void>, int, int, Pointer<Int32>);
+typedef _GroupsDestroyC = Int32 Function(Pointer<Void>);
+typedef _GroupsDestroyD = int Function(Pointer<Void>);
+typedef _SearchGroupedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchGroupedD = int Function(Pointer<Void>, Pointer<Float>, int, int, double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchGroupedStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchGroupedStatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
@@ -364,6 +377,11 @@ final class HipVectorBackend {
   static late final _SearchAfterStatsD _searchAfterStats;
   static late final _SearchCountD _searchCount;
   static late final _SearchCountStatsD _searchCountStats;
+  static late final _GroupsCreateD _groupsCreate;
+  static late final _GroupsSetD _groupsSet;
+  static late final _GroupsDestroyD _groupsDestroy;
+  static late final _SearchGroupedD _searchGrouped;
+  static late final _SearchGroupedStatsD _searchGroupedStats;
   static late final _ProbeScanI8D _probeScanI8;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
@@ -436,6 +454,12 @@ final class HipVectorBackend {
       _searchCount = lib.lookupFunction<_SearchCountC, _SearchCountD>('tsh_search_count');
       _searchCountStats =
           lib.lookupFunction<_SearchCountStatsC, _SearchCountStatsD>('tsh_search_count_stats');
+      _groupsCreate = lib.lookupFunction<_GroupsCreateC, _GroupsCreateD>('tsh_groups_create');
+      _groupsSet = lib.lookupFunction<_GroupsSetC, _GroupsSetD>('tsh_groups_set');
+      _groupsDestroy = lib.lookupFunction<_GroupsDestroyC, _GroupsDestroyD>('tsh_groups_destroy');
+      _searchGrouped = lib.lookupFunction<_SearchGroupedC, _SearchGroupedD>('tsh_search_grouped');
+      _searchGroupedStats =
+          lib.lookupFunction<_SearchGroupedStatsC, _SearchGroupedStatsD>('tsh_search_grouped_stats');
       _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
@@ -1019,6 +1043,84 @@ final class HipVectorBackend {
     }
   }
 
+  /// The group of every node id, for [searchGrouped] (tsh_groups_create): entry i of `groupOf` is the group of node
+  /// id i -- a document, a video, a product --, at least 0 and below `nGroups`, or negative for a row that stands for
+  /// itself; rows beyond the list are ungrouped.  The array crosses the FFI boundary once; [HipRowGroups.set] extends
+  /// it as rows are appended.  Dispose it before this backend.
+  HipRowGroups? createGroups(Int32List groupOf, int nGroups) {
+    final buf = calloc<Int32>(groupOf.isEmpty ? 1 : groupOf.length);
+    final out = calloc<Pointer<Void>>();
+    try {
+      buf.asTypedList(groupOf.length).setAll(0, groupOf);
+      final rc = _groupsCreate(_handle, buf, groupOf.length, nGroups, out.cast<Void>());
+      if (rc != 0) {
+        Logger.warn('tsh_groups_create failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return HipRowGroups._(out.value);
+    } finally {
+      calloc.free(buf);
+      calloc.free(out);
+    }
+  }
+
+  /// The nearest row of each of the `topK` nearest groups (tsh_search_grouped; no reference counterpart): the list
+  /// [search] would return with topK = infinity, every entry dropped whose group occurred earlier in it, cut to topK.
+  /// One scan, three passes over its keys and a handful of exact rows -- not one [searchAfter] page per long document.
+  /// Null on any native failure; a disposed [HipRowGroups] or [HipRowMask] is refused (null, with a warning), never
+  /// sent as NULL.
+  List<HipGroupedResult>? searchGrouped(Float32List query, int topK, HipRowGroups groups,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) {
+    if (groups._groups == nullptr) {
+      Logger.warn('searchGrouped with a disposed HipRowGroups', label: 'HipVectorBackend');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchGrouped with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (topK <= 0 || size == 0) return <HipGroupedResult>[];
+    final q = calloc<Float>(dimensions);
+    final ids = calloc<Int64>(topK);
+    final dist = calloc<Double>(topK);
+    final grp = calloc<Int32>(topK);
+    final cnt = calloc<Int32>();
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _searchGrouped(_handle, q, 1, topK, distanceThreshold ?? double.nan, maskBytes,
+          mask != null ? mask._mask : nullptr, groups._groups, ids, dist, grp, cnt);
+      if (rc != 0) {
+        Logger.warn('tsh_search_grouped failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return [for (var i = 0; i < cnt.value; ++i) HipGroupedResult(ids[i], dist[i], grp[i])];
+    } finally {
+      calloc.free(q);
+      calloc.free(ids);
+      calloc.free(dist);
+      calloc.free(grp);
+      calloc.free(cnt);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+  }
+
+  /// The grouped searches' counters (tsh_search_grouped_stats), per shard search: all of them, rows their side passes
+  /// sent to the side list, searches redone with a larger side list, searches answered without the device group passes.
+  Map<String, int>? searchGroupedStats() {
+    final o = calloc<Int64>(4);
+    try {
+      if (_searchGroupedStats(_handle, o) != 0) return null;
+      return {'searches': o[0], 'sideRows': o[1], 'redone': o[2], 'noDevicePasses': o[3]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
   /// Diagnostics for Logger (handler/logger.dart:8-60): rows, searches, candidates per query,
   /// resident bytes, safe mode / quarantined rows.
   Map<String, num>? counters() {
@@ -1469,6 +1571,43 @@ final class HipRowMask {
     if (_mask != nullptr) {
       HipVectorBackend._maskDestroy(_mask);
       _mask = nullptr;
+    }
+  }
+}
+
+/// One entry of [HipVectorBackend.searchGrouped]: a group's nearest row; `group` is -1 for a row that stands for itself.
+final class HipGroupedResult {
+  final int nodeId;
+  final double distance;
+  final int group;
+  const HipGroupedResult(this.nodeId, this.distance, this.group);
+}
+
+/// The group of every node id ([HipVectorBackend.createGroups], tsh_groups_create), kept by the library for as many
+/// grouped searches as it serves.  [set] extends or overwrites a range of entries, the companion of the append feed.
+/// Dispose it before its backend; a disposed handle is refused by [HipVectorBackend.searchGrouped] (null, with a
+/// warning), and one whose backend was disposed first is orphaned by the library and still safe to dispose.
+final class HipRowGroups {
+  Pointer<Void> _groups;
+
+  HipRowGroups._(this._groups);
+
+  /// Entries [firstNodeId, firstNodeId + groupOf.length) of the array; false on failure (or on a disposed handle).
+  bool set(int firstNodeId, Int32List groupOf) {
+    if (_groups == nullptr) return false;
+    final buf = calloc<Int32>(groupOf.isEmpty ? 1 : groupOf.length);
+    try {
+      buf.asTypedList(groupOf.length).setAll(0, groupOf);
+      return HipVectorBackend._groupsSet(_groups, firstNodeId, groupOf.length, buf) == 0;
+    } finally {
+      calloc.free(buf);
+    }
+  }
+
+  void dispose() {
+    if (_groups != nullptr) {
+      HipVectorBackend._groupsDestroy(_groups);
+      _groups = nullptr;
     }
   }
 }

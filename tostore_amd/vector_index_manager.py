@@ -23,7 +23,7 @@ from typing import Callable, Dict, Optional, Sequence
 
 import numpy as np
 
-from .backend import HipVectorBackend, HipVectorIndex
+from .backend import HipVectorBackend, HipVectorIndex, NghSearchResult
 from ._ffi import METRIC_COSINE, METRIC_IP, METRIC_L2
 
 
@@ -142,8 +142,11 @@ class VectorIndexManager:
     # -- query path -----------------------------------------------------------------
     def vectorSearch(self, queryVector: Sequence[float], topK: int = 10, efSearch: Optional[int] = None,
                      distanceThreshold: Optional[float] = None, rowMask=None,
-                     pk_of: Optional[Callable[[int], Optional[str]]] = None, after=None) -> list:
+                     pk_of: Optional[Callable[[int], Optional[str]]] = None, after=None, group_by=None) -> list:
         """ref: core/vector_index_manager.dart:475-589.
+        group_by (no reference counterpart): a HipGroups (`self.index.make_groups(group_of, n_groups)`: the document, video
+        or product of every node id) -- the answer holds one result per group, the nearest row of each of the topK nearest
+        groups (HipVectorIndex.search_grouped), in one scan.  Not together with `after`.
         after (no reference counterpart): a cursor (distance, nodeId), usually `(r.distance, r.nodeId)` of the last entry
         of the page before: the answer is the next topK rows past it in the result order (distance, then node id), so
         successive pages concatenate to the full list.  The node id form keeps working when that row has been deleted
@@ -165,8 +168,17 @@ class VectorIndexManager:
         search_query = query_f32
         if self.metric == METRIC_COSINE:  # :516-520
             search_query = normalize_float32(query_f32)
-        results = self.backend.search(query=search_query, topK=topK, efSearch=efSearch,
-                                      distanceThreshold=distanceThreshold, rowMask=rowMask, after=after)  # :538
+        if group_by is not None:
+            if after is not None:
+                raise ValueError("group_by and after cannot be combined: grouped searches have no cursor yet")
+            if topK <= 0:
+                return []
+            ids, dist, _, cnt = self.index.search_grouped(search_query, topK, group_by, distance_threshold=distanceThreshold,
+                                                          row_mask=rowMask)
+            results = [NghSearchResult(nodeId=int(ids[0, i]), distance=float(dist[0, i])) for i in range(int(cnt[0]))]
+        else:
+            results = self.backend.search(query=search_query, topK=topK, efSearch=efSearch,
+                                          distanceThreshold=distanceThreshold, rowMask=rowMask, after=after)  # :538
         if not results:  # :553
             return []
         sorted_by_node = sorted(results, key=lambda r: r.nodeId)  # :555-556
