@@ -53,6 +53,8 @@ extern "C" {
  *    tsh_search_shard_masked, tsh_search_shard_begin_masked, tsh_search_sharded_masked;
  *    tsh_search_count, tsh_search_count_stats;
  *    tsh_groups_create, tsh_groups_set, tsh_groups_destroy, tsh_search_grouped, tsh_search_grouped_stats. */
+/*    Additive since, same version, continued: tsh_search_grouped_after, tsh_search_grouped_count,
+ *    tsh_search_grouped_after_stats. */
 
 /* status codes */
 #define TSH_OK 0
@@ -455,8 +457,9 @@ int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out);
  *   caller's loop of tsh_search_after pages until k groups were seen (984 us at k = 10, 1258 at k = 100, 2 to 4 pages) it
  *   is 0.45 resp. 0.35, and it costs what tsh_search_count costs ("Grouped search";
  *   profiles/search_grouped_ab.json).
- * The next step would bring, none of it here: a cursor, so that groups can be paged.  More than one row per group.  A
- *   ticket form (tsh_search_submit_grouped).  The tsh_search_shard* and tsh_search_sharded* entries.  A count of groups.
+ * A cursor, so that groups can be paged, and a count of groups: tsh_search_grouped_after and tsh_search_grouped_count,
+ *   below.  The next step would bring, none of it here: more than one row per group.  A ticket form
+ *   (tsh_search_submit_grouped).  The tsh_search_shard* and tsh_search_sharded* entries.
  * tsh_counters keeps its layout; a grouped search counts in searches and scan_launches like any other search.
  * The handle is a tsh_groups * (typedef below).  In the prototypes it travels as `void *`, and tsh_groups_create's
  * `out` -- the address of the caller's tsh_groups * (a tsh_groups **) -- as `void *` too: the bindings' prototype tables
@@ -472,6 +475,67 @@ int32_t tsh_search_grouped(tsh_index *idx, const float *queries, int32_t nq, int
 /* out[0] grouped searches, out[1] rows sent to the side list, out[2] searches redone with a larger side list,
  * out[3] searches answered without the device group passes (safe mode); summed over the shards */
 int32_t tsh_search_grouped_stats(tsh_index *idx, int64_t *out);
+
+/* ---- grouped search behind a cursor, and a count of groups (additive since ABI 5) ------------------------------------
+ * L and G as above: G is L with every entry removed whose group occurred earlier, under the same row mask (pointer or
+ * handle, at most one), tombstones, gaps, quarantined rows and distance_threshold.
+ *
+ * tsh_search_grouped_after takes tsh_search_grouped's arguments and a cursor per query (after_dist / after_id, nq
+ * each).  It returns the first k entries of G that follow (after_dist[q], after_id[q]) strictly, in tsh_search_after's
+ * order (double.compareTo on the distance, ties by id).  A cursor of -inf is "from the start" and equals
+ * tsh_search_grouped bit for bit.  Successive pages, each started from the last entry of the page before, concatenate
+ * to exactly G; a page shorter than k is the last.  The cursor need not name an existing row.  A group whose best row
+ * is at or before the cursor is consumed: none of its rows comes back, those past the cursor included -- which is what
+ * tsh_search_after pages with the repeated groups dropped by the caller cannot give without remembering every group
+ * shown.  Unused slots and out_group behave as in tsh_search_grouped.  A NULL cursor array is TSH_E_BAD_ARG; the other
+ * argument errors and the trivial cases are the grouped search's.
+ *
+ * tsh_search_grouped_count: out_count[q] is the number of entries of G (k = infinity) that pass the threshold exactly
+ * as the finaliser applies it (tsh_search_count's words) and, with a cursor, follow it.  after_dist == after_id == NULL:
+ * no cursor; exactly one NULL is TSH_E_BAD_ARG.  After any page, count(after = the page's last entry) == count(no
+ * cursor) - entries of G returned so far.
+ *
+ * How (tostore_amd/csrc/tsh_group_after_rule.h has the rules and their proof, tsh_group.hip.h the kernels): the head
+ * table is built over all live rows, whatever the cursor; a group is classified by its head's f32 key against the
+ * cursor's floor keys (resp. the count's window) -- certainly after the cursor: today's grouped rules; certainly before
+ * it: consumed, none of its rows goes anywhere; undecided: the head and the group's rows within the head's band get
+ * their exact distances and the finaliser decides.  Several queries per call run as the pipeline of single-query f32
+ * tile scans or list scans, never the batched path, the fp16 / int8 copies or the exact path.  A +inf or NaN cursor runs
+ * no scan (no scanned row follows it).
+ *
+ * The exact-all route.  The per-shard rule does not hold (a) for a handle over several devices whose groups have rows
+ * in the row ranges of two shards -- one shard consumes a group while another offers one of its rows; found on the host
+ * by one pass over the array whenever it is given or changed (tsh_groups_create, tsh_groups_set) -- and (b) while a
+ * shard holds a live quarantined row: such rows are not in the head table, yet can be a group's best or consume it;
+ * looked at per call under the shard locks.  Every shard's job of such a call then runs as safe mode does: no device
+ * group passes, every live row's exact sums reach the finaliser, which then IS the specification.  This route is slow
+ * -- the exact distance of every live row per query -- and exact.  The cheaper follow-up, not built here: flag the few
+ * open groups (spanning, or holding a quarantined row) in the device copy of group_of, so that only their rows go to
+ * the side list.
+ *
+ * Shard handles: the answer is for the shard's own rows, as if they were the whole index.  The ranks' merged pages
+ * (concatenate, order, drop repeated groups, cut to k) are exact ONLY when no group has rows on two ranks: with a cursor,
+ * a group consumed on one rank can reappear from another.  The tsh_search_shard* / tsh_search_sharded* forms stay out
+ * of scope.
+ *
+ * tsh_search_grouped_after_stats, summed over the shards (a job counts once per shard): out[0] grouped cursor searches,
+ * out[1] group counts, out[2] rows sent to the side list, out[3] jobs redone with a larger side list, out[4] jobs
+ * answered by the exact-all route (safe mode's jobs included: they run the same way).  These jobs move NONE of
+ * tsh_search_grouped_stats, tsh_search_after_stats and tsh_search_count_stats, which keep their meaning for their own
+ * entries; tsh_counters counts them in searches and scan_launches like any other search.
+ * Cost: a page costs one grouped search at any depth -- measured on 1 M x 768, L2, 64-query calls, per query: pages 1, 2
+ * and 10 at 453.2 / 453.4 / 453.7 us (k = 10) and 453.9 / 454.0 / 454.2 us (k = 100) against 453.0 / 453.6 us of
+ * tsh_search_grouped in the same run, and against 999 / 1237 / 1485 us (k = 10) of the caller's loop of tsh_search_after
+ * pages with repeated groups dropped on the host, which grows with depth; a group count 469.9 us against 453.4 us of
+ * tsh_search_count ("grouped search behind a cursor"; profiles/search_grouped_after_ab.json). */
+int32_t tsh_search_grouped_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double distance_threshold,
+                                 const uint8_t *row_mask, tsh_mask *mask, void *groups,
+                                 const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                                 double *out_dist, int32_t *out_group, int32_t *out_count);
+int32_t tsh_search_grouped_count(tsh_index *idx, const float *queries, int32_t nq, double distance_threshold,
+                                 const uint8_t *row_mask, tsh_mask *mask, void *groups,
+                                 const double *after_dist, const int64_t *after_id, int64_t *out_count);
+int32_t tsh_search_grouped_after_stats(tsh_index *idx, int64_t *out);
 
 /* ---- row-sharded deployments (one process per GPU) ----------------------
  * Each rank scans its shard and emits, per query, one fixed-size candidate

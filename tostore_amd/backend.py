@@ -407,6 +407,73 @@ class HipVectorIndex:
         _ffi.check(_ffi.lib().tsh_search_grouped_stats(self._h, out))
         return {"searches": out[0], "side_rows": out[1], "redone": out[2], "no_device_passes": out[3]}
 
+    def search_grouped_after(self, queries, k: int, groups: "HipGroups", after, distance_threshold: Optional[float] = None, row_mask=None):
+        """The next k groups past a cursor: (ids[nq,k], dist[nq,k], group[nq,k], count[nq]) like search_grouped(), holding
+        the first k entries of the grouped list that are strictly greater than the cursor.  A group whose best row is at
+        or before the cursor is consumed: none of its rows comes back.  after: as search_after() takes it; the last entry
+        of the page before continues the list, (-inf, anything) starts it -- search_grouped()'s answer.  A page shorter
+        than k is the last one.  row_mask: None, a byte mask or a HipMask."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be nq x {self.dim}")
+        if not isinstance(groups, HipGroups):
+            raise TypeError("groups must be a HipGroups (HipVectorIndex.make_groups)")
+        nq, kk = q.shape[0], max(int(k), 0)
+        a_dist = np.ascontiguousarray(np.broadcast_to(np.asarray(after[0], dtype=np.float64).reshape(-1), (nq,)))
+        a_id = np.ascontiguousarray(np.broadcast_to(np.asarray(after[1], dtype=np.int64).reshape(-1), (nq,)))
+        ids = np.empty((nq, max(kk, 1)), dtype=np.int64)
+        dist = np.empty((nq, max(kk, 1)), dtype=np.float64)
+        grp = np.empty((nq, max(kk, 1)), dtype=np.int32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        thr = math.nan if distance_threshold is None else float(distance_threshold)
+        handle, mp = None, None
+        if isinstance(row_mask, HipMask):
+            handle = row_mask.handle()
+        else:
+            row_mask, mp = self.mask_arg(row_mask)
+        _ffi.check(_ffi.lib().tsh_search_grouped_after(self._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp, handle, groups.handle(),
+                                                       a_dist.ctypes.data_as(_ffi.p_f64), a_id.ctypes.data_as(_ffi.p_i64),
+                                                       ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                       grp.ctypes.data_as(_ffi.p_i32), cnt.ctypes.data_as(_ffi.p_i32)))
+        return ids[:, :kk], dist[:, :kk], grp[:, :kk], cnt
+
+    def count_groups(self, queries, groups: "HipGroups", distance_threshold: Optional[float] = None, row_mask=None, after=None) -> np.ndarray:
+        """How many entries search_grouped_after() would return with k = infinity: count[nq] (int64), under the same
+        threshold, mask, tombstones and cursor.  after: None for the whole grouped list, or a cursor; count(after = a page's
+        last entry) is count(None) minus the entries returned so far."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be nq x {self.dim}")
+        if not isinstance(groups, HipGroups):
+            raise TypeError("groups must be a HipGroups (HipVectorIndex.make_groups)")
+        nq = q.shape[0]
+        a_dist = a_id = pd = pi = None
+        if after is not None:
+            a_dist = np.ascontiguousarray(np.broadcast_to(np.asarray(after[0], dtype=np.float64).reshape(-1), (nq,)))
+            a_id = np.ascontiguousarray(np.broadcast_to(np.asarray(after[1], dtype=np.int64).reshape(-1), (nq,)))
+            pd, pi = a_dist.ctypes.data_as(_ffi.p_f64), a_id.ctypes.data_as(_ffi.p_i64)
+        cnt = np.zeros(nq, dtype=np.int64)
+        thr = math.nan if distance_threshold is None else float(distance_threshold)
+        handle, mp = None, None
+        if isinstance(row_mask, HipMask):
+            handle = row_mask.handle()
+        else:
+            row_mask, mp = self.mask_arg(row_mask)
+        _ffi.check(_ffi.lib().tsh_search_grouped_count(self._h, q.ctypes.data_as(_ffi.p_f32), nq, thr, mp, handle, groups.handle(), pd, pi,
+                                                       cnt.ctypes.data_as(_ffi.p_i64)))
+        return cnt
+
+    def search_grouped_after_stats(self) -> dict:
+        """The grouped cursor searches' and group counts' counters, per shard job: the searches, the counts, rows sent to the
+        side list, jobs redone with a larger side list, jobs answered by the exact-all route."""
+        out = (ctypes.c_int64 * 5)()
+        _ffi.check(_ffi.lib().tsh_search_grouped_after_stats(self._h, out))
+        return {"searches": out[0], "counts": out[1], "side_rows": out[2], "redone": out[3], "exact_all": out[4]}
+
     # -- asynchronous single-query form (several queries in flight) -----------------
     def submit(self, query, k: int, row_mask=None, after=None) -> tuple:
         """after: a (distance, id) cursor -- the ticket answers search_after() instead of search()."""

@@ -28,6 +28,7 @@
 
 #include <cstdint>
 
+#include "tsh_group_after_rule.h"
 #include "tsh_group_rule.h"
 #include "tsh_kernels.hip.h"
 
@@ -138,6 +139,137 @@ static __global__ void __launch_bounds__(256) group_side_kernel(GroupSideArgs s)
       const uint32_t pos = base + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
       if (pos < s.side_cap) s.side_rows[pos] = a.list ? a.list[(int64_t)t * 64 + lane] : (uint32_t)((int64_t)t * 64 + lane);
     }
+  }
+}
+
+// ---- grouped cursor searches and group counts (tsh_search_grouped_after, tsh_search_grouped_count) ----------------------
+// The rules and their proof are in tsh_group_after_rule.h.  G1 runs unchanged -- the head table is built over ALL live
+// rows, whatever the cursor: a group whose best row is at or before the cursor is consumed, rows past the cursor included --
+// and the passes below take the places of G2 and G3, or of select, re-rank and G3 altogether for a count:
+//   G2a group_heads_after_kernel   G2 with the cursor's floor keys: a head certainly AFTER the cursor keeps its key in the
+//                                  heads array, a head certainly BEFORE it becomes KEY_DEAD (its group is consumed), an
+//                                  AMBIGUOUS head becomes KEY_DEAD and its id goes to the side list.
+//   G3a group_side_after_kernel    G3 with the floor keys: rows of an AFTER group are SIDE as in G3, rows of a BEFORE group
+//                                  go nowhere, rows of an AMBIGUOUS group at or below band_of(head key) go to the side
+//                                  list whatever the select's band says.
+//   GC  group_count_window_kernel  count_window_kernel's shape (four tiles per wave, one LDS-reduced atomic per workgroup,
+//                                  for the reason written there) over heads: a head certainly IN the window counts one
+//                                  group, a head certainly OUT none; an AMBIGUOUS head and its group's rows at or below
+//                                  band_of(head key) go to the side list.
+// All of them draw places in the context's one side list through the job's one count word (a ballot, one atomic per tile
+// that has such rows); after_side_kernel / count_side_kernel take the exact sums.  Every branch around a ballot or a
+// shuffle is wave-uniform (a wave's tile, a tile's gmin).
+
+// the lanes with `side` set append `row` to the side list: ids past the capacity are counted, not written
+__device__ __forceinline__ void group_side_push(bool side, uint32_t row, int lane, uint32_t *side_rows, uint32_t *side_count, uint32_t side_cap) {
+  const uint64_t bm = __ballot(side);
+  if (bm) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(side_count, (uint32_t)__popcll(bm));
+    base = (uint32_t)__shfl((int)base, 0);
+    if (side) {
+      const uint32_t pos = base + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
+      if (pos < side_cap) side_rows[pos] = row;
+    }
+  }
+}
+
+struct GroupHeadsAfterArgs {
+  GroupArgs g;
+  uint32_t *side_rows;   // local ids of the AMBIGUOUS heads, side_cap of them at most
+  uint32_t *side_count;  // all of them, written or not
+  uint32_t side_cap;
+  uint32_t floor_lo, floor_hi;  // AfterFloor
+};
+
+// G2a
+static __global__ void __launch_bounds__(256) group_heads_after_kernel(GroupHeadsAfterArgs h) {
+  const GroupArgs &a = h.g;
+  const int lane = threadIdx.x & 63;
+  const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
+  if (t >= a.n_tiles) return;
+  const int64_t i = (int64_t)t * 64 + lane;
+  if (a.gmin[t] == KEY_DEAD) {
+    a.heads[i] = KEY_DEAD;
+    if (lane == 0) a.hmin[t] = KEY_DEAD;
+    return;
+  }
+  const GroupPos p = group_pos(a, t, lane);
+  const bool head = p.live && group_is_head(p.grouped, p.word, p.grouped ? a.gm[p.group] : 0ull);
+  const int cls = group_after_class(p.key, h.floor_lo, h.floor_hi);
+  const uint32_t hk = head && cls == GROUP_AFTER ? p.key : KEY_DEAD;
+  a.heads[i] = hk;
+  group_side_push(head && cls == GROUP_AMBIGUOUS, a.list ? a.list[i] : (uint32_t)i, lane, h.side_rows, h.side_count, h.side_cap);
+  const uint32_t m = wave_min_u32(hk);
+  if (lane == 0) a.hmin[t] = m;
+}
+
+struct GroupSideAfterArgs {
+  GroupSideArgs s;
+  uint32_t floor_lo, floor_hi;  // AfterFloor
+};
+
+// G3a
+static __global__ void __launch_bounds__(256) group_side_after_kernel(GroupSideAfterArgs sa) {
+  const GroupSideArgs &s = sa.s;
+  const GroupArgs &a = s.g;
+  const int lane = threadIdx.x & 63;
+  const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
+  if (t >= a.n_tiles) return;
+  if (a.gmin[t] == KEY_DEAD) return;
+  const uint32_t select_band = s.hdr->band_key;
+  // (an AMBIGUOUS group's head key is at most floor_hi, band_of is monotone: no row above both bands can be wanted)
+  const uint32_t floor_band = band_of(sa.floor_hi, s.eps_rel, s.delta_abs);
+  const GroupPos p = group_pos(a, t, lane);
+  bool side = false;
+  if (p.grouped && (p.key <= select_band || p.key <= floor_band)) {
+    const unsigned long long hw = a.gm[p.group];
+    const uint32_t hk = group_word_key(hw);
+    side = hw != p.word &&
+           group_after_side(group_after_class(hk, sa.floor_lo, sa.floor_hi), p.key, band_of(hk, s.eps_rel, s.delta_abs), select_band);
+  }
+  group_side_push(side, a.list ? a.list[(int64_t)t * 64 + lane] : (uint32_t)((int64_t)t * 64 + lane), lane, s.side_rows, s.side_count, s.side_cap);
+}
+
+struct GroupCountArgs {
+  GroupArgs g;           // (heads / hmin unused)
+  uint32_t *side_rows;   // local ids of the AMBIGUOUS groups' rows, side_cap of them at most
+  uint32_t *side_count;  // all of them, written or not
+  uint32_t *certain;     // the groups certainly IN
+  uint32_t side_cap;
+  uint32_t in_lo, in_hi, out_lo, out_hi;  // CountWindow
+  float eps_rel, delta_abs;
+};
+
+constexpr int GROUP_COUNT_WAVE_TILES = 4;  // as COUNT_WAVE_TILES (tsh_count.hip.h)
+
+// GC
+static __global__ void __launch_bounds__(256) group_count_window_kernel(GroupCountArgs c) {
+  __shared__ uint32_t s_in[4];
+  const GroupArgs &a = c.g;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int t0 = (int)(blockIdx.x * 4u + (uint32_t)wave) * GROUP_COUNT_WAVE_TILES;  // a wave's first tile: wave-uniform
+  uint32_t n_in = 0;
+#pragma unroll
+  for (int u = 0; u < GROUP_COUNT_WAVE_TILES; ++u) {
+    const int t = t0 + u;
+    if (t >= a.n_tiles) break;
+    if (a.gmin[t] == KEY_DEAD) continue;
+    const GroupPos p = group_pos(a, t, lane);
+    const unsigned long long hw = p.grouped ? a.gm[p.group] : p.word;  // (ungrouped: its own head)
+    const bool head = p.live && hw == p.word;
+    const uint32_t hk = group_word_key(hw);
+    const int cls = group_count_class(hk, c.in_lo, c.in_hi, c.out_lo, c.out_hi);
+    const bool in = head && cls == 0;
+    const bool side = p.live && cls == 2 && (head || p.key <= band_of(hk, c.eps_rel, c.delta_abs));
+    n_in += (uint32_t)__popcll(__ballot(in));
+    group_side_push(side, a.list ? a.list[(int64_t)t * 64 + lane] : (uint32_t)((int64_t)t * 64 + lane), lane, c.side_rows, c.side_count, c.side_cap);
+  }
+  if (lane == 0) s_in[wave] = n_in;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t sum = s_in[0] + s_in[1] + s_in[2] + s_in[3];
+    if (sum) atomicAdd(c.certain, sum);
   }
 }
 

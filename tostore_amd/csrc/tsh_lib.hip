@@ -324,6 +324,10 @@ struct Shard {
   // grouped searches (tsh_search_grouped_stats): all of them, rows their side passes sent to the side list, searches redone
   // with a larger side list, searches answered without the device group passes (safe mode)
   std::atomic<int64_t> c_grouped{0}, c_grouped_side{0}, c_grouped_redone{0}, c_grouped_nodev{0};
+  // grouped cursor searches and group counts (tsh_search_grouped_after_stats): the searches, the counts, rows their passes
+  // sent to the side list, jobs redone with a larger side list, jobs answered by the exact-all route.  These jobs move
+  // none of the counters above
+  std::atomic<int64_t> c_gafter{0}, c_gcount{0}, c_gafter_side{0}, c_gafter_redone{0}, c_gafter_all{0};
   int cus = 0;  // compute units of the shard's device (grid of the persistent key kernels)
   std::atomic<int> f16_strikes{0};      // batched calls in a row whose fp16 bands overflowed many candidate lists
   std::atomic<int> f16_denied_calls{0};  // auto key-kernel choice: bf16x3 instead of fp16 for this many more batched calls
@@ -1006,6 +1010,11 @@ struct Job {
   // reaches the finaliser (grouping without grouped)
   bool grouping = false, grouped = false;
   const GroupPart *gpart = nullptr;
+  // a grouped cursor search or a group count (JobReq::group_after; tsh_group_after_rule.h): grouped and floored, or grouped
+  // and windowed -- G1, then the passes with the floor resp. the window pass in the places of G2 / G3 resp. select and
+  // re-rank.  exact_all: the rule does not hold for this call (JobReq::exact_all): a plain search job whose every live
+  // row reaches the finaliser, as in safe mode
+  bool group_after = false, exact_all = false;
   const float *redo_query = nullptr;  // the caller's query (a ticket's own copy): valid until the job is finished
   std::vector<uint64_t> redo_words;   // a ticket's copy of a pointer mask's words (JobReq::mask_dies), else empty
 };
@@ -1442,6 +1451,8 @@ struct JobReq {
   bool count = false;             // a count (tsh_search_count): how many rows pass count_thr and follow `after`, if given
   double count_thr = 0;           // ... its threshold (NaN: none)
   const GroupPart *groups = nullptr;  // a grouped search (tsh_search_grouped): this shard's part of the groups handle
+  bool group_after = false;       // ... of tsh_search_grouped_after / tsh_search_grouped_count: `after` resp. `count` hold for GROUPS
+  bool exact_all = false;         // ... whose rule does not hold for this call: every live row's exact sums for the finaliser
   bool mask_dies = false;         // ... enqueued for a ticket: a pointer mask's words and list are gone before the job is finished
 };
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
@@ -1696,6 +1707,44 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     TSH_LAUNCH_EV(exact_pick_kernel, (unsigned)((xp.n_entries + 255) / 256), 256, ts, none, done, xp);
   } else if (j->route.exact || i8) {
     TSH_LAUNCH_EV(exact_select_kernel, 1, 1024, ts, none, done, j->xsel);
+  } else if (j->windowed && j->grouped) {
+    // a group count: the head table cleared, every group's head found (G1); the window pass classifies the heads, counts
+    // the groups certainly in the list and sends the rows of the groups it could not decide to the side list (GC); their
+    // exact sums by the count jobs' side re-rank (C2) -- tsh_group.hip.h.  No select, no re-rank
+    const GroupPart *gp = j->gpart;
+    const int32_t n_tiles = ka.se.n_tiles;
+    const uint32_t side_cap = (uint32_t)c->side_cap;
+    uint32_t *const side_count = c->d_side_cnt + j->side_word;
+    const CountWindow &w = j->window;
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, nullptr, nullptr, gp->built_rows.load(), gp->n_groups, n_tiles};
+    if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
+    group_min_kernel<<<(unsigned)((n_tiles + 3) / 4), 256, 0, ts>>>(ga);
+    const GroupCountArgs gc{ga, c->d_side_rows, side_count, c->d_side_cnt + 2, side_cap, w.in_lo, w.in_hi, w.out_lo, w.out_hi, ka.se.eps_rel, ka.se.delta_abs};
+    group_count_window_kernel<<<(unsigned)((n_tiles + 4 * GROUP_COUNT_WAVE_TILES - 1) / (4 * GROUP_COUNT_WAVE_TILES)), 256, 0, ts>>>(gc);
+    const CountSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->d_side_cnt + 2, c->h_side_dev,
+                           s->ld, s->row_base, s->dim, s->metric, side_cap};
+    TSH_LAUNCH_EV(count_side_kernel, std::min(side_cap, 1024u), 64, ts, none, done, sd);
+  } else if (j->grouped && j->floored) {
+    // a grouped cursor search: G1 as ever -- over all live rows, whatever the cursor --, then the heads pass and the side
+    // pass with the cursor's floor keys (G2a, G3a) around the unchanged select and re-rank -- tsh_group.hip.h.  Both
+    // passes draw places in the one side list through the job's one count word
+    const GroupPart *gp = j->gpart;
+    const int32_t n_tiles = ka.se.n_tiles;
+    const unsigned tgrid = (unsigned)((n_tiles + 3) / 4);
+    const uint32_t side_cap = (uint32_t)c->side_cap;
+    uint32_t *const side_count = c->d_side_cnt + j->side_word;
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
+    if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
+    group_min_kernel<<<tgrid, 256, 0, ts>>>(ga);
+    const GroupHeadsAfterArgs gh{ga, c->d_side_rows, side_count, side_cap, j->floor.lo, j->floor.hi};
+    group_heads_after_kernel<<<tgrid, 256, 0, ts>>>(gh);
+    launch_select(ka.se, n_tiles, ts);
+    TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, none, ka.ra);
+    const GroupSideAfterArgs gs{GroupSideArgs{ga, ka.se.hdr, c->d_side_rows, side_count, side_cap, ka.se.eps_rel, ka.se.delta_abs}, j->floor.lo, j->floor.hi};
+    group_side_after_kernel<<<tgrid, 256, 0, ts>>>(gs);
+    const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
+                           s->dim, s->metric, side_cap};
+    TSH_LAUNCH_EV(after_side_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, ts, none, done, sd);
   } else if (j->windowed) {
     // a count job: the window pass counts the rows certainly in the list (C1), the rows it could not decide get their
     // exact sums (C2) -- tsh_count.hip.h.  No select, no re-rank
@@ -1809,8 +1858,13 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   j->certain = 0;
   j->grouping = rq.groups != nullptr;
   j->gpart = rq.groups;
+  j->group_after = rq.group_after;
+  j->exact_all = rq.exact_all;
   const Route &r = j->route =
       choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after || rq.count || j->grouping);
+  // (the exact-all route of a grouped cursor search or group count: what safe mode runs -- no floor, no window, no group
+  // passes below, and the wide-band pass hands every live row's exact sums to the finaliser)
+  if (rq.exact_all) j->route.band.force_all = 1;
   // A cursor inside the error model gets its floor in the scan's key space (tsh_after_band.h); "from the start" has
   // none; a +inf or NaN cursor can only be followed by quarantined rows -- every row the scan offers has a finite
   // distance -- so no scan runs at all.  Safe mode: no floor, the finaliser filters.
@@ -1838,7 +1892,10 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   float *q;
   int rc = job_stage(s, j, rq, &ka, &q);
   if (rc) return rc;
-  if (j->after_skip) return enqueue_after_skip(s, j, rq, q);
+  if (j->after_skip) {
+    j->grouped = false;  // (a grouped cursor search or group count no scanned row can follow: no group passes, no side list)
+    return enqueue_after_skip(s, j, rq, q);
+  }
   if (j->grouped && (rc = ctx_reserve_group(c, rq.groups->n_groups))) return rc;
   if (j->floored || j->windowed || j->grouped) {
     if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(rq.side_want, AFTER_SIDE_CAP), c->side_cap)))) return rc;
@@ -2085,7 +2142,7 @@ int redo_after_side(Shard *s, Job *j) {
   const int64_t n = c->h_side[0].id;
   if (n <= c->side_cap) return TSH_OK;
   if (j->after_redone) return set_err(TSH_E_HIP, "a cursor search's side list overflowed twice (%lld rows): internal error", (long long)n);
-  (j->grouping ? s->c_grouped_redone : j->counting ? s->c_count_redone : s->c_after_redone)++;
+  (j->group_after ? s->c_gafter_redone : j->grouping ? s->c_grouped_redone : j->counting ? s->c_count_redone : s->c_after_redone)++;
   const Cursor cur = j->after;
   JobReq rq(j->redo_query, j->k, j->entries);
   rq.mask = j->redo_mask;
@@ -2097,6 +2154,8 @@ int redo_after_side(Shard *s, Job *j) {
   rq.count = j->counting;
   rq.count_thr = j->count_thr;
   rq.groups = j->gpart;
+  rq.group_after = j->group_after;
+  rq.exact_all = j->exact_all;
   rq.side_want = round_up(n, 1024);
   int rc = job_enqueue(s, j, rq);
   if (j->counted) {
@@ -2182,7 +2241,10 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     extra->clear();
     for (uint32_t i : j->quar_sel) extra->push_back(c->h_quar[i]);
   }
-  if (j->grouping) {
+  if (j->group_after) {
+    (j->counting ? s->c_gcount : s->c_gafter)++;
+    if (j->route.band.force_all) s->c_gafter_all++;
+  } else if (j->grouping) {
     s->c_grouped++;
     if (!j->grouped) s->c_grouped_nodev++;
   } else if (j->counting) {
@@ -2199,7 +2261,7 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     if (j->quar_sel.empty()) extra->clear();
     const uint32_t side_n = (uint32_t)c->h_side[0].id;
     extra->insert(extra->end(), c->h_side + 1, c->h_side + 1 + side_n);
-    (j->grouped ? s->c_grouped_side : j->windowed ? s->c_count_side : s->c_after_side) += side_n;
+    (j->group_after ? s->c_gafter_side : j->grouped ? s->c_grouped_side : j->windowed ? s->c_count_side : s->c_after_side) += side_n;
     if (j->windowed) j->certain = (int64_t)c->h_side[0].s0;
   }
   s->c_searches++;
@@ -2267,6 +2329,11 @@ struct SearchOut {
   double count_thr = 0;
   // ... host mode, a grouped search (tsh_search_grouped): this shard's part of the groups handle
   const GroupPart *groups = nullptr;
+  // ... a grouped cursor search or a group count (tsh_search_grouped_after, tsh_search_grouped_count): `after` and
+  // `count_out` hold for groups.  A group count leaves count_out[q] = the groups counted on the device only, and blocks,
+  // spill and extra to the caller: groups may span shards, so the group-count step runs once over every shard's entries.
+  // exact_all: JobReq::exact_all for every job of the call
+  bool group_after = false, exact_all = false;
 };
 
 // One submitting thread's share of a multi-query call: queries [q0, q1) of the call, at most
@@ -2305,6 +2372,8 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       rq.count = out->count_out != nullptr;
       rq.count_thr = out->count_thr;
       rq.groups = out->groups;
+      rq.group_after = out->group_after;
+      rq.exact_all = out->exact_all;
       rc = job_enqueue(s, &j, rq);
       if (rc) {
         release_all();
@@ -2323,7 +2392,9 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       return rc;
     }
     if (out->h_blocks) memcpy(out->h_blocks + (size_t)q * bb, j.c->h_block, bb);
-    if (out->count_out) {  // the rows counted on the device, and whatever reached the host with its exact sums
+    if (out->count_out && out->group_after) {
+      out->count_out[q] = j.certain;
+    } else if (out->count_out) {  // the rows counted on the device, and whatever reached the host with its exact sums
       EntryList two[2];
       const size_t n_lists = shard_lists(j.c->h_block, sp, ex, two);
       Cursor cur;
@@ -2553,6 +2624,10 @@ struct tsh_groups {
   std::shared_mutex use_mu;  // searches: shared, for the whole call; tsh_groups_set: exclusive
   std::mutex mu;             // builds / rebuilds of the parts
   std::vector<std::unique_ptr<GroupPart>> parts;  // one per shard of the index
+  // does a group have rows in the row ranges of two shards?  (groups_update_spans: set with the array -- by create, and by
+  // tsh_groups_set, which marks every part for its rebuild -- and read by the grouped cursor searches and group counts,
+  // whose per-shard rule does not hold then: tsh_group_after_rule.h)
+  bool spans = false;
 };
 
 namespace {
@@ -2730,6 +2805,27 @@ const GroupPart *groups_part(tsh_groups *h, size_t g, Shard *s, int *rc) {
     if (*rc) return nullptr;
   }
   return p;
+}
+
+// tsh_groups::spans: one pass over the array against the shards' row ranges.  A multi-device index cuts its rows at
+// multiples of rows_per_shard whatever the shards hold yet, so the answer changes with the array only, never with an
+// append (a group that will span once rows named in the array arrive counts as spanning already: exact, only slower)
+void groups_update_spans(tsh_groups *g) {
+  g->spans = false;
+  const tsh_index *idx = g->idx;
+  if (!idx || idx->shards.size() < 2 || idx->rows_per_shard <= 0) return;
+  const int64_t last = (int64_t)idx->shards.size() - 1;
+  std::vector<int32_t> first((size_t)g->n_groups, -1);
+  for (size_t i = 0; i < g->group_of.size(); ++i) {
+    const int32_t gi = g->group_of[i];
+    if (gi < 0 || gi >= g->n_groups) continue;
+    const int32_t sh = (int32_t)std::min<int64_t>((int64_t)i / idx->rows_per_shard, last);
+    if (first[(size_t)gi] < 0) first[(size_t)gi] = sh;
+    else if (first[(size_t)gi] != sh) {
+      g->spans = true;
+      return;
+    }
+  }
 }
 
 // group ids of a caller's array: negative (ungrouped) or below n_groups
@@ -3187,6 +3283,11 @@ int32_t tsh_groups_create(tsh_index *idx, const int32_t *group_of, int64_t n, in
     return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)n);
   }
   for (size_t i = 0; i < idx->shards.size(); ++i) g->parts.emplace_back(new GroupPart());
+  try {
+    groups_update_spans(g.get());
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %d groups' shards", n_groups);
+  }
   {
     std::lock_guard<std::mutex> lk(g->mu);
     for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
@@ -3227,6 +3328,11 @@ int32_t tsh_groups_set(void *groups, int64_t first_row_id, int64_t n, const int3
     return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)(first_row_id + n));
   }
   memcpy(g->group_of.data() + first_row_id, group_of, (size_t)n * sizeof(int32_t));
+  try {
+    groups_update_spans(g);
+  } catch (...) {
+    g->spans = true;  // (no memory for the pass: the exact-all route is always right)
+  }
   for (auto &p : g->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next search of each shard
   return TSH_OK;
 }
@@ -3312,6 +3418,143 @@ int32_t tsh_search_grouped_stats(tsh_index *idx, int64_t *out) {
     out[1] += sp->c_grouped_side.load();
     out[2] += sp->c_grouped_redone.load();
     out[3] += sp->c_grouped_nodev.load();
+  }
+  return TSH_OK;
+}
+
+// ---- grouped cursor search and group count (tsh_group_after_rule.h) ------------------------------------------------------
+namespace {
+
+// Does this call take the exact-all route?  Groups with rows on several shards (the handle's flag), or a shard holding a
+// live quarantined row (deleted ones are off the list: set_deleted), looked at under each shard's lock.  The shards' jobs
+// look again under the lock they run under, so an append in between cannot slip a quarantined row past its own shard --
+// and where groups stay inside a shard, its own shard is the only one such a row matters to
+bool grouped_after_exact_all(tsh_index *idx, const tsh_groups *groups) {
+  if (groups->spans) return true;
+  for (auto &sp : idx->shards) {
+    std::shared_lock<RwLock> sl = share(idx, sp.get());
+    if (!sp->quar_ids.empty()) return true;
+  }
+  return false;
+}
+
+// The two entries' common body: count == false, a page of k groups per query past `after` (never empty); count == true,
+// the number of groups per query past `after` (or all of them) into out_n.  One finaliser step per query over all shards
+int grouped_after_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const uint8_t *row_mask, tsh_mask *mask_h,
+                       tsh_groups *groups, Cursors after, bool count, int64_t *out_ids, double *out_dist, int32_t *out_group, int32_t *out_count,
+                       int64_t *out_n) {
+  std::shared_lock<std::shared_mutex> use(groups->use_mu);  // the array stays as it is until the finaliser has read it
+  const size_t ns = idx->shards.size();
+  const int32_t entries = tsh_default_block_entries(k);
+  const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
+  const bool exact_all = grouped_after_exact_all(idx, groups);
+  std::vector<std::unique_ptr<uint8_t[]>> blocks(ns);
+  std::vector<std::vector<int64_t>> certain(ns);
+  std::vector<std::vector<std::vector<BlockEntry>>> spills(ns), extras(ns);
+  int rc = for_each_shard(idx, [&](size_t g) -> int {
+    Shard *s = idx->shards[g].get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    if (s->rows == 0) return TSH_OK;
+    blocks[g].reset(new uint8_t[bb * (size_t)nq]);
+    spills[g].resize((size_t)nq);
+    extras[g].resize((size_t)nq);
+    SearchOut so;
+    so.h_blocks = blocks[g].get();
+    so.spill = &spills[g];
+    so.extra = &extras[g];
+    so.after = after;
+    so.group_after = true;
+    so.exact_all = exact_all || !s->quar_ids.empty();
+    if (count) {
+      certain[g].assign((size_t)nq, 0);
+      so.count_out = certain[g].data();
+      so.count_thr = thr;
+    }
+    int prc = TSH_OK;
+    so.groups = groups_part(groups, g, s, &prc);
+    if (!so.groups) return prc;
+    MaskSrc ms;
+    int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
+    if (mrc) return mrc;
+    // (the pipeline of single-query scans, never the batched path)
+    return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
+  });
+  if (rc) return rc;
+  const GroupTable table{groups->group_of.data(), (int64_t)groups->group_of.size()};
+  parallel_for(nq, [&](int32_t q) {
+    std::vector<EntryList> lists;
+    int64_t sure = 0;
+    for (size_t g = 0; g < ns; ++g) {
+      if (!blocks[g]) continue;
+      EntryList two[2];
+      const size_t n_lists = shard_lists(blocks[g].get() + (size_t)q * bb, &spills[g][(size_t)q], &extras[g][(size_t)q], two);
+      lists.insert(lists.end(), two, two + n_lists);
+      if (count) sure += certain[g][(size_t)q];
+    }
+    Cursor cur;
+    const Cursor *c = after.at(q, &cur);
+    const float *query = queries + (size_t)q * idx->dim;
+    if (count)
+      out_n[q] = sure + group_count_entries(idx->metric, idx->dim, query, thr, lists.data(), lists.size(), table, c);
+    else
+      out_count[q] = finalize_grouped_after(idx->metric, idx->dim, query, k, thr, lists.data(), lists.size(), table, *c, out_ids + (size_t)q * k,
+                                            out_dist + (size_t)q * k, out_group ? out_group + (size_t)q * k : nullptr);
+  });
+  return TSH_OK;
+}
+
+}  // namespace
+
+int32_t tsh_search_grouped_after(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const uint8_t *row_mask,
+                                 tsh_mask *mask_h, void *groups_p, const double *after_dist, const int64_t *after_id, int64_t *out_ids,
+                                 double *out_dist, int32_t *out_group, int32_t *out_count) {
+  tsh_groups *groups = static_cast<tsh_groups *>(groups_p);
+  if (row_mask && mask_h) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!groups) return set_err(TSH_E_BAD_ARG, "groups is NULL");
+  if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (groups->idx != idx) return set_err(TSH_E_BAD_ARG, "the groups handle was made for another index (or its index was destroyed)");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
+  if (nq == 0) return TSH_OK;
+  if (!queries || !out_count) return set_err(TSH_E_BAD_ARG, "queries / out_count is NULL");
+  for (int32_t q = 0; q < nq; ++q) out_count[q] = 0;
+  if (k <= 0) return TSH_OK;
+  if (!out_ids || !out_dist) return set_err(TSH_E_BAD_ARG, "out_ids / out_dist is NULL");
+  return grouped_after_impl(idx, queries, nq, k, thr, row_mask, mask_h, groups, Cursors{after_dist, after_id}, false, out_ids, out_dist, out_group,
+                            out_count, nullptr);
+}
+
+int32_t tsh_search_grouped_count(tsh_index *idx, const float *queries, int32_t nq, double thr, const uint8_t *row_mask, tsh_mask *mask_h,
+                                 void *groups_p, const double *after_dist, const int64_t *after_id, int64_t *out_count) {
+  tsh_groups *groups = static_cast<tsh_groups *>(groups_p);
+  if (row_mask && mask_h) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!groups) return set_err(TSH_E_BAD_ARG, "groups is NULL");
+  if (half_cursor(after_dist, after_id)) return set_err(TSH_E_BAD_ARG, "after_dist / after_id: both or neither");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (groups->idx != idx) return set_err(TSH_E_BAD_ARG, "the groups handle was made for another index (or its index was destroyed)");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
+  if (nq == 0) return TSH_OK;
+  if (!queries || !out_count) return set_err(TSH_E_BAD_ARG, "queries / out_count is NULL");
+  for (int32_t q = 0; q < nq; ++q) out_count[q] = 0;
+  // (the block of a count job: used on the exact-all route only, where the job is a search for one row whose wide-band
+  // pass spills every live row)
+  return grouped_after_impl(idx, queries, nq, /*k*/ 1, thr, row_mask, mask_h, groups, Cursors{after_dist, after_id}, true, nullptr, nullptr, nullptr,
+                            nullptr, out_count);
+}
+
+int32_t tsh_search_grouped_after_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+  for (auto &sp : idx->shards) {
+    out[0] += sp->c_gafter.load();
+    out[1] += sp->c_gcount.load();
+    out[2] += sp->c_gafter_side.load();
+    out[3] += sp->c_gafter_redone.load();
+    out[4] += sp->c_gafter_all.load();
   }
   return TSH_OK;
 }

@@ -135,6 +135,16 @@ typedef _SearchGroupedD = int Function(Pointer<Void>, Pointer<Float>, int, int, 
     Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
 typedef _SearchGroupedStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
 typedef _SearchGroupedStatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchGroupedAfterC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchGroupedAfterD = int Function(Pointer<Void>, Pointer<Float>, int, int, double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchGroupedCountC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>);
+typedef _SearchGroupedCountD = int Function(Pointer<Void>, Pointer<Float>, int, double, Pointer<Uint8>, Pointer<Void>,
+    Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>);
+typedef _SearchGroupedAfterStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchGroupedAfterStatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
@@ -382,6 +392,9 @@ final class HipVectorBackend {
   static late final _GroupsDestroyD _groupsDestroy;
   static late final _SearchGroupedD _searchGrouped;
   static late final _SearchGroupedStatsD _searchGroupedStats;
+  static late final _SearchGroupedAfterD _searchGroupedAfter;
+  static late final _SearchGroupedCountD _searchGroupedCount;
+  static late final _SearchGroupedAfterStatsD _searchGroupedAfterStats;
   static late final _ProbeScanI8D _probeScanI8;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
@@ -460,6 +473,12 @@ final class HipVectorBackend {
       _searchGrouped = lib.lookupFunction<_SearchGroupedC, _SearchGroupedD>('tsh_search_grouped');
       _searchGroupedStats =
           lib.lookupFunction<_SearchGroupedStatsC, _SearchGroupedStatsD>('tsh_search_grouped_stats');
+      _searchGroupedAfter =
+          lib.lookupFunction<_SearchGroupedAfterC, _SearchGroupedAfterD>('tsh_search_grouped_after');
+      _searchGroupedCount =
+          lib.lookupFunction<_SearchGroupedCountC, _SearchGroupedCountD>('tsh_search_grouped_count');
+      _searchGroupedAfterStats =
+          lib.lookupFunction<_SearchGroupedAfterStatsC, _SearchGroupedAfterStatsD>('tsh_search_grouped_after_stats');
       _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
@@ -1116,6 +1135,116 @@ final class HipVectorBackend {
     try {
       if (_searchGroupedStats(_handle, o) != 0) return null;
       return {'searches': o[0], 'sideRows': o[1], 'redone': o[2], 'noDevicePasses': o[3]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
+  /// The next `topK` groups past a cursor (tsh_search_grouped_after): the entries of [searchGrouped]'s list that follow
+  /// (`afterDistance`, `afterId`) strictly -- the last entry of the page before; double.negativeInfinity starts the list.
+  /// A group whose best row is at or before the cursor is consumed: none of its rows comes back.  A page shorter than
+  /// topK is the last.  Null on any native failure; a disposed [HipRowGroups] or [HipRowMask] is refused (null, with a
+  /// warning), never sent as NULL.
+  List<HipGroupedResult>? searchGroupedAfter(Float32List query, int topK, HipRowGroups groups, double afterDistance, int afterId,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) {
+    if (groups._groups == nullptr) {
+      Logger.warn('searchGroupedAfter with a disposed HipRowGroups', label: 'HipVectorBackend');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchGroupedAfter with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (topK <= 0 || size == 0) return <HipGroupedResult>[];
+    final q = calloc<Float>(dimensions);
+    final ids = calloc<Int64>(topK);
+    final dist = calloc<Double>(topK);
+    final grp = calloc<Int32>(topK);
+    final cnt = calloc<Int32>();
+    final aDist = calloc<Double>();
+    final aId = calloc<Int64>();
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      aDist.value = afterDistance;
+      aId.value = afterId;
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _searchGroupedAfter(_handle, q, 1, topK, distanceThreshold ?? double.nan, maskBytes,
+          mask != null ? mask._mask : nullptr, groups._groups, aDist, aId, ids, dist, grp, cnt);
+      if (rc != 0) {
+        Logger.warn('tsh_search_grouped_after failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return [for (var i = 0; i < cnt.value; ++i) HipGroupedResult(ids[i], dist[i], grp[i])];
+    } finally {
+      calloc.free(q);
+      calloc.free(ids);
+      calloc.free(dist);
+      calloc.free(grp);
+      calloc.free(cnt);
+      calloc.free(aDist);
+      calloc.free(aId);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+  }
+
+  /// How many groups [searchGroupedAfter] would return with topK = infinity (tsh_search_grouped_count): with
+  /// `afterDistance` null, the whole grouped list.  Null on any native failure or a disposed handle.
+  int? countGroups(Float32List query, HipRowGroups groups,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask, double? afterDistance, int afterId = 0}) {
+    if (groups._groups == nullptr) {
+      Logger.warn('countGroups with a disposed HipRowGroups', label: 'HipVectorBackend');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('countGroups with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (size == 0) return 0;
+    final q = calloc<Float>(dimensions);
+    final out = calloc<Int64>();
+    Pointer<Double> aDist = nullptr;
+    Pointer<Int64> aId = nullptr;
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      if (afterDistance != null) {
+        aDist = calloc<Double>();
+        aId = calloc<Int64>();
+        aDist.value = afterDistance;
+        aId.value = afterId;
+      }
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _searchGroupedCount(_handle, q, 1, distanceThreshold ?? double.nan, maskBytes,
+          mask != null ? mask._mask : nullptr, groups._groups, aDist, aId, out);
+      if (rc != 0) {
+        Logger.warn('tsh_search_grouped_count failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return out.value;
+    } finally {
+      calloc.free(q);
+      calloc.free(out);
+      if (aDist != nullptr) calloc.free(aDist);
+      if (aId != nullptr) calloc.free(aId);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+  }
+
+  /// The grouped cursor searches' and group counts' counters (tsh_search_grouped_after_stats), per shard job: the
+  /// searches, the counts, rows sent to the side list, jobs redone with a larger side list, jobs answered by the
+  /// exact-all route.
+  Map<String, int>? searchGroupedAfterStats() {
+    final o = calloc<Int64>(5);
+    try {
+      if (_searchGroupedAfterStats(_handle, o) != 0) return null;
+      return {'searches': o[0], 'counts': o[1], 'sideRows': o[2], 'redone': o[3], 'exactAll': o[4]};
     } finally {
       calloc.free(o);
     }

@@ -170,7 +170,7 @@ class VectorIndexManager:
             search_query = normalize_float32(query_f32)
         if group_by is not None:
             if after is not None:
-                raise ValueError("group_by and after cannot be combined: grouped searches have no cursor yet")
+                raise ValueError("group_by and after cannot be combined here: page groups with vectorSearchGroupedAfter")
             if topK <= 0:
                 return []
             ids, dist, _, cnt = self.index.search_grouped(search_query, topK, group_by, distance_threshold=distanceThreshold,
@@ -194,3 +194,33 @@ class VectorIndexManager:
         import functools
         entries.sort(key=functools.cmp_to_key(lambda a, b: _dart_compare(a.distance, b.distance)))
         return entries
+
+    def vectorSearchGroupedAfter(self, queryVector: Sequence[float], group_by, after, topK: int = 10,
+                                 distanceThreshold: Optional[float] = None, rowMask=None) -> list:
+        """The next page of a grouped search (no reference counterpart; vectorSearch itself keeps refusing group_by with
+        after): the topK groups past the cursor `after` = (distance, nodeId) -- the last entry of the page before, or
+        (-inf, 0) for the first page -- each by its nearest row (HipVectorIndex.search_grouped_after).  A group shown on an
+        earlier page does not come back through its other rows.  Entries come in the result order (distance, then node
+        id), so the last one is the next cursor; a page shorter than topK is the last."""
+        if self.index.size == 0 or topK <= 0:
+            return []
+        query_f32 = to_float32(queryVector, self.dimensions)
+        if self.metric == METRIC_COSINE:
+            query_f32 = normalize_float32(query_f32)
+        ids, dist, _, cnt = self.index.search_grouped_after(query_f32, topK, group_by, (float(after[0]), int(after[1])),
+                                                            distance_threshold=distanceThreshold, row_mask=rowMask)
+        out = []
+        for i in range(int(cnt[0])):
+            node, d = int(ids[0, i]), float(dist[0, i])
+            out.append(VectorSearchResult(primaryKey=self._pk.get(node), distance=d, score=distance_to_score(d, self.metric), nodeId=node))
+        return out
+
+    def countGroups(self, queryVector: Sequence[float], group_by, distanceThreshold: Optional[float] = None, rowMask=None, after=None) -> int:
+        """How many groups a grouped search would list (HipVectorIndex.count_groups): all of them, or those past `after`."""
+        if self.index.size == 0:
+            return 0
+        query_f32 = to_float32(queryVector, self.dimensions)
+        if self.metric == METRIC_COSINE:
+            query_f32 = normalize_float32(query_f32)
+        a = None if after is None else (float(after[0]), int(after[1]))
+        return int(self.index.count_groups(query_f32, group_by, distance_threshold=distanceThreshold, row_mask=rowMask, after=a)[0])
