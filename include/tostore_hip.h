@@ -55,6 +55,7 @@ extern "C" {
  *    tsh_groups_create, tsh_groups_set, tsh_groups_destroy, tsh_search_grouped, tsh_search_grouped_stats. */
 /*    Additive since, same version, continued: tsh_search_grouped_after, tsh_search_grouped_count,
  *    tsh_search_grouped_after_stats. */
+/*    Additive since, same version, continued: tsh_search_grouped_rows, tsh_search_grouped_rows_stats. */
 
 /* status codes */
 #define TSH_OK 0
@@ -458,8 +459,8 @@ int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out);
  *   is 0.45 resp. 0.35, and it costs what tsh_search_count costs ("Grouped search";
  *   profiles/search_grouped_ab.json).
  * A cursor, so that groups can be paged, and a count of groups: tsh_search_grouped_after and tsh_search_grouped_count,
- *   below.  The next step would bring, none of it here: more than one row per group.  A ticket form
- *   (tsh_search_submit_grouped).  The tsh_search_shard* and tsh_search_sharded* entries.
+ *   below.  More than one row per group: tsh_search_grouped_rows, below them.  The next step would bring, none of it
+ *   here: a ticket form (tsh_search_submit_grouped).  The tsh_search_shard* and tsh_search_sharded* entries.
  * tsh_counters keeps its layout; a grouped search counts in searches and scan_launches like any other search.
  * The handle is a tsh_groups * (typedef below).  In the prototypes it travels as `void *`, and tsh_groups_create's
  * `out` -- the address of the caller's tsh_groups * (a tsh_groups **) -- as `void *` too: the bindings' prototype tables
@@ -536,6 +537,63 @@ int32_t tsh_search_grouped_count(tsh_index *idx, const float *queries, int32_t n
                                  const uint8_t *row_mask, tsh_mask *mask, void *groups,
                                  const double *after_dist, const int64_t *after_id, int64_t *out_count);
 int32_t tsh_search_grouped_after_stats(tsh_index *idx, int64_t *out);
+
+/* ---- grouped search, several rows per group ------------------------------
+ * tsh_search_grouped_rows: the rows_per_group nearest rows of each of the k nearest groups -- a document's best
+ * passages, a video's best frames -- from the one scan of a grouped search.  L and G as above (L: tsh_search's list for
+ * k = infinity under the same row mask, tombstones, gaps, quarantined rows and threshold; G: L without every entry whose
+ * group occurred earlier).  The k winning groups are the groups of G's first k entries, in that order; for the i-th of
+ * them the answer holds the first rows_per_group entries of L that belong to it, in L's order, ids and distances bit for
+ * bit those of L.  An ungrouped row is a group of one row; a group with fewer surviving rows gives what it has; a row
+ * that fails the threshold, the mask or the tombstones never appears, so the first row of every group is exactly what
+ * tsh_search_grouped returns.  With rows_per_group = 1 the entry equals tsh_search_grouped bit for bit; with every row
+ * in one group it equals tsh_search cut to rows_per_group.
+ *
+ * Slot (q, i, j) lives at (q * k + i) * rows_per_group + j of out_ids / out_dist; unused slots read id -1 and distance
+ * NaN.  out_group / out_rows (nq x k, either may be NULL): the group (-1: ungrouped) and the rows it returned; an unused
+ * group reads -1 and 0.  out_count (nq): the groups returned.  rows_per_group runs from 1 to 64 -- an interface limit --
+ * and anything else is TSH_E_BAD_ARG, except that rows_per_group <= 0 together with k <= 0 or an empty index is the
+ * grouped search's trivial case (TSH_OK, counts 0).  Every other argument error is tsh_search_grouped's: NULL groups,
+ * both mask forms, a handle of another index or of a destroyed one.  At most one of row_mask / mask.
+ *
+ * How: a grouped job up to its re-rank.  The groups whose head key is at or below the band the select left contain every
+ * winning group; they are marked, their live rows gathered, and of each the rows at or below band_of(the group's
+ * rows_per_group-th smallest key) -- all rows of a smaller group -- get their exact sums beside the select's candidates
+ * (tostore_amd/csrc/tsh_group_rows_rule.h has the proof, tsh_group_rows.hip.h the five passes).  No host round trip
+ * inside a job; the finaliser runs once per query over all shards.  Several queries per call run as the pipeline of
+ * single-query f32 tile scans or list scans, never the batched path, the fp16 / int8 copies or the exact path, as the
+ * other grouped jobs do.
+ *
+ * The EXACT-ALL route, slow and exact (every live row's exact sums reach the finaliser, no device group passes), is
+ * taken in the cases the grouped cursor search takes it in: a handle over several devices whose groups span two shards'
+ * row ranges (a winning group's second row can lie on a shard where the group is not marked at all), a shard that holds a
+ * live quarantined row (its group can win through a row the head table does not hold), and safe mode.  A job that marks
+ * more groups than it has slots for (2 k + 64: no bound at all from the select, or heads tied at the k-th by the
+ * hundred) runs again on that route; a job whose member or side lists overflow is redone once with lists sized from
+ * the counts the first run left.
+ *
+ * tsh_search_grouped_rows_stats, summed over the shards (a job counts once per shard): out[0] searches, out[1] marked
+ * groups, out[2] member rows sent on for exact sums, out[3] jobs redone with larger lists (or on the exact-all route
+ * after their slots ran out), out[4] jobs answered by the exact-all route.  These jobs move NONE of the other *_stats;
+ * tsh_counters keeps its layout and counts them in searches and scan_launches like any other search.
+ *
+ * Cost: the new passes read the 4 B key, the 4 B group id and one 8 B table word per row where the scan reads 3 KB --
+ *   measured on 1 M x 768, L2, groups of 8 rows, 64-query calls, per query: 447.8 to 452.5 us at k = 10 for m = 1, 3 and
+ *   10 (1.003 to 1.006 of tsh_search_grouped in the same process; 10.0 marked groups, 10 / 30 / 80 member rows per job),
+ *   449.9 to 468.2 us at k = 100 (1.010 to 1.051; 100.4 marked groups, 100 / 301 / 803 member rows), against 445.1 to
+ *   452.5 us for tsh_search_grouped, and against 1436 to 4149 us for the caller's loop of tsh_search_grouped and
+ *   tsh_search_after pages, which after six pages of k m rows still missed 4 to 8 % of the rows at m = 3.  The five
+ *   passes take 4.5 to 5.4 us each on an idle device ("several rows per group";
+ *   profiles/search_grouped_rows_ab.json, profiles/search_grouped_rows_kernel_stats.txt).
+ *
+ * Out of scope: a cursor or a count with rows per group; a ticket form; the tsh_search_shard* / tsh_search_sharded*
+ * entries (a shard handle answers for its own rows; merging ranks' answers is exact only when no group has rows on two
+ * ranks); a cheaper handling of spanning or quarantined groups than the exact-all route. */
+int32_t tsh_search_grouped_rows(tsh_index *idx, const float *queries, int32_t nq, int32_t k, int32_t rows_per_group,
+                                double distance_threshold, const uint8_t *row_mask, tsh_mask *mask, void *groups,
+                                int64_t *out_ids, double *out_dist, int32_t *out_group, int32_t *out_rows,
+                                int32_t *out_count);
+int32_t tsh_search_grouped_rows_stats(tsh_index *idx, int64_t *out);
 
 /* ---- row-sharded deployments (one process per GPU) ----------------------
  * Each rank scans its shard and emits, per query, one fixed-size candidate

@@ -116,6 +116,8 @@ SIGNATURES = {
     "tsh_search_grouped_after": (c_i32, [p_void, p_f32, c_i32, c_i32, c_f64, p_u8, p_void, p_void, p_f64, p_i64, p_i64, p_f64, p_i32, p_i32]),
     "tsh_search_grouped_count": (c_i32, [p_void, p_f32, c_i32, c_f64, p_u8, p_void, p_void, p_f64, p_i64, p_i64]),
     "tsh_search_grouped_after_stats": (c_i32, [p_void, p_i64]),
+    "tsh_search_grouped_rows": (c_i32, [p_void, p_f32, c_i32, c_i32, c_i32, c_f64, p_u8, p_void, p_void, p_i64, p_f64, p_i32, p_i32, p_i32]),
+    "tsh_search_grouped_rows_stats": (c_i32, [p_void, p_i64]),
     "tsh_candidate_block_bytes": (c_i64, [c_i32]),
     "tsh_default_block_entries": (c_i32, [c_i32]),
     "tsh_search_shard": (c_i32, [p_void, p_f32, c_i32, c_i32, p_u8, c_i32, p_void, p_void]),

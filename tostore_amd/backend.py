@@ -474,6 +474,46 @@ class HipVectorIndex:
         _ffi.check(_ffi.lib().tsh_search_grouped_after_stats(self._h, out))
         return {"searches": out[0], "counts": out[1], "side_rows": out[2], "redone": out[3], "exact_all": out[4]}
 
+    def search_grouped_rows(self, queries, k: int, rows_per_group: int, groups: "HipGroups", distance_threshold: Optional[float] = None,
+                            row_mask=None):
+        """The rows_per_group nearest rows of each of the k nearest groups: (ids[nq,k,m], dist[nq,k,m], group[nq,k],
+        rows[nq,k], count[nq]).  The winning groups are search_grouped()'s, in its order; of each the first m entries of
+        the list search() would return with k = infinity, in that list's order.  Unused slots read id -1 and distance NaN,
+        an unused group -1 and 0 rows.  rows_per_group: 1 to 64.  row_mask: None, a byte mask or a HipMask."""
+        q = _f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be nq x {self.dim}")
+        if not isinstance(groups, HipGroups):
+            raise TypeError("groups must be a HipGroups (HipVectorIndex.make_groups)")
+        nq, kk, mm = q.shape[0], max(int(k), 0), max(int(rows_per_group), 0)
+        ids = np.empty((nq, max(kk, 1), max(mm, 1)), dtype=np.int64)
+        dist = np.empty((nq, max(kk, 1), max(mm, 1)), dtype=np.float64)
+        grp = np.empty((nq, max(kk, 1)), dtype=np.int32)
+        rows = np.empty((nq, max(kk, 1)), dtype=np.int32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        thr = math.nan if distance_threshold is None else float(distance_threshold)
+        handle, mp = None, None
+        if isinstance(row_mask, HipMask):
+            handle = row_mask.handle()
+        else:
+            row_mask, mp = self.mask_arg(row_mask)
+        # (the C entry lays slot (q, i, j) at (q k + i) m + j: the arrays above have that shape only for k, m >= 1 -- a
+        # trivial call writes no slot)
+        _ffi.check(_ffi.lib().tsh_search_grouped_rows(self._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), int(rows_per_group), thr, mp, handle,
+                                                      groups.handle(), ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                      grp.ctypes.data_as(_ffi.p_i32), rows.ctypes.data_as(_ffi.p_i32),
+                                                      cnt.ctypes.data_as(_ffi.p_i32)))
+        return ids[:, :kk, :mm], dist[:, :kk, :mm], grp[:, :kk], rows[:, :kk], cnt
+
+    def search_grouped_rows_stats(self) -> dict:
+        """The rows-per-group searches' counters, per shard job: the searches, groups their mark passes marked, member rows
+        sent on for exact sums, jobs redone with larger lists, jobs answered by the exact-all route."""
+        out = (ctypes.c_int64 * 5)()
+        _ffi.check(_ffi.lib().tsh_search_grouped_rows_stats(self._h, out))
+        return {"searches": out[0], "marked_groups": out[1], "member_rows": out[2], "redone": out[3], "exact_all": out[4]}
+
     # -- asynchronous single-query form (several queries in flight) -----------------
     def submit(self, query, k: int, row_mask=None, after=None) -> tuple:
         """after: a (distance, id) cursor -- the ticket answers search_after() instead of search()."""

@@ -36,6 +36,7 @@
 #include "tsh_count.hip.h"
 #include "tsh_count_band.h"
 #include "tsh_group.hip.h"
+#include "tsh_group_rows.hip.h"
 #include "tsh_batch.hip.h"
 #include "tsh_batch_f16.hip.h"
 #include "tsh_batch_plan.h"
@@ -158,6 +159,12 @@ struct Ctx {
   int64_t heads_tiles = 0;
   unsigned long long *d_gm = nullptr;
   int64_t gm_cap = 0;
+  // grouped searches with several rows per group (tsh_group_rows.hip.h): the control words and the three per-slot arrays
+  // (count, placed, offset) in one allocation, and the member segments -- reserved by the context's first such job
+  uint32_t *d_gr_ctl = nullptr;
+  int64_t gr_slots = 0;
+  unsigned long long *d_gr_seg = nullptr;
+  int64_t gr_seg_cap = 0;
   int64_t bytes = 0;
 };
 
@@ -328,6 +335,10 @@ struct Shard {
   // sent to the side list, jobs redone with a larger side list, jobs answered by the exact-all route.  These jobs move
   // none of the counters above
   std::atomic<int64_t> c_gafter{0}, c_gcount{0}, c_gafter_side{0}, c_gafter_redone{0}, c_gafter_all{0};
+  // grouped searches with rows per group (tsh_search_grouped_rows_stats): the searches, groups their mark passes marked,
+  // member rows sent to the side list, jobs redone with larger lists, jobs answered by the exact-all route.  These jobs
+  // move none of the counters above either
+  std::atomic<int64_t> c_grows{0}, c_grows_marked{0}, c_grows_side{0}, c_grows_redone{0}, c_grows_all{0};
   int cus = 0;  // compute units of the shard's device (grid of the persistent key kernels)
   std::atomic<int> f16_strikes{0};      // batched calls in a row whose fp16 bands overflowed many candidate lists
   std::atomic<int> f16_denied_calls{0};  // auto key-kernel choice: bf16x3 instead of fp16 for this many more batched calls
@@ -721,6 +732,8 @@ void ctx_free_all(Ctx *c) {
   hipFree(c->d_heads);
   hipFree(c->d_hmin);
   hipFree(c->d_gm);
+  hipFree(c->d_gr_ctl);
+  hipFree(c->d_gr_seg);
 }
 
 int ctx_prepare(Shard *s, Ctx *c, int32_t entries, bool need_mask) {
@@ -1015,6 +1028,11 @@ struct Job {
   // re-rank.  exact_all: the rule does not hold for this call (JobReq::exact_all): a plain search job whose every live
   // row reaches the finaliser, as in safe mode
   bool group_after = false, exact_all = false;
+  // a grouped search with several rows per group (JobReq::group_rows, the rows per group; tsh_group_rows_rule.h): a grouped
+  // job whose G3 gives way to the mark, member and pick passes (tsh_group_rows.hip.h).  rows_redone: it runs for the
+  // second time, with larger lists or on the exact-all route
+  int32_t group_rows = 0;
+  bool rows_redone = false;
   const float *redo_query = nullptr;  // the caller's query (a ticket's own copy): valid until the job is finished
   std::vector<uint64_t> redo_words;   // a ticket's copy of a pointer mask's words (JobReq::mask_dies), else empty
 };
@@ -1129,6 +1147,33 @@ int ctx_reserve_group(Ctx *c, int64_t n_groups) {
     HIPCHK(hipMalloc(&c->d_gm, (size_t)want * 8));
     c->gm_cap = want;
     c->bytes += want * 8;
+  }
+  return TSH_OK;
+}
+
+// what a grouped job with rows per group adds on top (tsh_group_rows.hip.h): `slots` slots and segment space for
+// `seg_want` member rows
+constexpr int64_t GROUP_ROWS_SEG_CAP = 8192;  // member rows a context's segments hold before a job is redone with more
+int ctx_reserve_group_rows(Ctx *c, int64_t slots, int64_t seg_want) {
+  if (slots > c->gr_slots) {
+    hipFree(c->d_gr_ctl);
+    c->d_gr_ctl = nullptr;
+    c->bytes -= c->gr_slots * 12;
+    c->gr_slots = 0;
+    const int64_t want = round_up(slots, 256);
+    HIPCHK(hipMalloc(&c->d_gr_ctl, (size_t)(GROUP_ROWS_CTL + 3 * want) * sizeof(uint32_t)));
+    c->gr_slots = want;
+    c->bytes += want * 12;
+  }
+  seg_want = std::max(seg_want, GROUP_ROWS_SEG_CAP);
+  if (seg_want > c->gr_seg_cap) {
+    hipFree(c->d_gr_seg);
+    c->d_gr_seg = nullptr;
+    c->bytes -= c->gr_seg_cap * 8;
+    c->gr_seg_cap = 0;
+    HIPCHK(hipMalloc(&c->d_gr_seg, (size_t)seg_want * 8));
+    c->gr_seg_cap = seg_want;
+    c->bytes += seg_want * 8;
   }
   return TSH_OK;
 }
@@ -1453,6 +1498,9 @@ struct JobReq {
   const GroupPart *groups = nullptr;  // a grouped search (tsh_search_grouped): this shard's part of the groups handle
   bool group_after = false;       // ... of tsh_search_grouped_after / tsh_search_grouped_count: `after` resp. `count` hold for GROUPS
   bool exact_all = false;         // ... whose rule does not hold for this call: every live row's exact sums for the finaliser
+  int32_t group_rows = 0;         // ... of tsh_search_grouped_rows: this many rows of each group (0: a plain grouped search)
+  int64_t seg_want = 0;           // ... redone after its member segments overflowed: room for this many rows
+  bool rows_redone = false;       // ... redone at all (larger lists, or exact_all after its slots overflowed)
   bool mask_dies = false;         // ... enqueued for a ticket: a pointer mask's words and list are gone before the job is finished
 };
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
@@ -1758,6 +1806,36 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
                            s->ld, s->row_base, s->dim, s->metric, side_cap};
     // (the side re-rank's grid: one workgroup per row up to the re-rank's own 1024)
     TSH_LAUNCH_EV(count_side_kernel, std::min(side_cap, 1024u), 64, ts, none, done, sd);
+  } else if (j->grouped && j->group_rows > 0) {
+    // a grouped job with rows per group: G1, G2, select and re-rank as below; in G3's place the marked groups get their
+    // slots (R1), their live rows are counted, given segments and written there (R2 - R4), and a workgroup per slot
+    // sends the rows that may be among the group's m best to the side list (R5) -- tsh_group_rows.hip.h
+    const GroupPart *gp = j->gpart;
+    const int32_t n_tiles = ka.se.n_tiles;
+    const unsigned tgrid = (unsigned)((n_tiles + 3) / 4);
+    const uint32_t side_cap = (uint32_t)c->side_cap;
+    uint32_t *const side_count = c->d_side_cnt + j->side_word;
+    const uint32_t slot_cap = (uint32_t)std::min<int64_t>(group_rows_slots(j->k), c->gr_slots);
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
+    if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
+    // (the control words, cnt[] and cur[]; off[] is written before it is read)
+    HIPCHK(hipMemsetAsync(c->d_gr_ctl, 0, (size_t)(GROUP_ROWS_CTL + 2 * c->gr_slots) * sizeof(uint32_t), ts));
+    group_min_kernel<<<tgrid, 256, 0, ts>>>(ga);
+    group_heads_kernel<<<tgrid, 256, 0, ts>>>(ga);
+    launch_select(ka.se, n_tiles, ts);
+    TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, none, ka.ra);
+    uint32_t *const slots = c->d_gr_ctl + GROUP_ROWS_CTL;
+    const GroupRowsArgs gr{ga, ka.se.hdr, c->d_gr_ctl, slots, slots + c->gr_slots, slots + 2 * c->gr_slots, c->d_gr_seg, slot_cap,
+                           (uint32_t)std::min<int64_t>(c->gr_seg_cap, 0xFFFFFFFFll), (uint32_t)j->group_rows, c->d_side_rows, side_count, side_cap,
+                           ka.se.eps_rel, ka.se.delta_abs, c->h_side_dev};
+    group_rows_mark_kernel<<<tgrid, 256, 0, ts>>>(gr);
+    group_rows_member_kernel<false><<<tgrid, 256, 0, ts>>>(gr);
+    group_rows_alloc_kernel<<<(slot_cap + 255u) / 256u, 256, 0, ts>>>(gr);
+    group_rows_member_kernel<true><<<tgrid, 256, 0, ts>>>(gr);
+    group_rows_pick_kernel<<<slot_cap, 256, 0, ts>>>(gr);
+    const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
+                           s->dim, s->metric, side_cap};
+    TSH_LAUNCH_EV(after_side_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, ts, none, done, sd);
   } else if (j->grouped) {
     // a grouped job: the head table cleared, every group's head found (G1), one head per group left for the select (G2);
     // behind the re-rank the rows that may still be their group's best (G3) get their exact sums by the cursor jobs' side
@@ -1860,6 +1938,8 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   j->gpart = rq.groups;
   j->group_after = rq.group_after;
   j->exact_all = rq.exact_all;
+  j->group_rows = rq.groups ? rq.group_rows : 0;
+  j->rows_redone = rq.rows_redone;
   const Route &r = j->route =
       choose_route(s, rq.mask, j->masked, rq.k, rq.entries, rq.query, rq.no_f16, rq.no_i8, j->has_after || rq.count || j->grouping);
   // (the exact-all route of a grouped cursor search or group count: what safe mode runs -- no floor, no window, no group
@@ -1897,8 +1977,13 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
     return enqueue_after_skip(s, j, rq, q);
   }
   if (j->grouped && (rc = ctx_reserve_group(c, rq.groups->n_groups))) return rc;
+  const bool rows_job = j->grouped && j->group_rows > 0;
+  if (rows_job && (rc = ctx_reserve_group_rows(c, group_rows_slots(rq.k), rq.seg_want))) return rc;
+  // (a rows job sends on about m rows of each marked group: its side list starts with room for twice k * m of them, the
+  // shard's rows at the most)
+  const int64_t rows_side = !rows_job ? 0 : std::min<int64_t>(round_up(2 * (int64_t)rq.k * j->group_rows + AFTER_SIDE_CAP, 1024), round_up(s->rows, 1024));
   if (j->floored || j->windowed || j->grouped) {
-    if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(rq.side_want, AFTER_SIDE_CAP), c->side_cap)))) return rc;
+    if ((rc = ctx_reserve_side(c, std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(rq.side_want, rows_side), AFTER_SIDE_CAP), c->side_cap)))) return rc;
     if (c->side_dirty) {  // (a context's first cursor or count job, or one after a job that failed on its way)
       HIPCHK(hipMemsetAsync(c->d_side_cnt, 0, 3 * sizeof(uint32_t), s->aux_stream));
       HIPCHK(hipStreamSynchronize(s->aux_stream));
@@ -2140,9 +2225,22 @@ int redo_after_side(Shard *s, Job *j) {
   Ctx *c = j->c;
   c->side_dirty = false;  // (finished: A2 left the context's other count word at zero)
   const int64_t n = c->h_side[0].id;
-  if (n <= c->side_cap) return TSH_OK;
-  if (j->after_redone) return set_err(TSH_E_HIP, "a cursor search's side list overflowed twice (%lld rows): internal error", (long long)n);
-  (j->group_after ? s->c_gafter_redone : j->grouping ? s->c_grouped_redone : j->counting ? s->c_count_redone : s->c_after_redone)++;
+  // a job with rows per group that ran its device passes: the marked groups against its slots -- more, and it runs again on
+  // the exact-all route --, the member rows against its segment space.  Segments that did not fit sent nothing on, so that
+  // redo's side list gets room for every member: the pick sends on members only
+  const bool rows_job = j->grouped && j->group_rows > 0;
+  const int64_t marked = rows_job ? (int64_t)c->h_side[0].s0 : 0, members = rows_job ? (int64_t)c->h_side[0].s1 : 0;
+  const bool slots_over = rows_job && marked > std::min<int64_t>(group_rows_slots(j->k), c->gr_slots);
+  const bool seg_over = rows_job && !slots_over && members > c->gr_seg_cap;
+  if (rows_job && !j->rows_redone) s->c_grows_marked += marked;
+  if (n <= c->side_cap && !slots_over && !seg_over) return TSH_OK;
+  if (j->after_redone || j->rows_redone)
+    return set_err(TSH_E_HIP, "a cursor search's side list overflowed twice (%lld rows): internal error", (long long)n);
+  (rows_job           ? s->c_grows_redone
+   : j->group_after   ? s->c_gafter_redone
+   : j->grouping      ? s->c_grouped_redone
+   : j->counting      ? s->c_count_redone
+                      : s->c_after_redone)++;
   const Cursor cur = j->after;
   JobReq rq(j->redo_query, j->k, j->entries);
   rq.mask = j->redo_mask;
@@ -2155,8 +2253,11 @@ int redo_after_side(Shard *s, Job *j) {
   rq.count_thr = j->count_thr;
   rq.groups = j->gpart;
   rq.group_after = j->group_after;
-  rq.exact_all = j->exact_all;
-  rq.side_want = round_up(n, 1024);
+  rq.exact_all = j->exact_all || slots_over;
+  rq.group_rows = j->group_rows;
+  rq.rows_redone = rows_job;
+  rq.seg_want = seg_over ? round_up(members, 1024) : 0;
+  rq.side_want = slots_over ? 0 : round_up(std::max(n, seg_over ? members : 0), 1024);
   int rc = job_enqueue(s, j, rq);
   if (j->counted) {
     s->inflight.fetch_sub(1);
@@ -2165,6 +2266,7 @@ int redo_after_side(Shard *s, Job *j) {
   if (rc) return rc;
   HIPCHK(hipEventSynchronize(c->ev_done));
   HIPCHK(hipGetLastError());
+  if (!(j->floored || j->windowed || j->grouped)) return TSH_OK;  // (redone on the exact-all route: no side list this time)
   return redo_after_side(s, j);
 }
 
@@ -2244,6 +2346,9 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   if (j->group_after) {
     (j->counting ? s->c_gcount : s->c_gafter)++;
     if (j->route.band.force_all) s->c_gafter_all++;
+  } else if (j->grouping && j->group_rows > 0) {
+    s->c_grows++;
+    if (!j->grouped) s->c_grows_all++;
   } else if (j->grouping) {
     s->c_grouped++;
     if (!j->grouped) s->c_grouped_nodev++;
@@ -2261,7 +2366,11 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     if (j->quar_sel.empty()) extra->clear();
     const uint32_t side_n = (uint32_t)c->h_side[0].id;
     extra->insert(extra->end(), c->h_side + 1, c->h_side + 1 + side_n);
-    (j->group_after ? s->c_gafter_side : j->grouped ? s->c_grouped_side : j->windowed ? s->c_count_side : s->c_after_side) += side_n;
+    (j->group_rows > 0 ? s->c_grows_side
+     : j->group_after  ? s->c_gafter_side
+     : j->grouped      ? s->c_grouped_side
+     : j->windowed     ? s->c_count_side
+                       : s->c_after_side) += side_n;
     if (j->windowed) j->certain = (int64_t)c->h_side[0].s0;
   }
   s->c_searches++;
@@ -2334,6 +2443,8 @@ struct SearchOut {
   // spill and extra to the caller: groups may span shards, so the group-count step runs once over every shard's entries.
   // exact_all: JobReq::exact_all for every job of the call
   bool group_after = false, exact_all = false;
+  // ... a grouped search with rows per group (tsh_search_grouped_rows): JobReq::group_rows for every job of the call
+  int32_t group_rows = 0;
 };
 
 // One submitting thread's share of a multi-query call: queries [q0, q1) of the call, at most
@@ -2374,6 +2485,7 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       rq.groups = out->groups;
       rq.group_after = out->group_after;
       rq.exact_all = out->exact_all;
+      rq.group_rows = out->group_rows;
       rc = job_enqueue(s, &j, rq);
       if (rc) {
         release_all();
@@ -3555,6 +3667,93 @@ int32_t tsh_search_grouped_after_stats(tsh_index *idx, int64_t *out) {
     out[2] += sp->c_gafter_side.load();
     out[3] += sp->c_gafter_redone.load();
     out[4] += sp->c_gafter_all.load();
+  }
+  return TSH_OK;
+}
+
+// ---- grouped search with several rows per group (tsh_group_rows_rule.h) ---------------------------------------------------
+int32_t tsh_search_grouped_rows(tsh_index *idx, const float *queries, int32_t nq, int32_t k, int32_t m, double thr, const uint8_t *row_mask,
+                                tsh_mask *mask_h, void *groups_p, int64_t *out_ids, double *out_dist, int32_t *out_group, int32_t *out_rows,
+                                int32_t *out_count) {
+  tsh_groups *groups = static_cast<tsh_groups *>(groups_p);
+  if (row_mask && mask_h) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!groups) return set_err(TSH_E_BAD_ARG, "groups is NULL");
+  if (m > GROUP_ROWS_MAX) return set_err(TSH_E_BAD_ARG, "rows_per_group %d outside [1, %d]", m, GROUP_ROWS_MAX);
+  if (m <= 0 && k > 0) {  // (with k <= 0 or an empty index there is nothing to give rows of: the grouped search's trivial cases)
+    bool any = !idx;
+    for (size_t g = 0; idx && g < idx->shards.size(); ++g) {
+      std::shared_lock<RwLock> sl = share(idx, idx->shards[g].get());
+      any = any || idx->shards[g]->rows > 0;
+    }
+    if (any) return set_err(TSH_E_BAD_ARG, "rows_per_group %d outside [1, %d]", m, GROUP_ROWS_MAX);
+  }
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (groups->idx != idx) return set_err(TSH_E_BAD_ARG, "the groups handle was made for another index (or its index was destroyed)");
+  if (mask_h && mask_h->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
+  if (nq == 0) return TSH_OK;
+  if (!queries || !out_count) return set_err(TSH_E_BAD_ARG, "queries / out_count is NULL");
+  for (int32_t q = 0; q < nq; ++q) out_count[q] = 0;
+  if (k <= 0 || m <= 0) return TSH_OK;
+  if (!out_ids || !out_dist) return set_err(TSH_E_BAD_ARG, "out_ids / out_dist is NULL");
+  std::shared_lock<std::shared_mutex> use(groups->use_mu);  // the array stays as it is until the finaliser has read it
+  const size_t ns = idx->shards.size();
+  const int32_t entries = tsh_default_block_entries(k);
+  const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
+  const bool exact_all = grouped_after_exact_all(idx, groups);  // (the same two cases: tsh_group_rows_rule.h)
+  std::vector<std::unique_ptr<uint8_t[]>> blocks(ns);
+  std::vector<std::vector<std::vector<BlockEntry>>> spills(ns), extras(ns);
+  int rc = for_each_shard(idx, [&](size_t g) -> int {
+    Shard *s = idx->shards[g].get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    if (s->rows == 0) return TSH_OK;
+    blocks[g].reset(new uint8_t[bb * (size_t)nq]);
+    spills[g].resize((size_t)nq);
+    extras[g].resize((size_t)nq);
+    SearchOut so;
+    so.h_blocks = blocks[g].get();
+    so.spill = &spills[g];
+    so.extra = &extras[g];
+    so.group_rows = m;
+    so.exact_all = exact_all || !s->quar_ids.empty();
+    int prc = TSH_OK;
+    so.groups = groups_part(groups, g, s, &prc);
+    if (!so.groups) return prc;
+    MaskSrc ms;
+    int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
+    if (mrc) return mrc;
+    // (the pipeline of single-query scans, never the batched path)
+    return shard_search_blocks(s, queries, nq, k, ms, entries, &so, PIPE_DEPTH);
+  });
+  if (rc) return rc;
+  // groups span shards: the finaliser's step runs once per query over every shard's entries
+  const GroupTable table{groups->group_of.data(), (int64_t)groups->group_of.size()};
+  const size_t km = (size_t)k * (size_t)m;
+  parallel_for(nq, [&](int32_t q) {
+    std::vector<EntryList> lists;
+    for (size_t g = 0; g < ns; ++g) {
+      if (!blocks[g]) continue;
+      EntryList two[2];
+      const size_t n_lists = shard_lists(blocks[g].get() + (size_t)q * bb, &spills[g][(size_t)q], &extras[g][(size_t)q], two);
+      lists.insert(lists.end(), two, two + n_lists);
+    }
+    out_count[q] = finalize_grouped_rows(idx->metric, idx->dim, queries + (size_t)q * idx->dim, k, m, thr, lists.data(), lists.size(), table,
+                                         out_ids + (size_t)q * km, out_dist + (size_t)q * km, out_group ? out_group + (size_t)q * k : nullptr,
+                                         out_rows ? out_rows + (size_t)q * k : nullptr);
+  });
+  return TSH_OK;
+}
+
+int32_t tsh_search_grouped_rows_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+  for (auto &sp : idx->shards) {
+    out[0] += sp->c_grows.load();
+    out[1] += sp->c_grows_marked.load();
+    out[2] += sp->c_grows_side.load();
+    out[3] += sp->c_grows_redone.load();
+    out[4] += sp->c_grows_all.load();
   }
   return TSH_OK;
 }

@@ -145,6 +145,12 @@ typedef _SearchGroupedCountD = int Function(Pointer<Void>, Pointer<Float>, int, 
     Pointer<Void>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>);
 typedef _SearchGroupedAfterStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
 typedef _SearchGroupedAfterStatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchGroupedRowsC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Int32, Double, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchGroupedRowsD = int Function(Pointer<Void>, Pointer<Float>, int, int, int, double, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchGroupedRowsStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _SearchGroupedRowsStatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
@@ -395,6 +401,8 @@ final class HipVectorBackend {
   static late final _SearchGroupedAfterD _searchGroupedAfter;
   static late final _SearchGroupedCountD _searchGroupedCount;
   static late final _SearchGroupedAfterStatsD _searchGroupedAfterStats;
+  static late final _SearchGroupedRowsD _searchGroupedRows;
+  static late final _SearchGroupedRowsStatsD _searchGroupedRowsStats;
   static late final _ProbeScanI8D _probeScanI8;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
@@ -479,6 +487,10 @@ final class HipVectorBackend {
           lib.lookupFunction<_SearchGroupedCountC, _SearchGroupedCountD>('tsh_search_grouped_count');
       _searchGroupedAfterStats =
           lib.lookupFunction<_SearchGroupedAfterStatsC, _SearchGroupedAfterStatsD>('tsh_search_grouped_after_stats');
+      _searchGroupedRows =
+          lib.lookupFunction<_SearchGroupedRowsC, _SearchGroupedRowsD>('tsh_search_grouped_rows');
+      _searchGroupedRowsStats =
+          lib.lookupFunction<_SearchGroupedRowsStatsC, _SearchGroupedRowsStatsD>('tsh_search_grouped_rows_stats');
       _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
@@ -1135,6 +1147,74 @@ final class HipVectorBackend {
     try {
       if (_searchGroupedStats(_handle, o) != 0) return null;
       return {'searches': o[0], 'sideRows': o[1], 'redone': o[2], 'noDevicePasses': o[3]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
+  /// The `groupSize` nearest rows of each of the `topK` nearest groups (tsh_search_grouped_rows; no reference
+  /// counterpart): the winning groups are [searchGrouped]'s, in its order, and of each the first `groupSize` entries of
+  /// the list [search] would return with topK = infinity, in that list's order -- a document's best passages from the
+  /// one scan.  One inner list per group returned; a group with fewer surviving rows gives what it has.  `groupSize`
+  /// runs from 1 to 64.  Null on any native failure; a disposed [HipRowGroups] or [HipRowMask] is refused (null, with a
+  /// warning), never sent as NULL.
+  List<List<HipGroupedResult>>? searchGroupedRows(Float32List query, int topK, int groupSize, HipRowGroups groups,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) {
+    if (groups._groups == nullptr) {
+      Logger.warn('searchGroupedRows with a disposed HipRowGroups', label: 'HipVectorBackend');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchGroupedRows with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    if (groupSize < 1 || groupSize > 64) {
+      Logger.warn('searchGroupedRows: groupSize $groupSize outside [1, 64]', label: 'HipVectorBackend');
+      return null;
+    }
+    if (topK <= 0 || size == 0) return <List<HipGroupedResult>>[];
+    final q = calloc<Float>(dimensions);
+    final ids = calloc<Int64>(topK * groupSize);
+    final dist = calloc<Double>(topK * groupSize);
+    final grp = calloc<Int32>(topK);
+    final rows = calloc<Int32>(topK);
+    final cnt = calloc<Int32>();
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      q.asTypedList(dimensions).setAll(0, query);
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = _searchGroupedRows(_handle, q, 1, topK, groupSize, distanceThreshold ?? double.nan, maskBytes,
+          mask != null ? mask._mask : nullptr, groups._groups, ids, dist, grp, rows, cnt);
+      if (rc != 0) {
+        Logger.warn('tsh_search_grouped_rows failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return [
+        for (var i = 0; i < cnt.value; ++i)
+          [for (var j = 0; j < rows[i]; ++j) HipGroupedResult(ids[i * groupSize + j], dist[i * groupSize + j], grp[i])]
+      ];
+    } finally {
+      calloc.free(q);
+      calloc.free(ids);
+      calloc.free(dist);
+      calloc.free(grp);
+      calloc.free(rows);
+      calloc.free(cnt);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
+  }
+
+  /// The rows-per-group searches' counters (tsh_search_grouped_rows_stats), per shard job: the searches, groups their
+  /// mark passes marked, member rows sent on for exact sums, jobs redone with larger lists, jobs answered by the
+  /// exact-all route.
+  Map<String, int>? searchGroupedRowsStats() {
+    final o = calloc<Int64>(5);
+    try {
+      if (_searchGroupedRowsStats(_handle, o) != 0) return null;
+      return {'searches': o[0], 'markedGroups': o[1], 'memberRows': o[2], 'redone': o[3], 'exactAll': o[4]};
     } finally {
       calloc.free(o);
     }

@@ -215,6 +215,35 @@ class VectorIndexManager:
             out.append(VectorSearchResult(primaryKey=self._pk.get(node), distance=d, score=distance_to_score(d, self.metric), nodeId=node))
         return out
 
+    def vectorSearchGroups(self, queryVector: Sequence[float], group_by, topK: int = 10, groupSize: int = 3,
+                           distanceThreshold: Optional[float] = None, rowMask=None,
+                           pk_of: Optional[Callable[[int], Optional[str]]] = None) -> list:
+        """The groupSize nearest rows of each of the topK nearest groups (no reference counterpart; vectorSearch itself is
+        unchanged): a list of (group, [results]) in the order vectorSearch(group_by=) lists the groups, group -1 for a row
+        that stands for itself, each group's results in the result order (distance, then node id)
+        (HipVectorIndex.search_grouped_rows) -- a document's best passages from the one scan.  groupSize: 1 to 64.  A row
+        whose primary key `pk_of` does not know is dropped from its group's results; a group left without any is dropped."""
+        if self.index.size == 0 or topK <= 0:
+            return []
+        query_f32 = to_float32(queryVector, self.dimensions)
+        if self.metric == METRIC_COSINE:
+            query_f32 = normalize_float32(query_f32)
+        ids, dist, grp, rows, cnt = self.index.search_grouped_rows(query_f32, topK, groupSize, group_by, distance_threshold=distanceThreshold,
+                                                                   row_mask=rowMask)
+        lookup = pk_of if pk_of is not None else self._pk.get
+        out = []
+        for i in range(int(cnt[0])):
+            results = []
+            for j in range(int(rows[0, i])):
+                node, d = int(ids[0, i, j]), float(dist[0, i, j])
+                pk = lookup(node)
+                if pk is None:
+                    continue
+                results.append(VectorSearchResult(primaryKey=pk, distance=d, score=distance_to_score(d, self.metric), nodeId=node))
+            if results:
+                out.append((int(grp[0, i]), results))
+        return out
+
     def countGroups(self, queryVector: Sequence[float], group_by, distanceThreshold: Optional[float] = None, rowMask=None, after=None) -> int:
         """How many groups a grouped search would list (HipVectorIndex.count_groups): all of them, or those past `after`."""
         if self.index.size == 0:
