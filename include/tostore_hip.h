@@ -459,8 +459,9 @@ int32_t tsh_search_count_stats(tsh_index *idx, int64_t *out);
  *   is 0.45 resp. 0.35, and it costs what tsh_search_count costs ("Grouped search";
  *   profiles/search_grouped_ab.json).
  * A cursor, so that groups can be paged, and a count of groups: tsh_search_grouped_after and tsh_search_grouped_count,
- *   below.  More than one row per group: tsh_search_grouped_rows, below them.  The next step would bring, none of it
- *   here: a ticket form (tsh_search_submit_grouped).  The tsh_search_shard* and tsh_search_sharded* entries.
+ *   below.  More than one row per group: tsh_search_grouped_rows, below them.  Across row-range shards, one process
+ *   per GPU: tsh_search_shard_grouped, tsh_merge_candidates_grouped and tsh_search_sharded_grouped, with the other
+ *   sharded entries below.  The next step would bring, none of it here: a ticket form (tsh_search_submit_grouped).
  * tsh_counters keeps its layout; a grouped search counts in searches and scan_launches like any other search.
  * The handle is a tsh_groups * (typedef below).  In the prototypes it travels as `void *`, and tsh_groups_create's
  * `out` -- the address of the caller's tsh_groups * (a tsh_groups **) -- as `void *` too: the bindings' prototype tables
@@ -707,6 +708,57 @@ int32_t tsh_search_shard_masked(tsh_index *idx, const float *queries, int32_t nq
 int32_t tsh_search_shard_begin_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, tsh_mask *mask,
                                       const double *after_dist, const int64_t *after_id, int32_t entries,
                                       void *d_out_blocks, int32_t step, tsh_shard_stream **out);
+/* The sharded entries of the plain grouped search (tsh_search_grouped's semantics: no cursor, one row per group; additive
+ * since ABI 5; tsh_search_sharded_grouped is with the collective below).  The merged answer is bit for bit the one
+ * tsh_search_grouped gives on one un-sharded index over the same rows, the same GLOBAL group_of array, the same mask,
+ * tombstones and threshold.  Groups MAY have rows on any number of ranks.
+ *   row_mask / mask   GLOBAL, at most one of them: the pointer form, or a handle under tsh_search_shard_masked's rules.
+ *   groups      a handle made on THIS shard handle from the GLOBAL array (tsh_groups_create takes shard handles with
+ *               global ids).  Every rank makes its own from the same array; as with masks, the library does not check
+ *               that the ranks agree.  It travels as `void *`, as in tsh_search_grouped.
+ * Blocks: layout and tsh_candidate_block_bytes are unchanged.  A grouped block holds, with their exact sums, the
+ * select's candidates over the group HEADS (one row per group by f32 key), the SIDE rows (rows that are not their
+ * group's head by f32 key but may be by exact distance) and the quarantined rows that the mask keeps.  No group id
+ * travels in a block: the merge looks it up by global id.  A block the side rows do not fit in reports count > entries,
+ * the usual overflow protocol.
+ * tsh_merge_candidates_grouped is pure host code, no device: group_of / n_group_of is the same global array; an id at
+ * or beyond it, or a negative entry, is ungrouped, as in the groups handle.  It is the grouped finaliser over the UNION
+ * of all blocks' entries -- the step tsh_search_grouped runs over several devices: order by (distance, id), keep the
+ * first entry of every group, cut to k.  Exact for groups that span ranks: every rank's block holds each of its groups'
+ * exact best among the rows it may contribute (head and side rows), so the best entry of a group in the union is the
+ * group's best overall, and a rank offers at least its k nearest groups, of which no more than k can precede the
+ * answer's last.  out_group is nullable; unused slots read id -1, distance NaN, group -1.  A truncated block
+ * (count > entries) answers TSH_E_OVERFLOW with *needed_entries, as in tsh_merge_candidates.
+ * A grouped sharded call is never batched, whatever step or TSH_OPT_BATCH_MIN_NQ say: every query is its own f32 tile
+ * scan or list scan, never the exact path or the fp16 / int8 copies, as for the other grouped jobs.  Safe mode runs no
+ * device group passes: its blocks are tsh_search_shard's and the merge does the grouping.
+ * Argument errors are tsh_search_grouped's (TSH_E_BAD_ARG): both mask forms at once, NULL `groups`, a groups or mask
+ * handle of another index, an orphaned handle.  Trivial cases: with k <= 0 or an empty shard the shard still emits valid
+ * empty blocks, so that an exchange is never short a block; they merge to counts of 0.
+ * The groups handle is held shared while the search reads it -- the whole call, resp. the progressive search's thread
+ * from _begin until its last block is final; the handle must outlive _end, like a mask handle.
+ * tsh_search_grouped_stats on the shard handle counts these jobs (searches, side rows, redone, safe mode); no other
+ * *_stats moves and tsh_counters keeps its layout.
+ * Cost: a grouped shard search costs what tsh_search_grouped costs on the shard handle plus the side rows' append.
+ *   Measured on one MI355X (profiles/shard_grouped_ab.json, tools/ab_shard_grouped.py; two ranks sharing the GPU, two
+ *   shard handles of 500 k x 768 f32, L2, groups of 8 rows, 64-query calls over the host transport, us per query,
+ *   medians): tsh_search_sharded_grouped 458.7 - 460.2 at k = 10 and 458.8 - 460.5 at k = 100, against 468.5 - 473.3 resp.
+ *   531.5 - 538.3 for every rank's tsh_search_grouped plus a host gather and a NumPy merge -- not slower, which is all
+ *   that is claimed; tsh_search_sharded on the same shards 12 - 13.4 (one batched pass over a reduced copy, where a
+ *   grouped call is 64 f32 scans: DESIGN.md, "Grouped search", "Across shards").
+ * Out of scope: a cursor, a count or several rows per group across ranks (a group consumed on one rank can reappear from
+ * another, and a winning group's second row can lie on a rank where the group is not marked: both need a second
+ * exchange); a ticket form; any change to the grouped kernels' rules; the fp16 / int8 copies for grouped jobs. */
+int32_t tsh_search_shard_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask,
+                                 tsh_mask *mask, void *groups, int32_t entries, void *d_out_blocks, void *stream);
+int32_t tsh_search_shard_begin_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k,
+                                       const uint8_t *row_mask, tsh_mask *mask, void *groups, int32_t entries,
+                                       void *d_out_blocks, int32_t step, tsh_shard_stream **out);
+int32_t tsh_merge_candidates_grouped(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k,
+                                     double distance_threshold, const int32_t *group_of, int64_t n_group_of,
+                                     const void *blocks, int32_t n_blocks, int32_t entries, int64_t *out_ids,
+                                     double *out_dist, int32_t *out_group, int32_t *out_count,
+                                     int32_t *needed_entries);
 
 /* ---- the same exchange from a host without torch (a Dart process per GPU) ------------------------------------
  * RCCL all-gather of the per-shard candidate blocks over xGMI + host merge, behind plain C.  librccl is loaded
@@ -769,6 +821,19 @@ int32_t tsh_search_sharded_after(tsh_index *shard, tsh_comm *comm, const float *
 int32_t tsh_search_sharded_masked(tsh_index *shard, tsh_comm *comm, const float *queries, int32_t nq, int32_t k,
                                   double distance_threshold, tsh_mask *mask, const double *after_dist,
                                   const int64_t *after_id, int64_t *out_ids, double *out_dist, int32_t *out_count);
+/* tsh_search_sharded for the plain grouped search (see tsh_search_shard_grouped above): identical answer on every rank --
+ * the one tsh_search_grouped gives on one un-sharded index over the same rows and the same GLOBAL group_of array.
+ * row_mask / mask: GLOBAL, at most one; groups: this rank's handle, made on `shard`.  Groups follow the scan schedule
+ * (the shrinking groups) on every rank alike, and a group of queries is exchanged only when its blocks are FINAL,
+ * whatever TSH_OPT_EXCHANGE_AHEAD says: a grouped job can be redone by the host, as a cursor job can.  Failure protocol
+ * and timeline: tsh_search_sharded's.  A bad groups handle (NULL, another index's, orphaned), a bad mask handle or both
+ * mask forms at once is a LOCAL failure: the rank stays in the collective and returns its own error, its peers return
+ * TSH_E_PEER, the communicator stays usable.  Where only the slice owner merges and a second all-gather hands out ids
+ * and distances, every rank fills out_group (nullable) by looking the ids up in its own handle's array: the wire
+ * format of the result gather does not change. */
+int32_t tsh_search_sharded_grouped(tsh_index *shard, tsh_comm *comm, const float *queries, int32_t nq, int32_t k,
+                                   double distance_threshold, const uint8_t *row_mask, tsh_mask *mask, void *groups,
+                                   int64_t *out_ids, double *out_dist, int32_t *out_group, int32_t *out_count);
 
 /* Where the time of this rank's tsh_search_sharded calls went: sums over the calls since the communicator was made
  * (or since the last reset).  On the calling thread a call is, group after group,

@@ -134,6 +134,11 @@ SIGNATURES = {
     "tsh_search_shard_masked": (c_i32, [p_void, p_f32, c_i32, c_i32, p_void, p_f64, p_i64, c_i32, p_void, p_void]),
     "tsh_search_shard_begin_masked": (c_i32, [p_void, p_f32, c_i32, c_i32, p_void, p_f64, p_i64, c_i32, p_void, c_i32,
                                               ctypes.POINTER(p_void)]),
+    "tsh_search_shard_grouped": (c_i32, [p_void, p_f32, c_i32, c_i32, p_u8, p_void, p_void, c_i32, p_void, p_void]),
+    "tsh_search_shard_begin_grouped": (c_i32, [p_void, p_f32, c_i32, c_i32, p_u8, p_void, p_void, c_i32, p_void, c_i32,
+                                               ctypes.POINTER(p_void)]),
+    "tsh_merge_candidates_grouped": (c_i32, [c_i32, c_i32, p_f32, c_i32, c_i32, c_f64, p_i32, c_i64, p_void, c_i32, c_i32,
+                                             p_i64, p_f64, p_i32, p_i32, p_i32]),
     "tsh_comm_unique_id": (c_i32, [p_void]),
     "tsh_comm_create": (c_i32, [p_void, c_i32, c_i32, c_i32, ctypes.POINTER(p_void)]),
     "tsh_comm_create_host": (c_i32, [c_i32, c_i32, c_i32, p_void, p_void, ctypes.POINTER(p_void)]),
@@ -145,6 +150,8 @@ SIGNATURES = {
                                          p_i32]),
     "tsh_search_sharded_masked": (c_i32, [p_void, p_void, p_f32, c_i32, c_i32, c_f64, p_void, p_f64, p_i64, p_i64, p_f64,
                                           p_i32]),
+    "tsh_search_sharded_grouped": (c_i32, [p_void, p_void, p_f32, c_i32, c_i32, c_f64, p_u8, p_void, p_void, p_i64, p_f64,
+                                           p_i32, p_i32]),
     "tsh_comm_get_timeline": (c_i32, [p_void, ctypes.POINTER(TshCommTimeline), c_i32]),
     "tsh_get_counters": (c_i32, [p_void, ctypes.POINTER(TshCounters)]),
     "tsh_bench_scan": (c_i32, [p_void, p_f32, c_i32, p_u8, p_f64]),

@@ -96,6 +96,9 @@ class HipGroups:
         self.n_groups = int(n_groups)
         _ffi.check(_ffi.lib().tsh_groups_create(index._h, g.ctypes.data_as(_ffi.p_i32), g.shape[0], self.n_groups,
                                                 ctypes.byref(self._h)))
+        # the array as the handle holds it: what a sharded caller's host merge looks the groups up in
+        # (sharded.merge_candidate_blocks; the library's own collective reads the handle's copy)
+        self.group_of = g.copy()
         index._live_masks().add(self)
 
     def handle(self):
@@ -108,6 +111,10 @@ class HipGroups:
         """Entries [first_row_id, first_row_id + len(group_of)) of the array, extended where it was shorter."""
         g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
         _ffi.check(_ffi.lib().tsh_groups_set(self.handle(), int(first_row_id), g.shape[0], g.ctypes.data_as(_ffi.p_i32)))
+        end = int(first_row_id) + g.shape[0]
+        if g.shape[0] and end > self.group_of.shape[0]:
+            self.group_of = np.concatenate([self.group_of, np.full(end - self.group_of.shape[0], -1, dtype=np.int32)])
+        self.group_of[int(first_row_id):end] = g
 
     def close(self) -> None:
         if self._h:

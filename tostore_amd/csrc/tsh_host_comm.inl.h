@@ -367,10 +367,14 @@ int comm_exchange_enqueue(tsh_comm *c, const uint8_t *d_blocks, int32_t gq, int3
 // then a rank whose scans failed cannot mark its blocks any more -- its peers see that from the blocks' generation
 // (tag: what BlockHeader.pad[1] of every block of this group must say; 0 = blocks of a synchronous shard search).
 // after: the cursors of the group's queries (tsh_search_sharded_after), or none.
+// table: a grouped call (tsh_search_sharded_grouped) on a rank whose groups handle is good -- the merge is finalize_grouped
+// over the union of every rank's entries; out_group: filled from this rank's own table once the ids are in place, for
+// the slices other ranks merged too (the result gather's wire format carries no groups).
 // Collective; returns the same verdict class on every rank (own error / TSH_E_PEER / TSH_OK + need).
 int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int local_rc, const float *queries, int32_t gq,
                         int32_t k, double thr, int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count,
-                        GroupOut *go, bool enqueued = false, uint32_t tag = 0, Cursors after = Cursors()) {
+                        GroupOut *go, bool enqueued = false, uint32_t tag = 0, Cursors after = Cursors(), const GroupTable *table = nullptr,
+                        int32_t *out_group = nullptr) {
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries), W = (size_t)c->world, mine = bb * (size_t)gq;
   const bool whole = merge_whole(W, (size_t)gq);  // (same on every rank: W and gq are)
   const int32_t slice_q = whole ? gq : (int32_t)(((size_t)gq + W - 1) / W);
@@ -467,7 +471,8 @@ int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int lo
         double *dd = reinterpret_cast<double *>(r + (size_t)k * 8);
         int32_t *cnt = reinterpret_cast<int32_t *>(r + (size_t)k * 16);
         Cursor cur;  // (this rank's slice and the whole group alike: the cursor of query a + i)
-        cnt[0] = finalize_query(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, ids, dd, nullptr, after.at(a + i, &cur));
+        if (table) cnt[0] = finalize_grouped(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, *table, ids, dd, nullptr);
+        else cnt[0] = finalize_query(metric, dim, queries + (size_t)(a + i) * dim, k, thr, lp, W, ids, dd, nullptr, after.at(a + i, &cur));
         cnt[1] = 0;
       });
     }
@@ -514,6 +519,8 @@ int comm_exchange_group(tsh_comm *c, tsh_index *shard, uint8_t *d_blocks, int lo
       memcpy(out_ids + (size_t)q * k, r, (size_t)k * 8);
       memcpy(out_dist + (size_t)q * k, r + (size_t)k * 8, (size_t)k * 8);
       out_count[q] = *reinterpret_cast<const int32_t *>(r + (size_t)k * 16);
+      if (table && out_group)  // (unused slots read id -1: ungrouped there too)
+        for (int32_t i = 0; i < k; ++i) out_group[(size_t)q * k + i] = table->at(out_ids[(size_t)q * k + i]);
     }
   }
   tl.copy_out_us += now_us() - t4;
@@ -570,7 +577,8 @@ int comm_check_create(const void *id_or_fn, int32_t world, int32_t rank, int32_t
 }
 
 int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
-                        const CallMask &mask, Cursors after, int64_t *out_ids, double *out_dist, int32_t *out_count);
+                        const CallMask &mask, Cursors after, int64_t *out_ids, double *out_dist, int32_t *out_count,
+                        bool grouped = false, tsh_groups *groups = nullptr, int32_t *out_group = nullptr);
 
 }  // namespace
 
@@ -681,6 +689,14 @@ int32_t tsh_search_sharded_masked(tsh_index *shard, tsh_comm *c, const float *qu
   if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
   return search_sharded_impl(shard, c, queries, nq, k, thr, CallMask{nullptr, mask}, Cursors{after_dist, after_id}, out_ids, out_dist, out_count);
 }
+int32_t tsh_search_sharded_grouped(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
+                                   const uint8_t *row_mask, tsh_mask *mask, void *groups, int64_t *out_ids, double *out_dist,
+                                   int32_t *out_group, int32_t *out_count) {
+  if (!c && !shard && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  // (both mask forms, a NULL or foreign groups handle: this rank's own failures, answered through the exchange)
+  return search_sharded_impl(shard, c, queries, nq, k, thr, CallMask{row_mask, mask}, Cursors(), out_ids, out_dist, out_count, true,
+                             static_cast<tsh_groups *>(groups), out_group);
+}
 
 }  // extern "C"
 
@@ -693,7 +709,8 @@ namespace {
 // mask.handle: a mask handle in place of the bitmap (tsh_search_sharded_masked), or NULL -- this rank's own, so a bad one is a
 // local failure that travels through the exchange like a bad shard handle.
 int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int32_t nq, int32_t k, double thr,
-                        const CallMask &mask, Cursors after, int64_t *out_ids, double *out_dist, int32_t *out_count) {
+                        const CallMask &mask, Cursors after, int64_t *out_ids, double *out_dist, int32_t *out_count, bool grouped,
+                        tsh_groups *groups, int32_t *out_group) {
   // arguments that are the same on every rank by contract are answered locally ...
   if (!c) return set_err(TSH_E_BAD_ARG, "comm is NULL");
   if (nq < 0) return set_err(TSH_E_BAD_ARG, "nq < 0");
@@ -711,6 +728,23 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
     local_rc = set_err(TSH_E_BAD_ARG, "shard and communicator sit on different devices");
   else if (mask.handle && mask.handle->idx != shard)
     local_rc = set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
+  else if (grouped && mask.bytes && mask.handle)
+    local_rc = set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  else if (grouped && !groups)
+    local_rc = set_err(TSH_E_BAD_ARG, "groups is NULL");
+  else if (grouped && groups->idx != shard)
+    local_rc = set_err(TSH_E_BAD_ARG, "the groups handle was made for another index (or its index was destroyed)");
+  // a grouped call on a rank whose handle is good: the array stays as it is until the last merge of the call has read it
+  // (held here once for the window's scans on the helper thread, the retries and the merges: ShardSearchReq::groups_held)
+  std::shared_lock<std::shared_mutex> use;
+  GroupTable gtable;
+  const bool lone = after || grouped;  // every query its own scan on every rank, exchanged once its block is final
+  if (grouped && local_rc == TSH_OK) {
+    use = std::shared_lock<std::shared_mutex>(groups->use_mu);
+    gtable = GroupTable{groups->group_of.data(), (int64_t)groups->group_of.size()};
+  }
+  const GroupTable *const table = grouped && local_rc == TSH_OK ? &gtable : nullptr;
+  tsh_groups *const sgroups = table ? groups : nullptr;  // what the shard searches take
   std::string local_err = g_err;
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
@@ -754,7 +788,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
     for (int32_t q = 0; q < nq; q += Gmax) sizes.push_back(std::min(Gmax, nq - q));
   } else {
     // (a cursor call: the scan schedule -- the argument is the same on every rank, which no rank's own batch flag is)
-    sharded_schedule(nq, (double)c->scan_bytes_hint / 6.5e6, &sizes, after ? false : c->batch_hint);
+    sharded_schedule(nq, (double)c->scan_bytes_hint / 6.5e6, &sizes, lone ? false : c->batch_hint);
   }
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
   size_t gi = 0;  // next group
@@ -779,8 +813,8 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       opt.step = sizes[gi];
       opt.tag = ss_tag;
       opt.exec = c->worker.get();
-      opt.leave_overflow = !after && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
-      scan_rc = shard_stream_begin(shard, ShardSearchReq{queries + (size_t)w0 * dim, wn, k, entries, mask, after.from(w0), c->d_mine}, opt, &ss);
+      opt.leave_overflow = !lone && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire);
+      scan_rc = shard_stream_begin(shard, ShardSearchReq{queries + (size_t)w0 * dim, wn, k, entries, mask, after.from(w0), c->d_mine, sgroups, true}, opt, &ss);
       if (scan_rc) scan_err = g_err;
     }
     auto end_stream = [&] {  // nothing of this call may still run when it returns
@@ -796,7 +830,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       // behind their block writers (comm_exchange_enqueue): the collective's launch costs the host tens of
       // microseconds, which would otherwise follow the last block
       bool enqueued = false;
-      if (ss && scan_rc == TSH_OK && !after && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire)) {
+      if (ss && scan_rc == TSH_OK && !lone && c->comm && !c->host_fn && exchange_ahead_flag().load(std::memory_order_acquire)) {
         const double t_e = now_us();
         hipEvent_t behind[MAX_CTX];  // the block writers' events
         const int n_after = shard_stream_enqueued(ss, q0 + gq, behind, MAX_CTX);
@@ -825,7 +859,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
       GroupOut go;
       rc = comm_exchange_group(c, shard, c->d_mine + (size_t)q0 * bb, scan_rc, queries + (size_t)qa * dim, gq, k, thr,
                                entries, out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, enqueued,
-                               ss_tag, after.from(qa));
+                               ss_tag, after.from(qa), table, out_group ? out_group + (size_t)qa * k : nullptr);
       tl.groups++;
       for (int attempt = 0; rc == TSH_OK && go.need > 0; ++attempt) {
         // ties made a block overflow: every rank saw the same verdict and redoes this group with larger blocks, in a
@@ -846,7 +880,7 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
         std::string again_err = local_rc != TSH_OK ? local_err : scan_err;
         if (again_rc == TSH_OK) {
           const double t0 = now_us();
-          again_rc = search_shard_impl(shard, ShardSearchReq{queries + (size_t)qa * dim, gq, k, ent, mask, after.from(qa), c->d_retry}, nullptr);
+          again_rc = search_shard_impl(shard, ShardSearchReq{queries + (size_t)qa * dim, gq, k, ent, mask, after.from(qa), c->d_retry, sgroups, true}, nullptr);
           c->scan_ns.fetch_add((int64_t)((now_us() - t0) * 1e3), std::memory_order_relaxed);
           if (again_rc) again_err = g_err;
         }
@@ -854,7 +888,8 @@ int search_sharded_impl(tsh_index *shard, tsh_comm *c, const float *queries, int
         if (again_rc) g_err = again_err;
         go = GroupOut();
         rc = comm_exchange_group(c, shard, c->d_retry, again_rc, queries + (size_t)qa * dim, gq, k, thr, ent,
-                                 out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, false, 0, after.from(qa));
+                                 out_ids + (size_t)qa * k, out_dist + (size_t)qa * k, out_count + qa, &go, false, 0, after.from(qa), table,
+                                 out_group ? out_group + (size_t)qa * k : nullptr);
         tl.groups++;
       }
       if (rc) {

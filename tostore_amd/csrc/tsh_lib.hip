@@ -1033,6 +1033,9 @@ struct Job {
   // second time, with larger lists or on the exact-all route
   int32_t group_rows = 0;
   bool rows_redone = false;
+  // shard mode: the side rows' entries were appended to the caller's device block (A2', tsh_after.hip.h) -- a cursor job's
+  // and a plain grouped job's (tsh_search_shard_after, tsh_search_shard_grouped); nothing of them reaches the host lists
+  bool side_in_block() const { return dev_target && ((floored && !grouped) || (grouped && !floored && !windowed && group_rows == 0)); }
   const float *redo_query = nullptr;  // the caller's query (a ticket's own copy): valid until the job is finished
   std::vector<uint64_t> redo_words;   // a ticket's copy of a pointer mask's words (JobReq::mask_dies), else empty
 };
@@ -1853,9 +1856,15 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     TSH_LAUNCH_EV(rerank_kernel, (unsigned)std::min(j->entries, 1024), 64, ts, none, none, ka.ra);
     const GroupSideArgs gs{ga, ka.se.hdr, c->d_side_rows, side_count, side_cap, ka.se.eps_rel, ka.se.delta_abs};
     group_side_kernel<<<tgrid, 256, 0, ts>>>(gs);
-    const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
-                           s->dim, s->metric, side_cap};
-    TSH_LAUNCH_EV(after_side_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, ts, none, done, sd);
+    if (j->dev_target) {
+      // shard mode (tsh_search_shard_grouped): the side rows' entries go into the caller's device block behind the
+      // re-rank's, by the cursor jobs' own append (in front of the quarantined rows' append: both draw places in the block)
+      launch_after_side_append(s, c, j, ts, done);
+    } else {
+      const AfterSideArgs sd{s->d_rows, c->d_query, c->d_side_rows, side_count, c->d_side_cnt + (j->side_word ^ 1), c->h_side_dev, s->ld, s->row_base,
+                             s->dim, s->metric, side_cap};
+      TSH_LAUNCH_EV(after_side_kernel, side_cap > (uint32_t)AFTER_SIDE_CAP ? std::min(side_cap, 1024u) : 64u, 64, ts, none, done, sd);
+    }
   } else {
     // a cursor job: the floor pass takes the rows at or before the cursor out of the select's sight (A1), and the rows
     // it could not decide get their exact sums behind the re-rank (A2) -- tsh_after.hip.h
@@ -2329,8 +2338,8 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   } else if (h->flags & FLAG_LIST_OVERFLOW) {
     int rc = run_fallback(s, j, h->band_key, spill);  // keys[] of this query are still in the context
     if (rc) return rc;
-    if (j->dev_target && (j->floored || !j->quar_sel.empty())) {  // the fallback rewrote the device block: append again
-      if (j->floored) launch_after_side_append(s, c, j, s->aux_stream, nullptr);
+    if (j->side_in_block() || (j->dev_target && !j->quar_sel.empty())) {  // the fallback rewrote the device block: append again
+      if (j->side_in_block()) launch_after_side_append(s, c, j, s->aux_stream, nullptr);
       if (!j->quar_sel.empty()) launch_quarantine_append(s, c, j, s->aux_stream);
       HIPCHK(hipStreamSynchronize(s->aux_stream));
       HIPCHK(hipGetLastError());
@@ -2359,8 +2368,8 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
     s->c_after++;
     if (j->after_skip || (j->route.band.force_all && !j->after.from_start())) s->c_after_nofloor++;
   }
-  if (j->floored && j->dev_target) {  // (shard mode: the side rows' entries are in the device block already)
-    s->c_after_side += c->h_side[0].id;
+  if (j->side_in_block()) {  // (shard mode: the side rows' entries are in the device block already)
+    (j->grouped ? s->c_grouped_side : s->c_after_side) += c->h_side[0].id;
   } else if (j->floored || j->windowed || j->grouped) {  // the rows the floor / window / side pass could not decide join the candidates too
     if (!extra) return set_err(TSH_E_BAD_ARG, "no room for the side list's entries");
     if (j->quar_sel.empty()) extra->clear();
@@ -2956,7 +2965,22 @@ struct ShardSearchReq {
   CallMask mask;
   Cursors after;
   uint8_t *d_blocks = nullptr;
+  // a grouped call (tsh_search_shard_grouped and its kin): the groups handle made on this shard handle, or none.  Never
+  // with cursors; k <= 0 is answered with empty blocks
+  tsh_groups *groups = nullptr;
+  // ... whose use_mu the caller holds shared for as long as the search runs (tsh_search_sharded_grouped: one lock for the
+  // call's scans, retries and merges) -- it is not taken again here
+  bool groups_held = false;
 };
+// What every grouped shard-level entry checks before it runs (tsh_search_grouped's argument errors)
+inline int check_shard_groups(tsh_index *idx, const CallMask &m, const tsh_groups *groups) {
+  if (m.bytes && m.handle) return set_err(TSH_E_BAD_ARG, "row_mask and mask are both given: at most one");
+  if (!groups) return set_err(TSH_E_BAD_ARG, "groups is NULL");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (groups->idx != idx) return set_err(TSH_E_BAD_ARG, "the groups handle was made for another index (or its index was destroyed)");
+  return TSH_OK;
+}
 // ... and how a progressive one (shard_stream_begin) is to run
 struct ShardStreamOpts {
   int32_t step = 0;            // matrix-core route: queries per batched call (0: all in one)
@@ -3977,11 +4001,15 @@ namespace {
 int32_t search_shard_impl(tsh_index *idx, const ShardSearchReq &r, void *stream) {
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
   if (r.mask.handle && r.mask.handle->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
-  if (r.nq <= 0 || !r.queries || !r.d_blocks || r.k <= 0 || r.entries < 1)
+  if (r.nq <= 0 || !r.queries || !r.d_blocks || (r.k <= 0 && !r.groups) || r.entries < 1)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / pointers");
   Shard *s = idx->shards[0].get();
+  // (a grouped call: the handle's array stays as it is while the shard's part of it is read)
+  std::shared_lock<std::shared_mutex> use;
+  if (r.groups && !r.groups_held) use = std::shared_lock<std::shared_mutex>(r.groups->use_mu);
   std::shared_lock<RwLock> sl = share(idx, s);
-  if (s->rows == 0) return write_empty_blocks(s, r.nq, r.k, r.entries, 0, r.d_blocks);  // an empty shard contributes empty blocks
+  // an empty shard contributes empty blocks, and so does a grouped call for no groups at all
+  if (s->rows == 0 || r.k <= 0) return write_empty_blocks(s, r.nq, std::max(r.k, 0), r.entries, 0, r.d_blocks);
   MaskSrc ms;
   int rc = call_mask_for_shard(r.mask, 0, s, &ms);
   if (rc) return rc;
@@ -3989,7 +4017,8 @@ int32_t search_shard_impl(tsh_index *idx, const ShardSearchReq &r, void *stream)
   so.d_blocks = r.d_blocks;
   so.user_stream = static_cast<hipStream_t>(stream);
   so.after = r.after;
-  if (r.after)  // a cursor call is never batched: every query is its own scan
+  if (r.groups && !(so.groups = groups_part(r.groups, 0, s, &rc))) return rc;
+  if (r.after || r.groups)  // a cursor call or a grouped call is never batched: every query is its own scan
     return shard_search_blocks(s, r.queries, r.nq, r.k, ms, r.entries, &so, PIPE_DEPTH);
   return shard_search_any(s, s->batch, idx->batch_min_nq.load(), r.queries, r.nq, r.k, ms, r.entries, &so);
 }
@@ -4012,6 +4041,13 @@ int32_t tsh_search_shard_masked(tsh_index *idx, const float *queries, int32_t nq
   if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
   return search_shard_impl(
       idx, ShardSearchReq{queries, nq, k, entries, {nullptr, mask}, {after_dist, after_id}, static_cast<uint8_t *>(d_out_blocks)}, stream);
+}
+int32_t tsh_search_shard_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask, tsh_mask *mask,
+                                 void *groups, int32_t entries, void *d_out_blocks, void *stream) {
+  tsh_groups *g = static_cast<tsh_groups *>(groups);
+  int rc = check_shard_groups(idx, CallMask{row_mask, mask}, g);
+  if (rc) return rc;
+  return search_shard_impl(idx, ShardSearchReq{queries, nq, k, entries, {row_mask, mask}, {}, static_cast<uint8_t *>(d_out_blocks), g}, stream);
 }
 
 // ---- progressive shard search ---------------------------------------------------------------------------------
@@ -4088,6 +4124,9 @@ struct tsh_shard_stream {
   }
   int body() {
     Shard *s = idx->shards[0].get();
+    // (a grouped search: the handle's array stays as it is for as long as this thread reads the shard's part of it)
+    std::shared_lock<std::shared_mutex> use;
+    if (req.groups && !req.groups_held) use = std::shared_lock<std::shared_mutex>(req.groups->use_mu);
     std::shared_lock<RwLock> sl = share(idx, s);
     HIPCHK(hipSetDevice(s->device));
     if (!own_mask.empty()) {
@@ -4104,17 +4143,19 @@ struct tsh_shard_stream {
     if (mrc) return mrc;
     const int32_t nq = req.nq, k = req.k, entries = req.entries;
     const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
-    if (s->rows == 0) {  // an empty shard contributes empty blocks
+    if (s->rows == 0 || k <= 0) {  // an empty shard contributes empty blocks (k <= 0: a grouped search for no groups)
       route.store(2, std::memory_order_release);
-      int erc = write_empty_blocks(s, nq, k, entries, opt.tag, req.d_blocks);
+      int erc = write_empty_blocks(s, nq, std::max(k, 0), entries, opt.tag, req.d_blocks);
       if (erc) return erc;
       publish(nq);
       return TSH_OK;
     }
     const int32_t min_nq = idx->batch_min_nq.load();
     const int32_t st = opt.step > 0 ? std::min(opt.step, nq) : nq;
-    // (a cursor call is never batched, whatever step or the handle's batch threshold say)
-    if (req.after || !shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
+    const GroupPart *gpart = nullptr;
+    if (req.groups && !(gpart = groups_part(req.groups, 0, s, &mrc))) return mrc;
+    // (a cursor call or a grouped call is never batched, whatever step or the handle's batch threshold say)
+    if (req.after || gpart || !shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
       done_q.assign((size_t)nq, 0);
       enq_q.assign((size_t)nq, 0);
       ev_q.assign((size_t)nq, nullptr);
@@ -4125,6 +4166,7 @@ struct tsh_shard_stream {
       so.tag = opt.tag;
       so.leave_overflow = opt.leave_overflow;
       so.after = req.after;
+      so.groups = gpart;
       so.on_done = [this](int32_t q) { mark(q); };
       so.on_enqueued = [this](int32_t q, hipEvent_t ev, hipStream_t where, uint64_t seq) { mark_enqueued(q, ev, where, seq); };
       route.store(1, std::memory_order_release);
@@ -4173,7 +4215,7 @@ int shard_stream_begin(tsh_index *idx, const ShardSearchReq &r, const ShardStrea
   *out = nullptr;
   if (!idx || idx->shards.size() != 1) return set_err(TSH_E_BAD_ARG, "needs a single-shard handle");
   if (r.mask.handle && r.mask.handle->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index");
-  if (r.nq <= 0 || !r.queries || !r.d_blocks || r.k <= 0 || r.entries < 1 || opt.step < 0)
+  if (r.nq <= 0 || !r.queries || !r.d_blocks || (r.k <= 0 && !r.groups) || r.entries < 1 || opt.step < 0)
     return set_err(TSH_E_BAD_ARG, "bad nq / k / entries / step / pointers");
   std::unique_ptr<tsh_shard_stream> st(new tsh_shard_stream());
   st->idx = idx;
@@ -4311,6 +4353,15 @@ int32_t tsh_search_shard_begin_masked(tsh_index *idx, const float *queries, int3
       idx, ShardSearchReq{queries, nq, k, entries, {nullptr, mask}, {after_dist, after_id}, static_cast<uint8_t *>(d_out_blocks)},
       ShardStreamOpts{step, /*copy_inputs=*/true}, out);
 }
+int32_t tsh_search_shard_begin_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k, const uint8_t *row_mask, tsh_mask *mask,
+                                       void *groups, int32_t entries, void *d_out_blocks, int32_t step, tsh_shard_stream **out) {
+  if (out) *out = nullptr;
+  tsh_groups *g = static_cast<tsh_groups *>(groups);
+  int rc = check_shard_groups(idx, CallMask{row_mask, mask}, g);
+  if (rc) return rc;
+  return shard_stream_begin(idx, ShardSearchReq{queries, nq, k, entries, {row_mask, mask}, {}, static_cast<uint8_t *>(d_out_blocks), g},
+                            ShardStreamOpts{step, /*copy_inputs=*/true}, out);
+}
 int32_t tsh_search_shard_progress(tsh_shard_stream *st, int32_t want, int32_t *out_done) {
   if (!st) return set_err(TSH_E_BAD_ARG, "stream is NULL");
   return shard_stream_progress(st, want, out_done);
@@ -4324,7 +4375,8 @@ namespace {
 // tsh_merge_candidates; after: a cursor per query (tsh_merge_candidates_after), or none
 int32_t merge_candidates_impl(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k, double thr,
                               Cursors after, const void *blocks, int32_t n_blocks,
-                              int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count, int32_t *needed_entries) {
+                              int32_t entries, int64_t *out_ids, double *out_dist, int32_t *out_count, int32_t *needed_entries,
+                              const GroupTable *table = nullptr, int32_t *out_group = nullptr) {
   if (metric < 0 || metric > 2 || dim <= 0 || nq < 0 || n_blocks < 0 || entries < 0)
     return set_err(TSH_E_BAD_ARG, "bad metric / dim / nq / n_blocks / entries");
   if (nq == 0) return TSH_OK;
@@ -4350,6 +4402,11 @@ int32_t merge_candidates_impl(int32_t metric, int32_t dim, const float *queries,
   parallel_for(nq, [&](int32_t q) {
     std::vector<EntryList> lists;
     for (int32_t b = 0; b < n_blocks; ++b) lists.push_back(block_list(base + ((size_t)b * nq + q) * bb));  // (count <= entries: see above)
+    if (table) {  // finalize_grouped over the union of the blocks' entries: the step a grouped search runs over several devices
+      out_count[q] = finalize_grouped(metric, dim, queries + (size_t)q * dim, k, thr, lists.data(), lists.size(), *table,
+                                      out_ids + (size_t)q * k, out_dist + (size_t)q * k, out_group ? out_group + (size_t)q * k : nullptr);
+      return;
+    }
     Cursor cur;
     out_count[q] = finalize_query(metric, dim, queries + (size_t)q * dim, k, thr, lists,
                                   out_ids + (size_t)q * k, out_dist + (size_t)q * k, after.at(q, &cur));
@@ -4372,6 +4429,14 @@ int32_t tsh_merge_candidates_after(int32_t metric, int32_t dim, const float *que
   if (!after_dist || !after_id) return set_err(TSH_E_BAD_ARG, "after_dist / after_id is NULL");
   return merge_candidates_impl(metric, dim, queries, nq, k, thr, Cursors{after_dist, after_id}, blocks, n_blocks, entries, out_ids, out_dist,
                                out_count, needed_entries);
+}
+int32_t tsh_merge_candidates_grouped(int32_t metric, int32_t dim, const float *queries, int32_t nq, int32_t k, double thr,
+                                     const int32_t *group_of, int64_t n_group_of, const void *blocks, int32_t n_blocks, int32_t entries,
+                                     int64_t *out_ids, double *out_dist, int32_t *out_group, int32_t *out_count, int32_t *needed_entries) {
+  if (n_group_of < 0 || (n_group_of > 0 && !group_of)) return set_err(TSH_E_BAD_ARG, "group_of is NULL / n_group_of < 0");
+  const GroupTable table{group_of, n_group_of};
+  return merge_candidates_impl(metric, dim, queries, nq, k, thr, Cursors(), blocks, n_blocks, entries, out_ids, out_dist, out_count,
+                               needed_entries, &table, out_group);
 }
 
 int32_t tsh_get_counters(tsh_index *idx, tsh_counters *out) {

@@ -213,6 +213,22 @@ typedef _SearchShardedAfterC = Int32 Function(Pointer<Void>, Pointer<Void>, Poin
     Double, Pointer<Uint8>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchShardedAfterD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, int, int,
     double, Pointer<Uint8>, Pointer<Double>, Pointer<Int64>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
+typedef _SearchShardGroupedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Void>, Int32, Pointer<Void>, Pointer<Void>);
+typedef _SearchShardGroupedD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Void>, int, Pointer<Void>, Pointer<Void>);
+typedef _ShardBeginGroupedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Void>, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
+typedef _ShardBeginGroupedD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Uint8>,
+    Pointer<Void>, Pointer<Void>, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
+typedef _MergeGroupedC = Int32 Function(Int32, Int32, Pointer<Float>, Int32, Int32, Double, Pointer<Int32>,
+    Int64, Pointer<Void>, Int32, Int32, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>, Pointer<Int32>);
+typedef _MergeGroupedD = int Function(int, int, Pointer<Float>, int, int, double, Pointer<Int32>,
+    int, Pointer<Void>, int, int, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchShardedGroupedC = Int32 Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, Int32, Int32,
+    Double, Pointer<Uint8>, Pointer<Void>, Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
+typedef _SearchShardedGroupedD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Float>, int, int,
+    double, Pointer<Uint8>, Pointer<Void>, Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>, Pointer<Int32>);
 typedef _SearchShardMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Pointer<Void>,
     Pointer<Double>, Pointer<Int64>, Int32, Pointer<Void>, Pointer<Void>);
 typedef _SearchShardMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, Pointer<Void>,
@@ -422,6 +438,10 @@ final class HipVectorBackend {
   static late final _ShardBeginAfterD _shardBeginAfter;
   static late final _MergeAfterD _mergeAfter;
   static late final _SearchShardedAfterD _searchShardedAfter;
+  static late final _SearchShardGroupedD _searchShardGrouped;
+  static late final _ShardBeginGroupedD _shardBeginGrouped;
+  static late final _MergeGroupedD _mergeGrouped;
+  static late final _SearchShardedGroupedD _searchShardedGrouped;
   static late final _SearchShardMaskedD _searchShardMasked;
   static late final _ShardBeginMaskedD _shardBeginMasked;
   static late final _SearchShardedMaskedD _searchShardedMasked;
@@ -516,6 +536,13 @@ final class HipVectorBackend {
       _mergeAfter = lib.lookupFunction<_MergeAfterC, _MergeAfterD>('tsh_merge_candidates_after');
       _searchShardedAfter =
           lib.lookupFunction<_SearchShardedAfterC, _SearchShardedAfterD>('tsh_search_sharded_after');
+      _searchShardGrouped =
+          lib.lookupFunction<_SearchShardGroupedC, _SearchShardGroupedD>('tsh_search_shard_grouped');
+      _shardBeginGrouped =
+          lib.lookupFunction<_ShardBeginGroupedC, _ShardBeginGroupedD>('tsh_search_shard_begin_grouped');
+      _mergeGrouped = lib.lookupFunction<_MergeGroupedC, _MergeGroupedD>('tsh_merge_candidates_grouped');
+      _searchShardedGrouped =
+          lib.lookupFunction<_SearchShardedGroupedC, _SearchShardedGroupedD>('tsh_search_sharded_grouped');
       _searchShardMasked =
           lib.lookupFunction<_SearchShardMaskedC, _SearchShardMaskedD>('tsh_search_shard_masked');
       _shardBeginMasked =
@@ -1489,6 +1516,59 @@ final class HipVectorBackend {
         0;
   }
 
+  /// The same three for the plain grouped search (tsh_search_shard_grouped, tsh_search_shard_begin_grouped,
+  /// tsh_merge_candidates_grouped): every shard's block holds its group heads' candidates, the side rows and the
+  /// quarantined rows the mask keeps, and the merge -- the grouped finaliser over the union of all blocks -- gives
+  /// bit for bit what [searchGrouped] gives on one un-sharded index; groups may have rows on any number of ranks.
+  /// `groups`: made by [createGroups] on THIS backend from the same GLOBAL array every rank uses; `rowMask` / `mask`:
+  /// GLOBAL, at most one.  A disposed [HipRowGroups] or [HipRowMask] is refused (false / nullptr, with a warning).
+  /// [shardStreamProgress] / [shardStreamEnd] serve [shardStreamBeginGrouped] too; the handles must stay undisposed
+  /// until [shardStreamEnd].
+  bool searchShardGrouped(Pointer<Float> queries, int nq, int topK, Pointer<Uint8> rowMask, HipRowMask? mask,
+      HipRowGroups groups, int entries, Pointer<Void> deviceBlocks) {
+    if (groups._groups == nullptr) {
+      Logger.warn('searchShardGrouped with a disposed HipRowGroups', label: 'HipVectorBackend');
+      return false;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchShardGrouped with a disposed HipRowMask', label: 'HipVectorBackend');
+      return false;
+    }
+    return _searchShardGrouped(_handle, queries, nq, topK, rowMask, mask?._mask ?? nullptr, groups._groups, entries,
+            deviceBlocks, nullptr) ==
+        0;
+  }
+
+  Pointer<Void> shardStreamBeginGrouped(Pointer<Float> queries, int nq, int topK, Pointer<Uint8> rowMask,
+      HipRowMask? mask, HipRowGroups groups, int entries, Pointer<Void> deviceBlocks, int step) {
+    if (groups._groups == nullptr) {
+      Logger.warn('shardStreamBeginGrouped with a disposed HipRowGroups', label: 'HipVectorBackend');
+      return nullptr;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('shardStreamBeginGrouped with a disposed HipRowMask', label: 'HipVectorBackend');
+      return nullptr;
+    }
+    final out = calloc<Pointer<Void>>();
+    try {
+      final rc = _shardBeginGrouped(_handle, queries, nq, topK, rowMask, mask?._mask ?? nullptr, groups._groups,
+          entries, deviceBlocks, step, out);
+      return rc == 0 ? out.value : nullptr;
+    } finally {
+      calloc.free(out);
+    }
+  }
+
+  /// `groupOf` / `nGroupOf`: the GLOBAL array the ranks' [HipRowGroups] were made from; `outGroup` may be nullptr.
+  static bool mergeCandidatesGrouped(int metric, int dim, Pointer<Float> queries, int nq, int topK,
+      double? distanceThreshold, Pointer<Int32> groupOf, int nGroupOf, Pointer<Void> blocks, int nBlocks,
+      int entries, Pointer<Int64> outIds, Pointer<Double> outDist, Pointer<Int32> outGroup,
+      Pointer<Int32> outCount, Pointer<Int32> neededEntries) {
+    return _mergeGrouped(metric, dim, queries, nq, topK, distanceThreshold ?? double.nan, groupOf, nGroupOf,
+            blocks, nBlocks, entries, outIds, outDist, outGroup, outCount, neededEntries) ==
+        0;
+  }
+
   /// [searchShard] / [shardStreamBegin] with a device-resident WHERE row set in place of the bitmap pointer, and an
   /// optional GLOBAL cursor per query (tsh_search_shard_masked, tsh_search_shard_begin_masked): the library reads
   /// the mask's device words and list in place -- no per-call slice, count, list or copy of a bitmap on this rank.
@@ -1659,6 +1739,64 @@ final class HipShardComm {
         (afterDistances.length != queries.length || afterNodeIds!.length != queries.length)) return null;
     return _search(queries, topK, distanceThreshold, null, afterDistances, afterNodeIds,
         handle: mask, viaHandle: true);
+  }
+
+  /// [search] for the plain grouped search (tsh_search_sharded_grouped): the nearest row of each of the topK nearest
+  /// groups over ALL ranks' rows, identical on every rank and equal to what [HipVectorBackend.searchGrouped] gives on
+  /// one un-sharded index.  `groups`: made by [HipVectorBackend.createGroups] on this rank's shard from the same
+  /// GLOBAL array on every rank; groups may have rows on any number of ranks.  `rowMask` / `mask`: GLOBAL, at most
+  /// one.  A disposed handle is refused before the collective is entered (null, with a warning): every rank must
+  /// refuse alike.  A handle of another backend is this rank's own failure inside the collective: its peers get
+  /// TSH_E_PEER and the communicator stays usable.
+  List<List<HipGroupedResult>>? searchShardedGrouped(List<Float32List> queries, int topK, HipRowGroups groups,
+      {double? distanceThreshold, Uint8List? rowMask, HipRowMask? mask}) {
+    if (groups._groups == nullptr) {
+      Logger.warn('searchShardedGrouped with a disposed HipRowGroups', label: 'HipShardComm');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('searchShardedGrouped with a disposed HipRowMask', label: 'HipShardComm');
+      return null;
+    }
+    final nq = queries.length, d = shard.dimensions;
+    if (nq == 0 || topK <= 0) return [for (var i = 0; i < nq; i++) const []];
+    final q = calloc<Float>(nq * d);
+    final ids = calloc<Int64>(nq * topK);
+    final dist = calloc<Double>(nq * topK);
+    final grp = calloc<Int32>(nq * topK);
+    final cnt = calloc<Int32>(nq);
+    Pointer<Uint8> maskBytes = nullptr;
+    try {
+      final view = q.asTypedList(nq * d);
+      for (var i = 0; i < nq; i++) {
+        view.setRange(i * d, (i + 1) * d, queries[i]);
+      }
+      if (mask == null && rowMask != null) {
+        maskBytes = calloc<Uint8>(rowMask.length);
+        maskBytes.asTypedList(rowMask.length).setAll(0, rowMask);
+      }
+      final rc = HipVectorBackend._searchShardedGrouped(shard._handle, _comm, q, nq, topK,
+          distanceThreshold ?? double.nan, maskBytes, mask?._mask ?? nullptr, groups._groups, ids, dist, grp, cnt);
+      if (rc != 0) {
+        Logger.warn('tsh_search_sharded_grouped failed ($rc): ${HipVectorBackend._errorText()}',
+            label: 'HipShardComm');
+        return null;
+      }
+      return [
+        for (var i = 0; i < nq; i++)
+          [
+            for (var j = 0; j < cnt[i]; j++)
+              HipGroupedResult(ids[i * topK + j], dist[i * topK + j], grp[i * topK + j])
+          ]
+      ];
+    } finally {
+      calloc.free(q);
+      calloc.free(ids);
+      calloc.free(dist);
+      calloc.free(grp);
+      calloc.free(cnt);
+      if (maskBytes != nullptr) calloc.free(maskBytes);
+    }
   }
 
   List<List<NghSearchResult>>? _search(List<Float32List> queries, int topK, double? distanceThreshold,

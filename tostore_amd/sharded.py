@@ -55,6 +55,17 @@ def mask_forms(index, row_mask):
     return keep, mp, None
 
 
+def group_forms(index, groups, after=None):
+    """A grouped call's two inputs: (tsh_groups* of the caller's HipGroups, its GLOBAL group_of array for a host merge);
+    (None, None) without groups.  The handle must have been made on this rank's shard (HipVectorIndex.make_groups, from
+    the same GLOBAL array on every rank); the plain grouped search takes no cursor."""
+    if groups is None:
+        return None, None
+    if after is not None:
+        raise ValueError("a grouped sharded search takes no cursor")
+    return groups.handle(), groups.group_of
+
+
 def _cursor_ptrs(cur):
     """(after_dist, after_id) pointers of cursor_arrays' pair; (None, None) without a cursor"""
     if cur is None:
@@ -64,8 +75,11 @@ def _cursor_ptrs(cur):
 
 def merge_candidate_blocks(metric: int, dim: int, queries: np.ndarray, k: int,
                            distance_threshold: Optional[float], blocks: np.ndarray, n_blocks: int,
-                           entries: int, after=None):
+                           entries: int, after=None, group_of=None):
     """Host merge of `n_blocks` x nq candidate blocks (uint8 array, layout [block][query]).
+
+    `group_of`: the GLOBAL group array of a grouped search's blocks (tsh_merge_candidates_grouped: the nearest row of
+    each of the k nearest groups over all blocks); the answer is then (ids, dist, count, groups[nq,k]).  Not with `after`.
 
     `after`: a cursor -- one (distance, id), or one per query -- behind which the answer starts
     (tsh_merge_candidates_after); None = from the start (tsh_merge_candidates).
@@ -86,7 +100,18 @@ def merge_candidate_blocks(metric: int, dim: int, queries: np.ndarray, k: int,
     cnt = np.zeros(nq, dtype=np.int32)
     need = ctypes.c_int32(entries)
     thr = math.nan if distance_threshold is None else float(distance_threshold)
-    if after is None:
+    if group_of is not None:
+        if after is not None:
+            raise ValueError("a grouped merge takes no cursor")
+        g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
+        grp = np.full((nq, max(kk, 1)), -1, dtype=np.int32)
+        rc = _ffi.lib().tsh_merge_candidates_grouped(metric, dim, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr,
+                                                     g.ctypes.data_as(_ffi.p_i32), g.shape[0],
+                                                     blocks.ctypes.data_as(ctypes.c_void_p), n_blocks, entries,
+                                                     ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
+                                                     grp.ctypes.data_as(_ffi.p_i32), cnt.ctypes.data_as(_ffi.p_i32),
+                                                     ctypes.byref(need))
+    elif after is None:
         rc = _ffi.lib().tsh_merge_candidates(metric, dim, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr,
                                              blocks.ctypes.data_as(ctypes.c_void_p), n_blocks, entries,
                                              ids.ctypes.data_as(_ffi.p_i64), dist.ctypes.data_as(_ffi.p_f64),
@@ -102,6 +127,8 @@ def merge_candidate_blocks(metric: int, dim: int, queries: np.ndarray, k: int,
         err = _ffi.TshError(rc, _ffi.last_error())
         err.needed_entries = need.value
         raise err
+    if group_of is not None:
+        return ids[:, :kk], dist[:, :kk], cnt, grp[:, :kk]
     return ids[:, :kk], dist[:, :kk], cnt
 
 
@@ -136,12 +163,16 @@ class ShardedSearcher:
         _, mine, allb, host = cur
         return mine[: nq * bb], allb[: self.world * nq * bb], host[: self.world * nq * bb]
 
-    def _scan(self, q: np.ndarray, k: int, mp, entries: int, slot: int, cur=None, mh=None):
+    def _scan(self, q: np.ndarray, k: int, mp, entries: int, slot: int, cur=None, mh=None, gh=None):
         """This rank's shard: candidate blocks for the queries of one group, left in device memory.
         cur: the queries' cursor arrays (cursor_arrays), or None.  mh: a mask handle in place of the pointer mp
-        (tsh_search_shard_masked, with or without the cursor)."""
+        (tsh_search_shard_masked, with or without the cursor).  gh: a groups handle (tsh_search_shard_grouped, behind
+        either mask form)."""
         mine, _, _ = self._buffers(q.shape[0], entries, slot)
-        if mh is not None:
+        if gh is not None:
+            _ffi.check(_ffi.lib().tsh_search_shard_grouped(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k),
+                                                           mp, mh, gh, entries, ctypes.c_void_p(mine.data_ptr()), None))
+        elif mh is not None:
             ad, ai = _cursor_ptrs(cur)
             _ffi.check(_ffi.lib().tsh_search_shard_masked(self.index._h, q.ctypes.data_as(_ffi.p_f32), q.shape[0], int(k),
                                                           mh, ad, ai, entries, ctypes.c_void_p(mine.data_ptr()), None))
@@ -154,7 +185,7 @@ class ShardedSearcher:
                                                          cur[1].ctypes.data_as(_ffi.p_i64), entries,
                                                          ctypes.c_void_p(mine.data_ptr()), None))
 
-    def _exchange_merge(self, q: np.ndarray, k: int, thr, entries: int, slot: int, mine=None, after=None):
+    def _exchange_merge(self, q: np.ndarray, k: int, thr, entries: int, slot: int, mine=None, after=None, group_of=None):
         t = self._torch
         own, allb, host = self._buffers(q.shape[0], entries, slot)
         mine = own if mine is None else mine
@@ -163,7 +194,7 @@ class ShardedSearcher:
             mine_h = mine.cpu()
             self._dist.all_gather_into_tensor(host, mine_h, group=self.group)
             return merge_candidate_blocks(self.index.metric, self.index.dim, q, k, thr, host.numpy(),
-                                          self.world, entries, after)
+                                          self.world, entries, after, group_of)
         if self._dist.is_initialized():
             self._dist.all_gather_into_tensor(allb, mine, group=self.group)
         else:
@@ -171,15 +202,16 @@ class ShardedSearcher:
         host[: allb.numel()].copy_(allb, non_blocking=True)
         t.cuda.current_stream().synchronize()
         return merge_candidate_blocks(self.index.metric, self.index.dim, q, k, thr, host[: allb.numel()].numpy(),
-                                      self.world, entries, after)
+                                      self.world, entries, after, group_of)
 
     def search_many(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None,
-                    group: int = 8, after=None):
+                    group: int = 8, after=None, groups=None):
         """A stream of independent queries, exchanged in groups: this rank's scans of ALL the queries run as one
         pipeline on a library thread (tsh_search_shard_begin: the GPU sees no group boundaries), and the calling
         thread all-gathers and merges every group as soon as its blocks are final (collectives stay on one thread,
         in one order on every rank).  Same results as search().  `after`, `row_mask`: as in search() (a HipMask:
-        tsh_search_shard_begin_masked; it must stay open until this returns)."""
+        tsh_search_shard_begin_masked; it must stay open until this returns).  `groups`: as in search()
+        (tsh_search_shard_begin_grouped): the answer is (ids, dist, count, groups)."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -187,13 +219,15 @@ class ShardedSearcher:
         ids = np.full((nq, kk), -1, dtype=np.int64)
         dist = np.full((nq, kk), np.nan, dtype=np.float64)
         cnt = np.zeros(nq, dtype=np.int32)
+        grp = np.full((nq, kk), -1, dtype=np.int32)
+        gh, group_of = group_forms(self.index, groups, after)
         L = _ffi.lib()
         entries = L.tsh_default_block_entries(int(k))
         row_mask, mp, mh = mask_forms(self.index, row_mask)  # GLOBAL mask: one bit per row id below this shard's end
         group = max(1, int(group))
         spans = [(s, min(nq, s + group)) for s in range(0, nq, group)]
         if not spans:
-            return ids, dist, cnt
+            return (ids, dist, cnt) if gh is None else (ids, dist, cnt, grp)
         bb = L.tsh_candidate_block_bytes(entries)
         key = ("many", entries)
         cur = self._bufs.get(key)
@@ -204,7 +238,10 @@ class ShardedSearcher:
         mine_all = cur[1]
         st = ctypes.c_void_p()
         cursors = None if after is None else cursor_arrays(after, nq)
-        if mh is not None:
+        if gh is not None:
+            _ffi.check(L.tsh_search_shard_begin_grouped(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mp, mh, gh,
+                                                        entries, ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
+        elif mh is not None:
             ad, ai = _cursor_ptrs(cursors)
             _ffi.check(L.tsh_search_shard_begin_masked(self.index._h, q.ctypes.data_as(_ffi.p_f32), nq, int(k), mh, ad, ai,
                                                        entries, ctypes.c_void_p(mine_all.data_ptr()), group, ctypes.byref(st)))
@@ -221,24 +258,29 @@ class ShardedSearcher:
                 _ffi.check(L.tsh_search_shard_progress(st, hi, None))  # this group's blocks are final
                 try:
                     part = None if cursors is None else (cursors[0][lo:hi], cursors[1][lo:hi])
-                    i, d, c = self._exchange_merge(q[lo:hi], k, distance_threshold, entries, g % 2,
-                                                   mine_all[lo * bb: hi * bb], part)
+                    got = self._exchange_merge(q[lo:hi], k, distance_threshold, entries, g % 2,
+                                               mine_all[lo * bb: hi * bb], part, group_of)
                 except _ffi.TshError as e:
                     if e.code != _ffi.TSH_E_OVERFLOW:
                         raise
                     _ffi.check(L.tsh_search_shard_progress(st, nq, None))  # nothing overlaps a retry
-                    i, d, c = self.search(q[lo:hi], k, distance_threshold, row_mask, part)  # ties: bigger blocks
-                ids[lo:hi], dist[lo:hi], cnt[lo:hi] = i, d, c
+                    got = self.search(q[lo:hi], k, distance_threshold, row_mask, part, groups)  # ties: bigger blocks
+                ids[lo:hi], dist[lo:hi], cnt[lo:hi] = got[:3]
+                if gh is not None:
+                    grp[lo:hi] = got[3]
         finally:
             rc = L.tsh_search_shard_end(st)
         _ffi.check(rc)
-        return ids, dist, cnt
+        return (ids, dist, cnt) if gh is None else (ids, dist, cnt, grp)
 
-    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, after=None):
+    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, after=None, groups=None):
         """`after`: a GLOBAL cursor -- one (distance, id), or one per query; the same on every rank -- behind which
         the answer starts: the next k rows past it (tsh_search_shard_after + tsh_merge_candidates_after).  A page
         shorter than k is the last one.  `row_mask`: a GLOBAL keep bitmap, or a HipMask made for this rank's shard
-        from it (tsh_search_shard_masked, on the first scan and on an overflow retry alike)."""
+        from it (tsh_search_shard_masked, on the first scan and on an overflow retry alike).  `groups`: a HipGroups made
+        on this rank's shard from the GLOBAL group array, the same on every rank -- the nearest row of each of the k
+        nearest groups over all ranks' rows (tsh_search_shard_grouped + tsh_merge_candidates_grouped; no cursor): the
+        answer is (ids, dist, count, groups)."""
         t = self._torch
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
@@ -248,10 +290,11 @@ class ShardedSearcher:
         entries = L.tsh_default_block_entries(int(k))
         row_mask, mp, mh = mask_forms(self.index, row_mask)  # GLOBAL mask: one bit per row id below this shard's end
         cur = None if after is None else cursor_arrays(after, nq)
+        gh, group_of = group_forms(self.index, groups, after)
         for _attempt in range(3):
-            self._scan(q, k, mp, entries, 0, cur, mh)
+            self._scan(q, k, mp, entries, 0, cur, mh, gh)
             try:
-                return self._exchange_merge(q, k, distance_threshold, entries, 0, None, after)
+                return self._exchange_merge(q, k, distance_threshold, entries, 0, None, after, group_of)
             except _ffi.TshError as e:
                 if e.code != _ffi.TSH_E_OVERFLOW:
                     raise
@@ -344,11 +387,15 @@ class CommSearcher:
     def __exit__(self, *exc):
         self.close()
 
-    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, shard=..., after=None):
+    def search(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, shard=..., after=None,
+               groups=None, groups_handle=...):
         """Collective.  `shard=None` (tests) passes a NULL handle: this rank fails locally and stays in the
         collective.  `after`: a GLOBAL cursor -- one (distance, id), or one per query; the same on every rank --
         behind which the answer starts (tsh_search_sharded_after).  `row_mask`: a GLOBAL keep bitmap, or a HipMask made
-        for this rank's shard from it (tsh_search_sharded_masked, with or without `after`)."""
+        for this rank's shard from it (tsh_search_sharded_masked, with or without `after`).  `groups`: a HipGroups made on
+        this rank's shard from the GLOBAL group array, the same on every rank (tsh_search_sharded_grouped; no cursor): the
+        answer is (ids, dist, count, groups).  `groups_handle` (tests) passes that pointer in the handle's place: a bad
+        one is this rank's own failure inside the collective."""
         q = np.ascontiguousarray(queries, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -359,6 +406,16 @@ class CommSearcher:
         thr = math.nan if distance_threshold is None else float(distance_threshold)
         row_mask, mp, mh = mask_forms(self.index, row_mask)
         h = self.index._h if shard is ... else shard
+        if groups is not None or groups_handle is not ...:
+            if after is not None:
+                raise ValueError("a grouped sharded search takes no cursor")
+            gh = groups.handle() if groups_handle is ... else groups_handle
+            grp = np.full((nq, max(kk, 1)), -1, dtype=np.int32)
+            _ffi.check(_ffi.lib().tsh_search_sharded_grouped(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mp, mh,
+                                                             gh, ids.ctypes.data_as(_ffi.p_i64),
+                                                             dist.ctypes.data_as(_ffi.p_f64), grp.ctypes.data_as(_ffi.p_i32),
+                                                             cnt.ctypes.data_as(_ffi.p_i32)))
+            return ids[:, :kk], dist[:, :kk], cnt, grp[:, :kk]
         if mh is not None:
             ad, ai = _cursor_ptrs(None if after is None else cursor_arrays(after, nq))
             _ffi.check(_ffi.lib().tsh_search_sharded_masked(h, self._c, q.ctypes.data_as(_ffi.p_f32), nq, int(k), thr, mh,
@@ -377,13 +434,13 @@ class CommSearcher:
         return ids[:, :kk], dist[:, :kk], cnt
 
     def search_many(self, queries, k: int, distance_threshold: Optional[float] = None, row_mask=None, group: int = 0,
-                    after=None):
+                    after=None, groups=None):
         """One collective call; the library forms the groups itself (same signature as
         ShardedSearcher.search_many; `group` > 0 overrides the library's choice)."""
         if group:
             self.set_group(group)
         try:
-            return self.search(queries, k, distance_threshold, row_mask, after=after)
+            return self.search(queries, k, distance_threshold, row_mask, after=after, groups=groups)
         finally:
             if group:
                 self.set_group(0)
