@@ -8,7 +8,7 @@
 //                           (tsh_after_band.h, where the proof is).  key < floor_lo: BEFORE the cursor for certain, the key
 //                           becomes KEY_DEAD.  key > floor_hi: AFTER it for certain, untouched.  In between, AMBIGUOUS:
 //                           KEY_DEAD as well, and the row's id goes to the context's side list (an atomic count; ids
-//                           past the list's capacity are counted, not written, as mask_compact_kernel does).  gmin[t]
+//                           past the list's capacity are counted, not written, as i8_list_kernel does).  gmin[t]
 //                           becomes the minimum over the tile's AFTER rows.  A tile whose gmin is KEY_DEAD already is
 //                           skipped unread: its keys are stale by contract.
 //   (select_kernel, rerank_kernel and on overflow the wide-band pass then see the AFTER rows only, with every guarantee

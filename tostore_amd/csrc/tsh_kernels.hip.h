@@ -189,6 +189,7 @@ struct RowsF32 {  // 16-byte loads, 1 KiB per wave instruction
   typedef float elem;
   typedef f32x4 chunk;
   static constexpr int SUM = METRIC;
+  static constexpr bool LOWER_MIN = false;
   static __device__ __forceinline__ const elem *rows(const float *rows, const void *) { return rows; }
   static __device__ __forceinline__ chunk load(const elem *p) { return ld16<NT>(p); }
   static __device__ __forceinline__ f32x4 widen(chunk x) { return x; }
@@ -198,6 +199,7 @@ struct RowsF16 {  // the fp16 copy: 8-byte loads, 512 B per wave instruction
   typedef _Float16 elem;
   typedef f16x4 chunk;
   static constexpr int SUM = METRIC_IP;
+  static constexpr bool LOWER_MIN = false;
   static __device__ __forceinline__ const elem *rows(const float *, const void *rows16) { return reinterpret_cast<const elem *>(rows16); }
   static __device__ __forceinline__ chunk load(const elem *p) { return __builtin_nontemporal_load(reinterpret_cast<const chunk *>(p)); }
   static __device__ __forceinline__ f32x4 widen(chunk x) { return __builtin_convertvector(x, f32x4); }
@@ -206,6 +208,7 @@ struct RowsI8 {  // the int8 copy, biased bytes: 4-byte loads, 256 B per wave in
   typedef uint8_t elem;
   typedef uint32_t chunk;
   static constexpr int SUM = METRIC_IP;
+  static constexpr bool LOWER_MIN = true;
   static __device__ __forceinline__ const elem *rows(const float *, const void *rows8) { return reinterpret_cast<const elem *>(rows8); }
   static __device__ __forceinline__ chunk load(const elem *p) { return __builtin_nontemporal_load(reinterpret_cast<const chunk *>(p)); }
   static __device__ __forceinline__ f32x4 widen(chunk x) {
@@ -317,10 +320,12 @@ static __global__ void __launch_bounds__(256) scan_f16_w_kernel(const float *sqn
 // and the band |key - exact| <= w_i of tsh_scan_i8_band.h.  keys[row] = the LOWER side key - w_i; gmin[tile] = the minimum
 // of the UPPER sides key + w_i: k distinct tiles hold a row whose exact key is at or below tau = the k-th smallest
 // gmin, so every row of the top k has a lower side <= tau, and the threshold step needs no band arithmetic.
+// gmin[n_tiles + tile] = the minimum of the LOWER sides (RowsI8::LOWER_MIN; the allocation holds both): a tile whose
+// lower minimum is above tau holds no survivor, so the list step (i8_list_kernel) reads the keys of a few hundred tiles only.
 // MASKED (tombstones, gaps, quarantined rows, a caller's dense mask): R = 4, two groups per batch -- a masked tile's batch
 // count may be odd, which the one-group-per-batch pipeline does not take -- so a wave has half the dense kernel's bytes in
-// flight.  Dead lanes store KEY_DEAD and add KEY_DEAD to the tile's minimum, a dead tile stores only gmin = KEY_DEAD (its
-// keys[] stay stale: i8_survivor_kernel drops the tile by its gmin).  scale8, |row|^2 and 1/|row| are read for live rows
+// flight.  Dead lanes store KEY_DEAD and add KEY_DEAD to the tile's minima, a dead tile stores only its two minima = KEY_DEAD
+// (its keys[] stay stale: i8_list_kernel never takes it for a candidate).  scale8, |row|^2 and 1/|row| are read for live rows
 // only: an absent row's scale was never written, a quarantined row's norm is not finite.
 template <int NCH, int METRIC, bool FULL, bool MASKED, int R, int WAVES, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) scan_i8_kernel(ScanArgsQ aq) {
@@ -343,9 +348,13 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) scan_i8_kernel(ScanArgsQ aq)
       x = METRIC == METRIC_L2 ? __builtin_fmaf(-2.f, dot, sq) : -dot;
       w = __builtin_fmaf(a.w_s, sc, __builtin_fmaf(a.w_alpha, __builtin_sqrtf(sq), a.w_beta));
     }
-    a.keys[row] = alive ? f2key(x - w) : KEY_DEAD;
-    const uint32_t m = wave_min_u32(alive ? f2key(x + w) : KEY_DEAD);
-    if (lane == 0) a.gmin[t] = m;
+    const uint32_t lower = alive ? f2key(x - w) : KEY_DEAD;
+    a.keys[row] = lower;
+    const uint32_t m = wave_min_u32(alive ? f2key(x + w) : KEY_DEAD), m_lo = wave_min_u32(lower);
+    if (lane == 0) {
+      a.gmin[t] = m;
+      a.gmin[a.n_tiles + t] = m_lo;
+    }
   }
 }
 

@@ -140,10 +140,8 @@ struct Ctx {
   double *d_xsum = nullptr;
   uint64_t *d_xpick = nullptr;  // exact_pick_kernel: [0] its counter (zero between searches), [1 ..] E1's wave minima
   int64_t x_cap = 0;
-  // the coarse int8 scan's tail (tsh_scan_i8.hip.h): [tau, survivor total | M1's counts | the survivors' ballot words] and
-  // the survivor list of I8_LIST_CAP ids
+  // the coarse int8 scan's tail (tsh_scan_i8.hip.h): [tau, survivor total] and the survivor list of I8_LIST_CAP ids
   uint32_t *d_i8 = nullptr, *d_i8_list = nullptr;
-  int64_t i8_tiles = 0;
   // cursor searches (tsh_after.hip.h): the side list of the rows the floor pass could not decide, its two count words
   // (side_flip: the one the next cursor job counts in -- the job before it left it at zero) and, pinned + mapped, their
   // count and entries: [0].id = count, [1 ..] the entries.  Count jobs (tsh_count.hip.h) use the same list and words, and a
@@ -755,8 +753,9 @@ int ctx_prepare(Shard *s, Ctx *c, int32_t entries, bool need_mask) {
     c->d_keys = nullptr;
     c->d_gmin = nullptr;
     HIPCHK(hipMalloc(&c->d_keys, (size_t)tiles * 64 * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_gmin, (size_t)tiles * sizeof(uint32_t)));
-    c->bytes += (tiles - c->tiles_cap) * 65 * 4;
+    // (two minima per tile: the coarse int8 scan leaves its tiles' minima of lower sides behind the n_tiles upper ones)
+    HIPCHK(hipMalloc(&c->d_gmin, (size_t)tiles * 2 * sizeof(uint32_t)));
+    c->bytes += (tiles - c->tiles_cap) * 66 * 4;
     c->tiles_cap = tiles;
   }
   if (need_mask && tiles > c->mask_words) {
@@ -1399,27 +1398,17 @@ void fill_scan_i8_args(const Shard *s, const ScanI8Band &ib, ScanArgsQ *aq) {
   aq->a.w_beta = ib.beta;
 }
 
-// the device buffers of the int8 scan's tail, for a shard of n_tiles tiles
-int ctx_reserve_i8(Ctx *c, int64_t n_tiles) {
+// the device buffers of the int8 scan's tail: the same for every shard size
+int ctx_reserve_i8(Ctx *c) {
+  if (!c->d_i8) {
+    HIPCHK(hipMalloc(&c->d_i8, 16));  // [0] tau, [1] the survivors' total
+    c->bytes += 16;
+  }
   if (!c->d_i8_list) {
     HIPCHK(hipMalloc(&c->d_i8_list, (size_t)I8_LIST_CAP * sizeof(uint32_t)));
     c->bytes += I8_LIST_CAP * 4;
   }
-  if (n_tiles <= c->i8_tiles) return TSH_OK;
-  hipFree(c->d_i8);
-  c->d_i8 = nullptr;
-  c->bytes -= c->i8_tiles * 9 + 16;
-  c->i8_tiles = 0;
-  const int64_t want = round_up(n_tiles + n_tiles / 2, MASK_BLOCK_WORDS);
-  // [0] tau, [1] the survivors' total, [4 ..) M1's counts (one per MASK_BLOCK_WORDS tiles), then the ballot words
-  HIPCHK(hipMalloc(&c->d_i8, (size_t)(16 + round_up(want / MASK_BLOCK_WORDS * 4, 16) + want * 8)));
-  c->i8_tiles = want;
-  c->bytes += want * 9 + 16;
   return TSH_OK;
-}
-inline uint32_t *i8_bsum(const Ctx *c) { return c->d_i8 + 4; }
-inline uint64_t *i8_words(const Ctx *c) {
-  return reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(c->d_i8) + 16 + round_up(c->i8_tiles / MASK_BLOCK_WORDS * 4, 16));
 }
 
 // the fp16 scan's arguments on top of the f32 scan's (fill_scan_args) and the select's
@@ -1742,15 +1731,10 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
   const hipEvent_t none = nullptr, done = quar ? none : c->ev_done;
   const bool i8 = j->store == RowStore::I8;
   if (i8) {
-    // threshold, survivors' ballot words, their count and ascending list (capped and padded by M2), E1 over the list
-    const int32_t n_tiles = ka.sa.a.n_tiles, n_blocks = (n_tiles + MASK_BLOCK_WORDS - 1) / MASK_BLOCK_WORDS;
-    if (n_tiles <= SEL_VPT * SEL_THREADS) i8_tau_kernel<true><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
-    else i8_tau_kernel<false><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, n_tiles, j->k, c->d_i8);
-    i8_survivor_kernel<<<(unsigned)((n_tiles + 4 * I8_SURV_TILES - 1) / (4 * I8_SURV_TILES)), 256, 0, ts>>>(c->d_keys, j->masked ? c->d_gmin : nullptr, c->d_i8, n_tiles,
-                                                                                                            i8_words(c));
-    mask_block_count_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, ts>>>(i8_words(c), n_tiles, i8_bsum(c));
-    mask_compact_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, ts>>>(i8_words(c), n_tiles, i8_bsum(c), c->d_i8_list, c->d_i8 + 1,
-                                                              (uint32_t)I8_LIST_CAP, (uint32_t)I8_LIST_CAP);
+    // threshold, candidate tiles, the survivors' ascending list (capped and padded) and their total; E1 over the list
+    const int32_t n_tiles = ka.sa.a.n_tiles;
+    if (n_tiles <= SEL_VPT * SEL_THREADS) i8_list_kernel<true><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, c->d_keys, n_tiles, j->k, c->d_i8_list, c->d_i8);
+    else i8_list_kernel<false><<<1, SEL_THREADS, 0, ts>>>(c->d_gmin, c->d_keys, n_tiles, j->k, c->d_i8_list, c->d_i8);
     launch_exact_scan(ka.xa, s->metric, ts, LaunchEv());
   }
   if (j->route.picked) {  // E2': one workgroup per 256 entries, a bound from E1's wave minima, no ranking below it
@@ -2019,7 +2003,7 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   j->store = RowStore::F32;
   if (r.i8_eligible && !s->rows8.route.take_denial() && r.ib.ok && rows8_ensure(s, s->scan_stream)) {
     j->store = RowStore::I8;
-    if ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c, (s->rows + 63) / 64))) return rc;
+    if ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c))) return rc;
   } else {
     if (!r.exact) j->route.picked = false;
     if (r.f16_eligible && !s->rows16.route.take_denial() && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp)) j->store = RowStore::F16;
@@ -2437,6 +2421,11 @@ struct SearchOut {
   // (`where`: the stream that event was recorded on -- kernels of one stream finish in order; `seq`: the job's place
   // in the order the device's streams were fed, which with two submitting threads is not the queries' order)
   std::function<void(int32_t q, hipEvent_t done, hipStream_t where, uint64_t seq)> on_enqueued;
+  // single-query pipeline, host mode, ONE submitting thread (shard_search_blocks: scans long enough that the thread has
+  // time to spare between two of them): called right after query q's job finished, with the context's own pinned block
+  // and the query's spill and extra lists -- the caller finalises q while the GPU scans the next queries.  The block is
+  // then NOT copied to h_blocks.  Calls that two threads submit do not use it: their blocks land in h_blocks as ever
+  std::function<void(int32_t q, const uint8_t *block, const std::vector<BlockEntry> *spill, const std::vector<BlockEntry> *extra)> on_block;
   uint32_t tag = 0;  // generation stamped into the blocks' headers (BlockHeader.pad[1])
   bool leave_overflow = false;  // device mode: see Job::leave_overflow
   // single-query pipeline, host or device mode: a cursor per query (tsh_search_after, tsh_search_shard_after), or none
@@ -2460,7 +2449,8 @@ struct SearchOut {
 // `depth` of them in flight on separate contexts so one query's select / rerank / copies hide
 // behind the next query's scan.
 int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, int32_t k, const ShardMask &mask,
-                       int32_t entries, SearchOut *out, int depth, int32_t stride = 1) {
+                       int32_t entries, SearchOut *out, int depth, int32_t stride = 1, bool sole = false) {
+  // (sole: this thread submits the whole call -- out->on_block, if set, takes the blocks)
   // this thread's queries: q0, q0 + stride, ... below q1 (cnt of them; i-th = q0 + i * stride)
   const size_t bb = (size_t)tsh_candidate_block_bytes(entries);
   const int32_t cnt = q1 > q0 ? (q1 - q0 + stride - 1) / stride : 0;
@@ -2512,7 +2502,8 @@ int shard_search_slice(Shard *s, const float *queries, int32_t q0, int32_t q1, i
       release_all();
       return rc;
     }
-    if (out->h_blocks) memcpy(out->h_blocks + (size_t)q * bb, j.c->h_block, bb);
+    if (sole && out->on_block) out->on_block(q, j.c->h_block, sp, ex);
+    else if (out->h_blocks) memcpy(out->h_blocks + (size_t)q * bb, j.c->h_block, bb);
     if (out->count_out && out->group_after) {
       out->count_out[q] = j.certain;
     } else if (out->count_out) {  // the rows counted on the device, and whatever reached the host with its exact sums
@@ -2546,7 +2537,9 @@ int shard_search_blocks(Shard *s, const float *queries, int32_t nq, int32_t k, c
   static const int forced_threads = probe_env("TSH_SUBMIT_THREADS") ? atoi(probe_env("TSH_SUBMIT_THREADS")) : 0;
   const int want = forced_threads > 0 ? forced_threads : (scan_bytes <= (160ll << 20) ? 2 : SUBMIT_THREADS);
   const int T = std::min(want, nq / 8);
-  if (T <= 1) return shard_search_slice(s, queries, 0, nq, k, m, entries, out, depth);
+  // (on_block only where one thread is the rule, not where a short call happens to get one: a thread that is the
+  // bottleneck -- short scans -- has no time to finalise in)
+  if (T <= 1) return shard_search_slice(s, queries, 0, nq, k, m, entries, out, depth, 1, /*sole*/ want <= 1);
   std::vector<int> rcs((size_t)T, TSH_OK);
   std::vector<std::string> errs((size_t)T);
   const int per_depth = std::max(2, depth / T);
@@ -3283,6 +3276,15 @@ static int32_t search_impl(tsh_index *idx, const float *queries, int32_t nq, int
         });
       };
     }
+    if (ns == 1)  // single-query pipeline, one submitting thread: query q is ordered and cut while the GPU scans q + 1 ...
+      so.on_block = [&](int32_t q, const uint8_t *block, const std::vector<BlockEntry> *sp, const std::vector<BlockEntry> *ex) {
+        EntryList two[2];
+        const size_t n_lists = shard_lists(block, sp, ex, two);
+        Cursor cur;
+        out_count[q] = finalize_query(idx->metric, idx->dim, queries + (size_t)q * idx->dim, k, thr, two, n_lists,
+                                      out_ids + (size_t)q * k, out_dist + (size_t)q * k, nullptr, after.at(q, &cur));
+        finalized[(size_t)q] = 1;
+      };
     MaskSrc ms;
     int mrc = call_mask_for_shard(mask, g, s, &ms);
     if (mrc) return mrc;

@@ -11,8 +11,7 @@
 //                                thread adds a few of them: 62 blocks at 1 M rows), a thread's = that + the exclusive
 //                                prefix of the popcounts in front of it (wave scan by DPP shuffles + the four wave
 //                                totals through LDS); it then writes its word's set bits as row ids, ascending.
-// The list's padding to whole 64-entry tiles (0xFFFFFFFF) is a memset behind M2 -- or M2's own last workgroup's (pad_to:
-// the coarse int8 scan's survivor list, tsh_scan_i8.hip.h, of a fixed capacity that M2 then does not write past).  No reference counterpart: the
+// The list's padding to whole 64-entry tiles (0xFFFFFFFF) is a memset behind M2.  No reference counterpart: the
 // reference's vectorSearch takes no filter; the row sets this serves are the ones that live across
 // queries there -- tombstones (/root/reference/lib/src/core/ngh_page.dart:105-108) and a WHERE's primary keys mapped
 // through the pk -> nodeId tree (/root/reference/lib/src/core/vector_index_manager.dart:1223-1378).
@@ -54,9 +53,8 @@ static __global__ void __launch_bounds__(MASK_BLOCK_WORDS) mask_compact_kernel(c
                                                                                int32_t n_words,
                                                                                const uint32_t *__restrict__ bsum,
                                                                                uint32_t *__restrict__ list,
-                                                                               uint32_t *__restrict__ total,
-                                                                               uint32_t cap = 0xFFFFFFFFu, uint32_t pad_to = 0u) {
-  __shared__ uint32_t s_red[MASK_BLOCK_WORDS / 64], s_tot[MASK_BLOCK_WORDS / 64], s_end;
+                                                                               uint32_t *__restrict__ total) {
+  __shared__ uint32_t s_red[MASK_BLOCK_WORDS / 64], s_tot[MASK_BLOCK_WORDS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // where this workgroup's rows start in the list
   uint32_t part = 0;
@@ -82,16 +80,9 @@ static __global__ void __launch_bounds__(MASK_BLOCK_WORDS) mask_compact_kernel(c
   }
   o += incl - c;
   const uint32_t base = (uint32_t)w * 64u;
-  // (cap: the list's capacity -- ids past it are counted, not written; the callers that size the list by the mask's
-  // popcount pass none)
-  for (; word; word &= word - 1, ++o)
-    if (o < cap) list[o] = base + (uint32_t)__builtin_ctzll(word);
+  // (the callers size the list by the mask's popcount)
+  for (; word; word &= word - 1, ++o) list[o] = base + (uint32_t)__builtin_ctzll(word);
   if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == MASK_BLOCK_WORDS - 1) *total = o;  // (the last thread's end)
-  if (pad_to && blockIdx.x == gridDim.x - 1) {  // workgroup-uniform: the list's tail [total, pad_to) = 0xFFFFFFFF
-    if (threadIdx.x == MASK_BLOCK_WORDS - 1) s_end = o;
-    __syncthreads();
-    for (uint32_t i = s_end + threadIdx.x; i < pad_to; i += MASK_BLOCK_WORDS) list[i] = 0xFFFFFFFFu;
-  }
 }
 
 }  // namespace tsh

@@ -79,7 +79,10 @@
       bits = ((uint64_t)hi << 32) | lo;
       cnt = __popcll(bits);
       if (cnt == 0) {
-        if (lane == 0) a.gmin[t] = KEY_DEAD;  // keys[] of a dead tile stay stale: every reader checks gmin first
+        if (lane == 0) {
+          a.gmin[t] = KEY_DEAD;  // keys[] of a dead tile stay stale: every reader checks gmin first
+          if constexpr (Store::LOWER_MIN) a.gmin[a.n_tiles + t] = KEY_DEAD;  // (the coarse scan's second minimum)
+        }
         continue;
       }
     }
