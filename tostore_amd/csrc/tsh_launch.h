@@ -6,6 +6,7 @@
 #include "tsh_batch.hip.h"
 #include "tsh_kernels.hip.h"
 #include "tsh_scan_overlap.h"  // SMALL_SHARD_TILES, RowStore, the dense scans' launch shape
+#include "tsh_scan_widths.h"   // pick_nch, scan_f16_supported, scan_i8_supported: row width -> instantiation
 
 namespace tsh {
 
@@ -31,16 +32,14 @@ bool scan_list_supported(int nch, int64_t ld);
 void launch_scan_list(const ScanArgsQ &a, int nch, int metric, hipStream_t s, const LaunchEv &ev = LaunchEv());
 
 // K1 over the fp16 copy of the rows (a.a.rows16 and the band fields of ScanArgs set): tile scans, dense or masked, of
-// rows of at least 256 elements, a multiple of 8 (scan_f16_supported).  masked / mostly_live: launch_scan's.
-// tsh_scan_tu.hip
-bool scan_f16_supported(int nch, int dim);
+// rows of at least 256 elements, a multiple of 8 (scan_f16_supported, tsh_scan_widths.h).  masked / mostly_live:
+// launch_scan's.  tsh_scan_tu.hip
 void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev = LaunchEv(),
                      bool mostly_live = false);
 
 // K1 over the int8 copy of the rows (a.a.rows16 = the copy, a.a.scale8 and the band fields of ScanArgs set): tile
-// scans, dense or masked, of rows of up to eight chunks (scan_i8_supported).  masked / mostly_live: launch_scan's.
-// tsh_scan_tu.hip
-bool scan_i8_supported(int nch);
+// scans, dense or masked, of rows of up to eight chunks (scan_i8_supported, tsh_scan_widths.h).  masked / mostly_live:
+// launch_scan's.  tsh_scan_tu.hip
 void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev = LaunchEv(),
                     bool mostly_live = false);
 

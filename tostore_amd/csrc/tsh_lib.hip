@@ -95,13 +95,7 @@ constexpr int MAX_DIM_SCAN = 4096;    // register-resident query (NCH <= 16; the
 // (the finaliser -- Hit, Cursor, Cursors, sort_hits, finalize_query, count_entries -- is in tsh_finalize.h: host only, CPU-tested)
 
 // ---- kernel dispatch ---------------------------------------------------------
-inline int pick_nch(int d4) {
-  int need = (d4 + 63) / 64;
-  static const int opts[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16};
-  for (int o : opts)
-    if (o >= need) return o;
-  return -1;
-}
+// (pick_nch -- row width -> the chunk count of its scan instantiation -- is in tsh_scan_widths.h: host only, CPU-tested)
 
 // the scan kernels' launchers live in their own translation unit (tsh_scan_tu.hip): 144 instantiations that
 // compile beside this file instead of in front of it

@@ -51,6 +51,7 @@ struct ScanF32 {
   template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::F32, NCH)>;
   static constexpr bool HAS_MASKED = true;
   static constexpr int MAX_NCH = 16;
+  static_assert(MAX_NCH == SCAN_F32_MAX_NCH, "tsh_scan_widths.h names this family's widest row");
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
     using T = Tune<NCH, MASKED>;
     return &scan_kernel<NCH, METRIC, FULL, MASKED, T::R, true, 4, T::MINW>;
@@ -68,6 +69,7 @@ struct ScanF16 {
   template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::F16, NCH)>;
   static constexpr bool HAS_MASKED = true;
   static constexpr int MAX_NCH = 14;  // (wider rows that end inside a chunk would spill: they stay on f32)
+  static_assert(MAX_NCH == SCAN_F16_MAX_NCH, "tsh_scan_widths.h names this family's widest row");
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
     using T = Tune<NCH, MASKED>;
     return &scan_f16_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>;
@@ -86,6 +88,7 @@ struct ScanI8 {
   template <int NCH> using Shape = ScanShape<row_store_shape_chunks(RowStore::I8, NCH)>;
   static constexpr bool HAS_MASKED = true;
   static constexpr int MAX_NCH = 8;
+  static_assert(MAX_NCH == SCAN_I8_MAX_NCH, "tsh_scan_widths.h names this family's widest row");
   template <int NCH, int METRIC, bool FULL, bool MASKED> static constexpr auto kernel() {
     using T = Tune<NCH, MASKED>;
     return &scan_i8_kernel<NCH, METRIC, FULL, MASKED, T::R, 4, T::MINW>;
@@ -168,14 +171,11 @@ void launch_scan_list_n(const ScanArgsQ &a, int metric, hipStream_t s, const Lau
 
 }  // namespace
 
-bool scan_f16_supported(int nch, int dim) { return dim >= 256 && dim % 8 == 0 && nch >= 1 && nch <= ScanF16::MAX_NCH; }
-
+// (scan_f16_supported, scan_i8_supported: tsh_scan_widths.h)
 void launch_scan_f16(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev, bool ml) {
   if (a.a.n_tiles <= 0) return;
   launch_tile_scan<ScanF16>(a, nch, metric, masked, std::max(1, (a.a.n_tiles + 3) / 4), s, ev, ml);
 }
-
-bool scan_i8_supported(int nch) { return nch >= 1 && nch <= ScanI8::MAX_NCH; }
 
 void launch_scan_i8(const ScanArgsQ &a, int nch, int metric, bool masked, hipStream_t s, const LaunchEv &ev, bool ml) {
   if (a.a.n_tiles <= 0) return;
