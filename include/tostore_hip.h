@@ -931,7 +931,7 @@ int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
  * identical whichever runs):
  *   0  f32 MFMA on the rows as stored;
  *   1  bf16x3: each f32 operand split into bf16 hi + lo, three bf16 MFMAs per
- *      product (error 3.1 * 2^-18 |q||v| on top of the f32 accumulation bound);
+ *      product (error 2^-15 |q||v| on top of the f32 accumulation bound);
  *      costs a second copy of the rows, 4 B per element;
  *   2  f16: operands rounded to fp16 after an exact power-of-two scaling (cosine
  *      rows normalised first), one f16 MFMA per product (error 2^-10 |q||v|);

@@ -37,8 +37,8 @@ assertion is soundness (ratio <= 1), the file is the record of tightness.
 
 Out of scope here: the big-shard launch shapes (6144 tiles and more: several waves per workgroup, more than one tile
 per wave) -- they need 400 MB indexes and are covered at d = 256 by the test_big_shard_launch_shape(s) tests; every
-shard here runs one-wave workgroups, one tile per wave.  scan_list_kernel (test_selective_masks_every_width) and the
-batched path are not touched either."""
+shard here runs one-wave workgroups, one tile per wave.  scan_list_kernel is test_selective_masks_every_width's; the
+batched path's key kernels have a sweep of their own, tests/test_gpu_batch_shapes.py."""
 import ctypes
 import json
 import os

@@ -20,6 +20,7 @@
 
 #include <type_traits>
 
+#include "tsh_batch_tiles.h"
 #include "tsh_kernels.hip.h"
 
 namespace tsh {
@@ -75,26 +76,14 @@ struct BatchArgs {
 // an upper bound of |v| from the stored |v|^2 (f32 from an f64 sum: 2^-24; the square root: one ulp)
 __device__ __forceinline__ float batch_norm_up(float sq) { return __builtin_sqrtf(sq) * 1.000001f; }
 
-// XCD-aware tile order: workgroup b runs on XCD b % 8; give each XCD runs of
-// q_tiles consecutive workgroups that share one row tile (L2 reuse of V)
 // Per-query candidate counters sit one per 128-byte line: every survivor of the filtered pass is one returning
 // atomic on its query's counter, and packed counters (a small batch: all of them in a few lines, i.e. a few L2
 // channels) serialise there.
 constexpr int CC_STRIDE = 32;  // uint32 units (4 KiB apart measured the same)
 
+// the XCD-aware tile order of tsh_batch_tiles.h for a launch's own tile counts
 __device__ __forceinline__ void batch_tile_of(const BatchArgs &a, int b, int *q_tile, int *n_tile) {
-  const int total = a.q_tiles * a.n_tiles;
-  const int xcd = b & 7, i = b >> 3;
-  const int per_round = 8 * a.q_tiles;
-  const int full_rounds = total / per_round;
-  if (b < full_rounds * per_round) {
-    *q_tile = i % a.q_tiles;
-    *n_tile = (i / a.q_tiles) * 8 + xcd;
-  } else {  // ragged tail: plain order
-    int r = b - full_rounds * per_round;
-    *n_tile = full_rounds * 8 + r / a.q_tiles;
-    *q_tile = r % a.q_tiles;
-  }
+  batch_tile_of(a.q_tiles, a.n_tiles, b, q_tile, n_tile);
 }
 
 // Epilogue shared by the f32 and the bf16x3 kernels: key transform (+ filter) of a wave's
@@ -270,12 +259,14 @@ __global__ void __launch_bounds__(BT_THREADS, BK == 32 ? 2 : 3) batch_score_kern
 }
 
 // ---------------------------------------------------------------------------
-// bf16x3 variant.  x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi), |r| <= 2^-18 |x|:
+// bf16x3 variant.  x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi): bf16 keeps 8 significant bits, so
+// |lo| <= 2^-8 |x| and |r| <= 2^-17 |x| (the residual lies below 2^-8 of x's binade, its own rounding 2^-9 below that):
 //   q.x ~= qh.xh + qh.xl + ql.xh      (three bf16 MFMAs; products exact in f32)
-// misses ql.xl + q.r_x + r_q.x <= 3.1 * 2^-18 |q||x| per element, which is an eighth of the
-// f32 accumulation bound the band already carries -- the keys are a
-// pre-filter, the f64 rerank decides.  v_mfma_f32_32x32x16_bf16 runs 16x the rate of the f32
-// MFMA, so three of them per k are 5.3x faster than the f32 kernel at the same tile shape.
+// misses ql.xl + q.r_x + r_q.(xh + xl) <= (2^-16 + 2^-17 + 2^-17 (1 + 2^-17)) |q||x| = 2^-15 (1 + 2^-19) |q||x| per
+// element (reached within 2 %: operands just above a power of two), a ninth of the f32 accumulation bound the band
+// carries at 768 elements -- the keys are a pre-filter, the f64 rerank decides.
+// v_mfma_f32_32x32x16_bf16 runs 16x the rate of the f32 MFMA, so three of them per k are 5.3x faster than the f32
+// kernel at the same tile shape.
 //
 // Operand layout ("split planes"): per row, per chunk of 32 k-values, 128 bytes:
 //   [ hi(k0..k0+31) : 64 B ][ lo(k0..k0+31) : 64 B ],  rows zero-padded to whole chunks
