@@ -56,6 +56,8 @@ extern "C" {
 /*    Additive since, same version, continued: tsh_search_grouped_after, tsh_search_grouped_count,
  *    tsh_search_grouped_after_stats. */
 /*    Additive since, same version, continued: tsh_search_grouped_rows, tsh_search_grouped_rows_stats. */
+/*    Additive since, same version, continued: tsh_attr_create, tsh_attr_set, tsh_attr_destroy, tsh_mask_create_range,
+ *    tsh_mask_read. */
 
 /* status codes */
 #define TSH_OK 0
@@ -341,6 +343,66 @@ int64_t tsh_mask_kept(tsh_mask *mask);
 int32_t tsh_search_masked(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double distance_threshold,
                           tsh_mask *mask, int64_t *out_ids, double *out_dist, int32_t *out_count);
 int32_t tsh_search_submit_masked(tsh_index *idx, const float *query, int32_t k, tsh_mask *mask, int32_t *out_ticket);
+
+/* ---- attribute columns: a WHERE range made into a mask handle on the device (additive since ABI 5) ------------------
+ * tsh_mask_create takes a bitmap the HOST made: for `tenant = 7` or `ts BETWEEN a AND b` the caller evaluates the
+ * predicate row by row, maps primary keys to node ids (lib/src/core/vector_index_manager.dart:1223-1378), packs the
+ * bitmap and hands it over, and the library slices, counts and uploads it again.  With a predicate per query (one
+ * tenant each, a time window each) that is the whole cost of a lone filtered query.  An ATTRIBUTE handle keeps one
+ * int64 column beside the rows on the device, by node id, 8 B per row; tsh_mask_create_range makes a mask handle from
+ * one range term over it in one coalesced pass (tostore_amd/csrc/tsh_where.hip.h: a wave per 64 rows, its ballot is
+ * the mask word), optionally combined with a handle that exists.  The bitmap never exists on the host first.  The
+ * result is an ordinary tsh_mask: every entry that takes one works with it unchanged.
+ *
+ * tsh_attr_create: values[i] is the attribute of GLOBAL row id i; TSH_ATTR_NULL (INT64_MIN) says the row has no value,
+ *   and rows at or beyond n read as NULL.  tsh_attr_set extends or overwrites [first_row_id, first_row_id + n): the
+ *   append feed's companion (the column does not follow appends on its own).  Doubles and datetimes are stored by an
+ *   order-preserving key (the bindings' f64_order_key: the value's bits b as int64, b if b >= 0 else
+ *   b ^ 0x7FFFFFFFFFFFFFFF, NaNs made the positive quiet NaN first: double.compareTo's order, and never TSH_ATTR_NULL).
+ * tsh_mask_create_range: row i of the index's current rows is kept iff  v[i] != NULL  and
+ *   (lo <= v[i] <= hi) != (negate != 0),  the result and-ed (TSH_MASK_AND) or or-ed (TSH_MASK_OR) with W[i] when `with`
+ *   is given -- W is with's bitmap, zero-extended to the current rows.  So a NULL row, or a row beyond the column, is
+ *   kept by no term, negated or not (`with` under OR can still keep it); lo > hi is the empty range: nothing without
+ *   negate, every non-NULL row with it.  The answer is exact: NumPy on the host is the specification.  Conjunctions,
+ *   IN-lists and NOT are chains of calls; each returns a new handle and the caller destroys the intermediates.  `with`
+ *   may be any handle of the same index, made from a bitmap or from a range, and is left as it was.
+ *   The handle is a SNAPSHOT: a later tsh_attr_set or tsh_attr_destroy does not change it, and rows appended later are
+ *   not kept -- after a rebuild for a grown shard it keeps exactly the rows it kept before (the handle contract above).
+ *   Tombstones and quarantined rows are treated as for any handle.
+ *   TSH_E_BAD_ARG (each clears *out): a NULL idx, attr or out; combine neither TSH_MASK_AND nor TSH_MASK_OR, even with
+ *   with == NULL; an attr or `with` made for another index, or orphaned.
+ * tsh_mask_read: the handle's GLOBAL bitmap as it stands, for any handle however made: bit i (LSB first) = row id i,
+ *   bytes past what the handle knows read 0.  (A bitmap-made handle answers with its copy of the caller's bits.)
+ *   TSH_E_BAD_ARG: n_bytes < 0, a NULL out_bits with n_bytes > 0, an orphaned handle.
+ * Lifetime: an attribute handle belongs to the index it was made for and works with any kind of handle -- a whole index,
+ *   several devices (each shard holds its slice on its own device), a shard with global ids.  tsh_index_destroy
+ *   orphans it: later use answers TSH_E_BAD_ARG, and tsh_attr_destroy then frees only the handle itself.  The two
+ *   destroys may come in either order.
+ * Threads: any number of tsh_mask_create_range calls may share one attribute handle.  tsh_attr_set takes the index lock
+ *   the way an append does and waits for the calls that use the handle.
+ * Cost, measured on 1 M x 768, L2, k = 100 ("Attribute columns"; profiles/mask_where_ab.json), medians by the
+ *   host clock: making the handle takes 78 us for `x = c` keeping 1 % and 48 us for a range keeping 50 %, against 592
+ *   and 554 us for the host route (NumPy compare, packbits, tsh_mask_create) and 55 and 24 us for tsh_mask_create
+ *   alone from a bitmap that exists; a lone query including make and destroy takes 129 and 187 us against the host
+ *   route's 650 and 698.  The range kernel runs 5.5 us; the copy of the words back to the host (the batched path and
+ *   the quarantined rows read them there) is what the call costs over tsh_mask_create, and the list of a selective mask
+ *   (M1 6.5 us + M2 5.2 us, tsh_mask.hip.h, with their synchronise) the 30 us between the two predicates.  M1 stayed a
+ *   launch of its own: folding it into the range kernel would save under a tenth of the call.
+ * The attribute handle is a tsh_attr * (typedef below) and travels as `void *`, tsh_attr_create's `out` -- the address
+ *   of the caller's tsh_attr * -- too, exactly as a tsh_groups * does (see tsh_groups_create below).
+ * Not here: string or multi-valued attributes; several terms in one launch; a predicate evaluated inside the scan
+ *   kernels without a handle; a column that follows appends on its own; collective (sharded) creation -- every rank
+ *   makes its own handle from its own column, as with bitmaps. */
+#define TSH_ATTR_NULL INT64_MIN
+#define TSH_MASK_AND 0
+#define TSH_MASK_OR 1
+typedef struct tsh_attr tsh_attr;
+int32_t tsh_attr_create(tsh_index *idx, const int64_t *values, int64_t n, void *out);
+int32_t tsh_attr_set(void *attr, int64_t first_row_id, int64_t n, const int64_t *values);
+int32_t tsh_attr_destroy(void *attr);
+int32_t tsh_mask_create_range(tsh_index *idx, void *attr, int64_t lo, int64_t hi, int32_t negate, tsh_mask *with,
+                              int32_t combine, tsh_mask **out);
+int32_t tsh_mask_read(tsh_mask *mask, uint8_t *out_bits, int64_t n_bytes);
 
 /* Asynchronous form of a single-query tsh_search, for callers that keep several
  * independent queries in flight (the reference serves concurrent vectorSearch

@@ -30,6 +30,8 @@ TSH_E_PEER = -11
 ABI_VERSION = 5
 
 METRIC_L2, METRIC_IP, METRIC_COSINE = 0, 1, 2
+TSH_ATTR_NULL = -(1 << 63)  # an attribute column's "no value" (tsh_attr_create)
+TSH_MASK_AND, TSH_MASK_OR = 0, 1
 
 c_i32, c_i64, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 p_f32 = ctypes.POINTER(ctypes.c_float)
@@ -97,6 +99,11 @@ SIGNATURES = {
     "tsh_mask_create": (c_i32, [p_void, p_u8, c_i64, ctypes.POINTER(p_void)]),
     "tsh_mask_destroy": (c_i32, [p_void]),
     "tsh_mask_kept": (c_i64, [p_void]),
+    "tsh_attr_create": (c_i32, [p_void, p_i64, c_i64, p_void]),  # (out: the address of a handle, as void *)
+    "tsh_attr_set": (c_i32, [p_void, c_i64, c_i64, p_i64]),
+    "tsh_attr_destroy": (c_i32, [p_void]),
+    "tsh_mask_create_range": (c_i32, [p_void, p_void, c_i64, c_i64, c_i32, p_void, c_i32, ctypes.POINTER(p_void)]),
+    "tsh_mask_read": (c_i32, [p_void, p_u8, c_i64]),
     "tsh_search_masked": (c_i32, [p_void, p_f32, c_i32, c_i32, c_f64, p_void, p_i64, p_f64, p_i32]),
     "tsh_search_submit_masked": (c_i32, [p_void, p_f32, c_i32, p_void, p_i32]),
     "tsh_max_inflight": (c_i32, []),

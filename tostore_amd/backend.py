@@ -51,11 +51,37 @@ class HipMask:
                                               ctypes.byref(self._h)))
         index._live_masks().add(self)
 
+    @classmethod
+    def _where(cls, index: "HipVectorIndex", attr: "HipAttr", lo: int, hi: int, negate: bool, with_mask, combine) -> "HipMask":
+        """A handle made on the device from one range term over an attribute column (`tsh_mask_create_range`)."""
+        ops = {"and": _ffi.TSH_MASK_AND, "or": _ffi.TSH_MASK_OR, _ffi.TSH_MASK_AND: _ffi.TSH_MASK_AND, _ffi.TSH_MASK_OR: _ffi.TSH_MASK_OR}
+        if combine not in ops:
+            raise ValueError("combine is 'and' or 'or'")
+        # (a closed attr or with_mask raises here: NULL would read as "no attr" / "no with")
+        a = attr.handle()
+        w = with_mask.handle() if with_mask is not None else None
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.index = index
+        _ffi.check(_ffi.lib().tsh_mask_create_range(index._h, a, int(lo), int(hi), 1 if negate else 0, w, ops[combine],
+                                                    ctypes.byref(self._h)))
+        index._live_masks().add(self)
+        return self
+
     def handle(self):
         """The `tsh_mask*` to pass to the library; ValueError once the mask (or its index) was closed."""
         if not self._h:
             raise ValueError("the mask is closed (or its index was)")
         return self._h
+
+    def bits(self, n_bytes: Optional[int] = None) -> np.ndarray:
+        """The handle's GLOBAL bitmap as it stands (`tsh_mask_read`): bit i, LSB first, = row id i; uint8, by default
+        one bit per row id the index holds now.  Bytes past what the handle knows read 0."""
+        if n_bytes is None:
+            n_bytes = (int(self.index.size) + 7) // 8  # (size: one past the last row id, a shard handle's base included)
+        out = np.zeros(max(int(n_bytes), 0), dtype=np.uint8)
+        _ffi.check(_ffi.lib().tsh_mask_read(self.handle(), out.ctypes.data_as(_ffi.p_u8), int(n_bytes)))
+        return out
 
     @property
     def kept(self) -> int:
@@ -134,6 +160,64 @@ class HipGroups:
             pass
 
 
+ATTR_NULL = _ffi.TSH_ATTR_NULL
+
+
+def f64_order_key(a) -> np.ndarray:
+    """int64 keys of a double (or datetime-as-double) column for `HipVectorIndex.make_attr`: ordered as Dart's
+    double.compareTo orders the values (-0.0 before 0.0, NaN last, every NaN the same key), so a range over the values is
+    a range over the keys.  NaNs are made the positive quiet NaN first; with b the value's bits as int64 the key is b
+    for b >= 0 and b ^ 0x7FFFFFFFFFFFFFFF below: no key is ATTR_NULL (that would be the bits of -NaN with a full payload)."""
+    v = np.array(a, dtype=np.float64, copy=True).reshape(-1)
+    nan = np.isnan(v)
+    b = v.view(np.int64)
+    b[nan] = 0x7FF8000000000000  # the positive quiet NaN's bits
+    return np.where(b >= 0, b, b ^ np.int64(0x7FFFFFFFFFFFFFFF))
+
+
+class HipAttr:
+    """One scalar attribute of every row, kept on the device (`tsh_attr*`, include/tostore_hip.h), for
+    `HipVectorIndex.make_mask_where`: entry i of `values` (int64) belongs to GLOBAL row id i; `ATTR_NULL` says the row
+    has no value, and rows beyond the array read as NULL.  `set()` extends or overwrites a range, as the append feed does
+    for the rows.  Doubles go in by `f64_order_key`.  An index that is closed first closes its attributes, and a closed
+    handle is refused (ValueError)."""
+
+    def __init__(self, index: "HipVectorIndex", values):
+        v = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        self._h = ctypes.c_void_p()
+        self.index = index
+        _ffi.check(_ffi.lib().tsh_attr_create(index._h, v.ctypes.data_as(_ffi.p_i64), v.shape[0], ctypes.byref(self._h)))
+        index._live_masks().add(self)
+
+    def handle(self):
+        """The `tsh_attr*` to pass to the library; ValueError once the handle (or its index) was closed."""
+        if not self._h:
+            raise ValueError("the attribute handle is closed (or its index was)")
+        return self._h
+
+    def set(self, first_row_id: int, values) -> None:
+        """Entries [first_row_id, first_row_id + len(values)) of the column, extended with NULLs where it was shorter."""
+        v = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        _ffi.check(_ffi.lib().tsh_attr_set(self.handle(), int(first_row_id), v.shape[0], v.ctypes.data_as(_ffi.p_i64)))
+
+    def close(self) -> None:
+        if self._h:
+            _ffi.lib().tsh_attr_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipVectorIndex:
     """Owner of one `tsh_index*`.  Destroy exactly once (close / context manager)."""
 
@@ -180,6 +264,18 @@ class HipVectorIndex:
     def make_groups(self, group_of, n_groups: int) -> "HipGroups":
         """The rows' groups for search_grouped (entry i of `group_of`: the group of GLOBAL row id i, negative: none)."""
         return HipGroups(self, group_of, n_groups)
+
+    def make_attr(self, values) -> "HipAttr":
+        """A scalar attribute column on the device (entry i of `values`, int64: GLOBAL row id i; ATTR_NULL: no value)."""
+        return HipAttr(self, values)
+
+    def make_mask_where(self, attr: "HipAttr", lo: int, hi: int, negate: bool = False, with_mask: Optional["HipMask"] = None,
+                        combine="and") -> "HipMask":
+        """A mask handle made ON the device from one range term: keeps the rows whose attribute is not NULL and for which
+        (lo <= value <= hi) != negate, and-ed / or-ed (`combine`) with `with_mask` when one is given.  lo > hi is the
+        empty range.  Conjunctions, IN-lists and NOT are chains of calls; close the intermediates.  A snapshot: later
+        `attr.set()` calls and appends do not change it."""
+        return HipMask._where(self, attr, lo, hi, negate, with_mask, combine)
 
     def _live_masks(self) -> "weakref.WeakSet":
         """The masks and groups handles made for this index and not yet closed: close() closes them before it destroys

@@ -50,6 +50,7 @@
 #include "tsh_scan_f16_band.h"
 #include "tsh_scan_i8.hip.h"
 #include "tsh_scan_i8_band.h"
+#include "tsh_where.hip.h"
 
 using namespace tsh;
 
@@ -960,6 +961,18 @@ struct GroupPart {
   int32_t *d_group = nullptr;
   int64_t cap = 0;
   int32_t n_groups = 0;
+};
+
+// ---- attribute handles (tsh_attr_create, include/tostore_hip.h): one shard's part --------------------------------------
+// The caller's column sliced to this shard's rows on the device: entry r = the value of local row r, for the rows the
+// shard had when the part was built (rows beyond the caller's array: TSH_ATTR_NULL).  A mask made from the handle
+// (tsh_mask_create_range) that finds the shard grown, or the array changed by tsh_attr_set (built_rows = -1), rebuilds
+// it first (attr_part).  8 B per row.
+struct AttrPart {
+  int device = 0;
+  std::atomic<int64_t> built_rows{-1};
+  int64_t *d_vals = nullptr;
+  int64_t cap = 0;
 };
 
 // One query in flight on one context.  Its three kernels (scan, select,
@@ -2583,6 +2596,7 @@ struct tsh_index {
   std::atomic<int32_t> batch_min_nq{1};  // 0 never, 1 by estimated cost, n >= 2: from n queries per call on
   std::vector<tsh_mask *> masks;  // live mask handles made for this index (guarded by g_mask_mu): orphaned by destroy
   std::vector<struct tsh_groups *> groups;  // ... and live groups handles, the same way
+  std::vector<struct tsh_attr *> attrs;     // ... and live attribute handles
   std::unique_ptr<ShardWorkers> workers;  // multi-device handles: one persistent host thread per further shard
   // result-block buffers of multi-query calls, kept between calls: a fresh 6 MB allocation per call spends
   // ~0.3 ms in page faults when it is first written
@@ -2738,6 +2752,15 @@ struct tsh_groups {
   bool spans = false;
 };
 
+// ---- attribute handles ----------------------------------------------------------------------------------------
+struct tsh_attr {
+  tsh_index *idx = nullptr;     // nullptr: orphaned -- its index was destroyed first (parts freed then)
+  std::vector<int64_t> values;  // the caller's column by GLOBAL row id (its own copy: the parts are sliced from it)
+  std::shared_mutex use_mu;     // tsh_mask_create_range: shared, for the whole call; tsh_attr_set: exclusive
+  std::mutex mu;                // builds / rebuilds of the parts
+  std::vector<std::unique_ptr<AttrPart>> parts;  // one per shard of the index
+};
+
 namespace {
 
 // Settles a mask's destroy against its index's (either may come first, from any thread): index -> masks lists, every
@@ -2756,25 +2779,8 @@ void mask_part_free(MaskPart *p) {
   p->bytes = 0;
 }
 
-// (Re)builds one shard's part for the rows the shard has now.  Caller holds s->mu shared (the rows cannot change) and
-// m->mu.  The words are sliced and counted on the host once -- the batched path and the quarantined rows read them
-// there --, uploaded once, and a selective mask's list is compacted on the device (tsh_mask.hip.h).
-int mask_build_part(tsh_mask *m, MaskPart *p, Shard *s) {
-  HIPCHK(hipSetDevice(s->device));
-  p->device = s->device;
-  const int64_t rows = s->rows;
-  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
-  // bits at or beyond the caller's n_bytes are not kept: the handle's copy grows with zeros to what slice_mask reads
-  const size_t need = (size_t)((s->row_base + rows + 7) / 8) + 1;
-  if (m->bits.size() < need) m->bits.resize(need, 0);
-  p->h_words.assign((size_t)n_tiles, 0);
-  if (n_tiles > 0) slice_mask(s, m->bits.data(), p->h_words.data(), n_tiles);
-  p->pre.assign((size_t)n_tiles + 1, 0);
-  for (int32_t t = 0; t < n_tiles; ++t) p->pre[(size_t)t + 1] = p->pre[(size_t)t] + __builtin_popcountll(p->h_words[(size_t)t]);
-  p->kept = p->pre[(size_t)n_tiles];
-  p->n_tiles = n_tiles;
-  p->list_padded = 0;
-  hipStream_t st = s->aux_stream;
+// Room for n_tiles words in a part's d_words (the current device is the part's)
+int mask_reserve_words(MaskPart *p, int32_t n_tiles) {
   if (n_tiles > p->words_cap) {
     hipFree(p->d_words);
     p->d_words = nullptr;
@@ -2785,8 +2791,21 @@ int mask_build_part(tsh_mask *m, MaskPart *p, Shard *s) {
     p->words_cap = want;
     p->bytes += want * 8;
   }
-  if (n_tiles > 0)
-    HIPCHK(hipMemcpyAsync(p->d_words, p->h_words.data(), (size_t)n_tiles * 8, hipMemcpyHostToDevice, st));
+  return TSH_OK;
+}
+
+// The second half of a part's build, whichever way its words were obtained (sliced from the handle's bitmap and uploaded:
+// mask_build_part; or written by mask_range_kernel and copied back: mask_range_part): p->h_words and p->d_words hold the
+// same n_tiles words (an upload may still be in flight on s->aux_stream; a copy back is done).  Counts them on the host once -- the
+// batched path and the quarantined rows read words and prefix there -- and compacts a selective mask's list on the device
+// (tsh_mask.hip.h).  Returns with the stream drained and the part current for `rows`.
+int mask_finish_part(MaskPart *p, Shard *s, int64_t rows, int32_t n_tiles) {
+  p->pre.assign((size_t)n_tiles + 1, 0);
+  for (int32_t t = 0; t < n_tiles; ++t) p->pre[(size_t)t + 1] = p->pre[(size_t)t] + __builtin_popcountll(p->h_words[(size_t)t]);
+  p->kept = p->pre[(size_t)n_tiles];
+  p->n_tiles = n_tiles;
+  p->list_padded = 0;
+  hipStream_t st = s->aux_stream;
   // the list: wherever a search may scan the kept rows as one (row_list_pays: few enough for the exact path at any
   // k and row width, or fewer than one row in list_div) -- compacted on the device, in id order
   const int64_t padded = round_up(p->kept, 64);
@@ -2832,6 +2851,25 @@ int mask_build_part(tsh_mask *m, MaskPart *p, Shard *s) {
   }
   p->built_rows.store(rows, std::memory_order_release);
   return TSH_OK;
+}
+
+// (Re)builds one shard's part for the rows the shard has now.  Caller holds s->mu shared (the rows cannot change) and
+// m->mu.  The words are sliced from the handle's bitmap on the host and uploaded once; mask_finish_part does the rest.
+int mask_build_part(tsh_mask *m, MaskPart *p, Shard *s) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  const int64_t rows = s->rows;
+  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
+  // bits at or beyond the caller's n_bytes are not kept: the handle's copy grows with zeros to what slice_mask reads
+  const size_t need = (size_t)((s->row_base + rows + 7) / 8) + 1;
+  if (m->bits.size() < need) m->bits.resize(need, 0);
+  p->h_words.assign((size_t)n_tiles, 0);
+  if (n_tiles > 0) slice_mask(s, m->bits.data(), p->h_words.data(), n_tiles);
+  int rc = mask_reserve_words(p, n_tiles);
+  if (rc) return rc;
+  if (n_tiles > 0)
+    HIPCHK(hipMemcpyAsync(p->d_words, p->h_words.data(), (size_t)n_tiles * 8, hipMemcpyHostToDevice, s->aux_stream));
+  return mask_finish_part(p, s, rows, n_tiles);
 }
 
 // shard g's part of a handle, current for the rows the shard has (caller holds s->mu shared); nullptr + *rc on failure
@@ -2913,6 +2951,105 @@ const GroupPart *groups_part(tsh_groups *h, size_t g, Shard *s, int *rc) {
     if (*rc) return nullptr;
   }
   return p;
+}
+
+void attr_part_free(AttrPart *p) {
+  if (hipSetDevice(p->device) != hipSuccess) return;
+  hipFree(p->d_vals);
+  p->d_vals = nullptr;
+  p->cap = 0;
+  p->built_rows.store(-1);
+}
+
+// (Re)builds one shard's part for the rows the shard has now: the slice of the handle's column, TSH_ATTR_NULL beyond it.
+// Caller holds s->mu shared, a->use_mu (shared or exclusive) and a->mu
+int attr_build_part(tsh_attr *a, AttrPart *p, Shard *s) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  const int64_t rows = s->rows;
+  if (rows > p->cap) {
+    hipFree(p->d_vals);
+    p->d_vals = nullptr;
+    p->cap = 0;
+    const int64_t want = round_up(rows + rows / 8, 1024);
+    HIPCHK(hipMalloc(&p->d_vals, (size_t)want * sizeof(int64_t)));
+    p->cap = want;
+  }
+  if (rows > 0) {
+    const int64_t have = std::min<int64_t>(rows, std::max<int64_t>((int64_t)a->values.size() - s->row_base, 0));
+    // (the rows the column names go up from the handle's copy as they lie; only the rows beyond it need a staged NULL)
+    if (have > 0)
+      HIPCHK(hipMemcpyAsync(p->d_vals, a->values.data() + s->row_base, (size_t)have * sizeof(int64_t), hipMemcpyHostToDevice,
+                            s->aux_stream));
+    std::vector<int64_t> nulls((size_t)(rows - have), ATTR_NULL);
+    if (rows > have)
+      HIPCHK(hipMemcpyAsync(p->d_vals + have, nulls.data(), (size_t)(rows - have) * sizeof(int64_t), hipMemcpyHostToDevice,
+                            s->aux_stream));
+    HIPCHK(hipStreamSynchronize(s->aux_stream));
+  }
+  p->built_rows.store(rows, std::memory_order_release);
+  return TSH_OK;
+}
+
+// shard g's part of an attribute handle, current for the rows the shard has (caller holds s->mu shared and h->use_mu
+// shared); nullptr + *rc on failure.  As groups_part: appends take the shard exclusively, tsh_attr_set the handle, so no
+// kernel reads the buffer while it is rebuilt
+const AttrPart *attr_part(tsh_attr *h, size_t g, Shard *s, int *rc) {
+  *rc = TSH_OK;
+  AttrPart *p = h->parts[g].get();
+  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
+    *rc = attr_build_part(h, p, s);
+    if (*rc) return nullptr;
+  }
+  return p;
+}
+
+// The words of a mask part obtained ON the device (tsh_where.hip.h): the range term over the shard's slice of the column,
+// combined with another handle's words if one is given, written straight into p->d_words by mask_range_kernel and copied
+// back once into p->h_words; mask_finish_part does the rest, as for an uploaded bitmap.  Caller holds s->mu shared, the
+// new handle's mu, and the attribute handle's use_mu shared; ap and wp are current for the shard's rows
+int mask_range_part(MaskPart *p, Shard *s, const AttrPart *ap, int64_t lo, int64_t hi, bool negate, const MaskPart *wp,
+                    int32_t combine) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  const int64_t rows = s->rows;
+  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
+  try {
+    p->h_words.assign((size_t)n_tiles, 0);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %d mask words", n_tiles);
+  }
+  int rc = mask_reserve_words(p, n_tiles);
+  if (rc) return rc;
+  if (n_tiles > 0) {
+    hipStream_t st = s->aux_stream;
+    // (wp was built for the same rows: n_tiles words, the bits at or past the last row 0)
+    mask_range_kernel<<<where_grid(n_tiles), WHERE_BLOCK, 0, st>>>(ap->d_vals, rows, n_tiles, lo, hi, negate ? 1 : 0,
+                                                                   wp ? wp->d_words : nullptr, combine, p->d_words);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return mask_finish_part(p, s, rows, n_tiles);
+}
+
+// A part's words put back where slice_mask would take them from: bit r of the words = bit row_base + r of the GLOBAL
+// bitmap (bits holds at least (row_base + rows + 7) / 8 + 1 bytes; or-ed in: neighbouring shards may share a byte)
+void unslice_mask(int64_t row_base, int64_t rows, const uint64_t *words, uint8_t *bits) {
+  const uint8_t *wb = reinterpret_cast<const uint8_t *>(words);
+  const int64_t nbytes = (rows + 7) / 8, b0 = row_base / 8;
+  const int sh = (int)(row_base & 7);
+  if (sh == 0) {
+    for (int64_t i = 0; i < nbytes; ++i) bits[b0 + i] |= wb[i];
+    return;
+  }
+  for (int64_t i = 0; i < nbytes; ++i) {
+    const unsigned v = wb[i];
+    bits[b0 + i] |= (uint8_t)(v << sh);
+    if (v >> (8 - sh)) bits[b0 + i + 1] |= (uint8_t)(v >> (8 - sh));
+  }
 }
 
 // tsh_groups::spans: one pass over the array against the shards' row ranges.  A multi-device index cuts its rows at
@@ -3114,6 +3251,11 @@ int32_t tsh_index_destroy(tsh_index *idx) {
       g->idx = nullptr;
     }
     idx->groups.clear();
+    for (tsh_attr *a : idx->attrs) {  // ... and attribute handles
+      for (auto &p : a->parts) attr_part_free(p.get());
+      a->idx = nullptr;
+    }
+    idx->attrs.clear();
   }
   idx->workers.reset();  // joins the shard threads
   for (auto &s : idx->shards) {
@@ -3843,6 +3985,147 @@ int64_t tsh_mask_kept(tsh_mask *mask) {
     kept += p->kept;
   }
   return kept;
+}
+
+// ---- attribute columns: a WHERE range term made into a mask handle on the device (tsh_where.hip.h) ----------------------
+// (the attribute handle travels as void *, and create's out as the address of one: see the header)
+int32_t tsh_attr_create(tsh_index *idx, const int64_t *values, int64_t n, void *out_p) {
+  tsh_attr **out = static_cast<tsh_attr **>(out_p);
+  if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (n < 0 || (n > 0 && !values)) return set_err(TSH_E_BAD_ARG, "values is NULL / n < 0");
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  std::unique_ptr<tsh_attr> a(new tsh_attr());
+  a->idx = idx;
+  try {
+    a->values.assign(values, values + n);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %lld attribute values", (long long)n);
+  }
+  for (size_t i = 0; i < idx->shards.size(); ++i) a->parts.emplace_back(new AttrPart());
+  int rc = TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
+      Shard *s = idx->shards[i].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      rc = attr_build_part(a.get(), a->parts[i].get(), s);
+    }
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    for (auto &p : a->parts) attr_part_free(p.get());
+    g_err = keep;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->attrs.push_back(a.get());
+  }
+  *out = a.release();
+  return TSH_OK;
+}
+
+int32_t tsh_attr_set(void *attr, int64_t first_row_id, int64_t n, const int64_t *values) {
+  tsh_attr *a = static_cast<tsh_attr *>(attr);
+  if (!a) return set_err(TSH_E_BAD_ARG, "attr is NULL");
+  if (first_row_id < 0 || n < 0 || (n > 0 && !values)) return set_err(TSH_E_BAD_ARG, "values is NULL / negative row range");
+  std::lock_guard<std::mutex> hold(g_mask_mu);  // (the index cannot be destroyed under the call)
+  tsh_index *idx = a->idx;
+  if (!idx) return set_err(TSH_E_BAD_ARG, "the attribute handle's index was destroyed");
+  if (n == 0) return TSH_OK;
+  std::lock_guard<std::mutex> lk(idx->mu);  // as an append does
+  std::unique_lock<std::shared_mutex> xl(a->use_mu);
+  try {
+    if ((int64_t)a->values.size() < first_row_id + n) a->values.resize((size_t)(first_row_id + n), ATTR_NULL);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %lld attribute values", (long long)(first_row_id + n));
+  }
+  memcpy(a->values.data() + first_row_id, values, (size_t)n * sizeof(int64_t));
+  for (auto &p : a->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next mask made of each shard
+  return TSH_OK;
+}
+
+int32_t tsh_attr_destroy(void *attr) {
+  tsh_attr *a = static_cast<tsh_attr *>(attr);
+  if (!a) return TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    if (tsh_index *idx = a->idx) {  // (an orphan's parts went with its index)
+      idx->attrs.erase(std::remove(idx->attrs.begin(), idx->attrs.end(), a), idx->attrs.end());
+      for (auto &p : a->parts) attr_part_free(p.get());
+    }
+  }
+  delete a;
+  return TSH_OK;
+}
+
+int32_t tsh_mask_create_range(tsh_index *idx, void *attr_p, int64_t lo, int64_t hi, int32_t negate, tsh_mask *with,
+                              int32_t combine, tsh_mask **out) {
+  tsh_attr *attr = static_cast<tsh_attr *>(attr_p);
+  if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (combine != TSH_MASK_AND && combine != TSH_MASK_OR) return set_err(TSH_E_BAD_ARG, "combine %d is neither TSH_MASK_AND nor TSH_MASK_OR", combine);
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (!attr) return set_err(TSH_E_BAD_ARG, "attr is NULL");
+  if (attr->idx != idx) return set_err(TSH_E_BAD_ARG, "the attribute handle was made for another index (or its index was destroyed)");
+  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
+  std::unique_ptr<tsh_mask> m(new tsh_mask());
+  m->idx = idx;
+  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
+  int rc = TSH_OK;
+  {
+    // the column stays as it is until every part is made (given up before g_mask_mu is taken below: tsh_attr_set holds
+    // that one while it waits for this one)
+    std::shared_lock<std::shared_mutex> use(attr->use_mu);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
+      Shard *s = idx->shards[g].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      const AttrPart *ap = attr_part(attr, g, s, &rc);
+      if (!ap) break;
+      const MaskPart *wp = with ? mask_part(with, g, s, &rc) : nullptr;
+      if (with && !wp) break;
+      MaskPart *p = m->parts[g].get();
+      rc = mask_range_part(p, s, ap, lo, hi, negate != 0, wp, combine);
+      if (rc) break;
+      // the handle's GLOBAL bitmap, as a bitmap-made handle holds it: what a rebuild after an append slices (the rows it
+      // keeps then are the rows it keeps now) and what tsh_mask_read copies
+      try {
+        const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
+        if (m->bits.size() < need) m->bits.resize(need, 0);
+      } catch (...) {
+        rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
+        break;
+      }
+      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
+    }
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    for (auto &p : m->parts) mask_part_free(p.get());
+    g_err = keep;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->masks.push_back(m.get());
+  }
+  *out = m.release();
+  return TSH_OK;
+}
+
+int32_t tsh_mask_read(tsh_mask *mask, uint8_t *out_bits, int64_t n_bytes) {
+  if (!mask) return set_err(TSH_E_BAD_ARG, "mask is NULL");
+  if (n_bytes < 0 || (n_bytes > 0 && !out_bits)) return set_err(TSH_E_BAD_ARG, "out_bits is NULL / n_bytes < 0");
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  if (!mask->idx) return set_err(TSH_E_BAD_ARG, "the mask's index was destroyed");
+  std::lock_guard<std::mutex> ml(mask->mu);  // (a rebuild may be extending the bitmap)
+  const size_t have = std::min<size_t>(mask->bits.size(), (size_t)n_bytes);
+  if (have > 0) memcpy(out_bits, mask->bits.data(), have);
+  if ((size_t)n_bytes > have) memset(out_bits + have, 0, (size_t)n_bytes - have);
+  return TSH_OK;
 }
 
 // ---- asynchronous single-query searches ------------------------------------------

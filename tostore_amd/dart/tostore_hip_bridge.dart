@@ -67,6 +67,18 @@ typedef _MaskDestroyC = Int32 Function(Pointer<Void>);
 typedef _MaskDestroyD = int Function(Pointer<Void>);
 typedef _MaskKeptC = Int64 Function(Pointer<Void>);
 typedef _MaskKeptD = int Function(Pointer<Void>);
+typedef _AttrCreateC = Int32 Function(Pointer<Void>, Pointer<Int64>, Int64, Pointer<Void>);
+typedef _AttrCreateD = int Function(Pointer<Void>, Pointer<Int64>, int, Pointer<Void>);
+typedef _AttrSetC = Int32 Function(Pointer<Void>, Int64, Int64, Pointer<Int64>);
+typedef _AttrSetD = int Function(Pointer<Void>, int, int, Pointer<Int64>);
+typedef _AttrDestroyC = Int32 Function(Pointer<Void>);
+typedef _AttrDestroyD = int Function(Pointer<Void>);
+typedef _MaskCreateRangeC = Int32 Function(
+    Pointer<Void>, Pointer<Void>, Int64, Int64, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
+typedef _MaskCreateRangeD = int Function(
+    Pointer<Void>, Pointer<Void>, int, int, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
+typedef _MaskReadC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Int64);
+typedef _MaskReadD = int Function(Pointer<Void>, Pointer<Uint8>, int);
 typedef _SearchMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double,
     Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, double,
@@ -450,6 +462,11 @@ final class HipVectorBackend {
   static late final _MaskCreateD _maskCreate;
   static late final _MaskDestroyD _maskDestroy;
   static late final _MaskKeptD _maskKept;
+  static late final _AttrCreateD _attrCreate;
+  static late final _AttrSetD _attrSet;
+  static late final _AttrDestroyD _attrDestroy;
+  static late final _MaskCreateRangeD _maskCreateRange;
+  static late final _MaskReadD _maskRead;
   static late final _SearchMaskedD _searchMasked;
   static late final _SubmitMaskedD _submitMasked;
 
@@ -556,6 +573,11 @@ final class HipVectorBackend {
       _maskCreate = lib.lookupFunction<_MaskCreateC, _MaskCreateD>('tsh_mask_create');
       _maskDestroy = lib.lookupFunction<_MaskDestroyC, _MaskDestroyD>('tsh_mask_destroy');
       _maskKept = lib.lookupFunction<_MaskKeptC, _MaskKeptD>('tsh_mask_kept');
+      _attrCreate = lib.lookupFunction<_AttrCreateC, _AttrCreateD>('tsh_attr_create');
+      _attrSet = lib.lookupFunction<_AttrSetC, _AttrSetD>('tsh_attr_set');
+      _attrDestroy = lib.lookupFunction<_AttrDestroyC, _AttrDestroyD>('tsh_attr_destroy');
+      _maskCreateRange = lib.lookupFunction<_MaskCreateRangeC, _MaskCreateRangeD>('tsh_mask_create_range');
+      _maskRead = lib.lookupFunction<_MaskReadC, _MaskReadD>('tsh_mask_read');
       _searchMasked = lib.lookupFunction<_SearchMaskedC, _SearchMaskedD>('tsh_search_masked');
       _submitMasked =
           lib.lookupFunction<_SubmitMaskedC, _SubmitMaskedD>('tsh_search_submit_masked');
@@ -687,6 +709,55 @@ final class HipVectorBackend {
       return HipRowMask._(out.value);
     } finally {
       calloc.free(buf);
+      calloc.free(out);
+    }
+  }
+
+  /// One scalar attribute of every node id, kept on the device (tsh_attr_create): entry i of `values` belongs to node
+  /// id i, [HipRowAttr.nullValue] says the row has none, rows beyond the list read as NULL.  The column crosses the FFI
+  /// boundary once; [HipRowAttr.set] extends it as rows are appended.  Doubles and DateTimes go in by
+  /// [HipRowAttr.doubleKey].  Dispose it before this backend.
+  HipRowAttr? createAttr(Int64List values) {
+    final buf = calloc<Int64>(values.isEmpty ? 1 : values.length);
+    final out = calloc<Pointer<Void>>();
+    try {
+      buf.asTypedList(values.length).setAll(0, values);
+      final rc = _attrCreate(_handle, buf, values.length, out.cast<Void>());
+      if (rc != 0) {
+        Logger.warn('tsh_attr_create failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return HipRowAttr._(out.value);
+    } finally {
+      calloc.free(buf);
+      calloc.free(out);
+    }
+  }
+
+  /// A mask made ON the device from one range term (tsh_mask_create_range): keeps the node ids whose attribute is not
+  /// NULL and for which (lo <= value <= hi) != negate, and-ed (or, with `or: true`, or-ed) with `withMask` when one is
+  /// given.  lo > hi is the empty range.  `tenant IN (3, 7) AND ts BETWEEN a AND b AND NOT flag` is a chain of calls, each
+  /// returning a new mask; dispose the intermediates.  The mask is a snapshot: later [HipRowAttr.set] calls and appends
+  /// do not change it.  Null on any native failure; a disposed [HipRowAttr] or `withMask` is refused (null, with a
+  /// warning), never sent as NULL.
+  HipRowMask? createMaskWhere(HipRowAttr attr, int lo, int hi, {bool negate = false, HipRowMask? withMask, bool or = false}) {
+    if (attr._attr == nullptr) {
+      Logger.warn('createMaskWhere with a disposed HipRowAttr', label: 'HipVectorBackend');
+      return null;
+    }
+    if (withMask != null && withMask._mask == nullptr) {
+      Logger.warn('createMaskWhere with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    final out = calloc<Pointer<Void>>();
+    try {
+      final rc = _maskCreateRange(_handle, attr._attr, lo, hi, negate ? 1 : 0, withMask?._mask ?? nullptr, or ? 1 : 0, out);
+      if (rc != 0) {
+        Logger.warn('tsh_mask_create_range failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return HipRowMask._(out.value);
+    } finally {
       calloc.free(out);
     }
   }
@@ -1914,10 +1985,69 @@ final class HipRowMask {
   /// Rows the mask keeps among the index's current node ids (tombstones not subtracted); -1 on failure.
   int get kept => _mask == nullptr ? -1 : HipVectorBackend._maskKept(_mask);
 
+  /// [HipVectorBackend.createMaskWhere] by its other name: the mask of one range term over an attribute column.
+  static HipRowMask? where(HipVectorBackend backend, HipRowAttr attr, int lo, int hi,
+          {bool negate = false, HipRowMask? withMask, bool or = false}) =>
+      backend.createMaskWhere(attr, lo, hi, negate: negate, withMask: withMask, or: or);
+
+  /// The first `nBytes` bytes of the mask's bitmap as it stands (tsh_mask_read): bit i (LSB first) = node id i, bytes
+  /// past what the mask knows read 0.  Null on failure, or on a disposed mask.
+  Uint8List? readBits(int nBytes) {
+    if (_mask == nullptr || nBytes < 0) return null;
+    final buf = calloc<Uint8>(nBytes == 0 ? 1 : nBytes);
+    try {
+      if (HipVectorBackend._maskRead(_mask, buf, nBytes) != 0) return null;
+      return Uint8List.fromList(buf.asTypedList(nBytes));
+    } finally {
+      calloc.free(buf);
+    }
+  }
+
   void dispose() {
     if (_mask != nullptr) {
       HipVectorBackend._maskDestroy(_mask);
       _mask = nullptr;
+    }
+  }
+}
+
+/// One scalar attribute of every node id ([HipVectorBackend.createAttr], tsh_attr_create), kept on the device for as
+/// many [HipVectorBackend.createMaskWhere] calls as it serves.  [set] extends or overwrites a range of entries, the
+/// companion of the append feed.  Dispose it before its backend; a disposed handle is refused by
+/// [HipVectorBackend.createMaskWhere] (null, with a warning), and one whose backend was disposed first is orphaned by
+/// the library and still safe to dispose.  Masks made from it outlive it.
+final class HipRowAttr {
+  Pointer<Void> _attr;
+
+  HipRowAttr._(this._attr);
+
+  /// TSH_ATTR_NULL: the row has no value, and no term keeps it.
+  static const int nullValue = -9223372036854775808;
+
+  /// The int64 key of a double column's value (a DateTime's microseconds need none: they are ints): ordered as
+  /// double.compareTo orders the values, -0.0 before 0.0 and NaN last, and never [nullValue].
+  static int doubleKey(double v) {
+    if (v.isNaN) return 0x7FF8000000000000;
+    final b = (ByteData(8)..setFloat64(0, v)).getInt64(0);
+    return b >= 0 ? b : b ^ 0x7FFFFFFFFFFFFFFF;
+  }
+
+  /// Entries [firstNodeId, firstNodeId + values.length) of the column; false on failure (or on a disposed handle).
+  bool set(int firstNodeId, Int64List values) {
+    if (_attr == nullptr) return false;
+    final buf = calloc<Int64>(values.isEmpty ? 1 : values.length);
+    try {
+      buf.asTypedList(values.length).setAll(0, values);
+      return HipVectorBackend._attrSet(_attr, firstNodeId, values.length, buf) == 0;
+    } finally {
+      calloc.free(buf);
+    }
+  }
+
+  void dispose() {
+    if (_attr != nullptr) {
+      HipVectorBackend._attrDestroy(_attr);
+      _attr = nullptr;
     }
   }
 }
