@@ -57,6 +57,18 @@ extern "C" void batch_sample_window_of(const int32_t *pre, int32_t n_words, int6
   out[1] = w.best;
 }
 
+// The power-of-two scale of the fp16 operands whose largest magnitude is `top` (rows: f16_rows_top; queries: the batch's
+// largest element).  Returns 1 inside the guard of f16_scale_exp, 0 where the plan turns to bf16x3 (rows) or the batch
+// answers its queries one by one (queries); *exp is set either way (tests/scale_inputs.py).
+extern "C" int batch_f16_scale_exp_of(float top, int *exp) { return tsh::f16_scale_exp(top, exp) ? 1 : 0; }
+
+// Does a call of nq queries on a shard of `rows` rows go to the matrix cores (shard_takes_batch)?  batch_min_nq: the
+// option (0 never, 1 by cost, n >= 2 from n queries on).
+extern "C" int batch_takes_of(int metric, int dim, int64_t rows, int batch_min_nq, int nq, int k) {
+  const tsh::BatchShardFacts s = facts(metric, dim, rows, 1.f, 1.f, 1.f, 3, 1);
+  return tsh::shard_takes_batch(s, batch_min_nq, nq, k) ? 1 : 0;
+}
+
 extern "C" int batch_k_est_of(int k, int64_t rows, int64_t n_sample) { return tsh::batch_k_est(k, rows, n_sample); }
 
 extern "C" void batch_tile_slot(int q_tiles, int n_tiles, int b, int *out) { tsh::batch_tile_of(q_tiles, n_tiles, b, &out[0], &out[1]); }

@@ -14,3 +14,7 @@ extern "C" int scan_f16_band_of(int metric, int dim, const float *q, float max_n
   out[2] = b.w_max;
   return b.ok ? 1 : 0;
 }
+
+// The scale of the fp16 copy for a shard whose largest |element| is max_abs: *v_exp is set either way.  Returns 1 when
+// the scale is inside the guard of scan_f16_exp, 0 when the scan stays on f32 (tests/scale_inputs.py).
+extern "C" int scan_f16_exp_of(float max_abs, int *v_exp) { return tsh::scan_f16_exp(max_abs, v_exp) ? 1 : 0; }

@@ -1,7 +1,9 @@
 // Host-only check of tostore_amd/csrc/tsh_scan_f16_band.h: the band claimed for the fp16 scan's key holds for a software
 // model of the kernel's arithmetic (operands rounded to fp16 after the power-of-two scale, f32 FMA chain, the epilogue's
 // roundings), on random rows, on rows whose operands sit at fp16 rounding midpoints -/+ 1 ulp with products of one sign,
-// and on rows deep in fp16's subnormal steps.  Prints the largest observed / claimed ratio; exit status 1 on a miss.
+// and on rows deep in fp16's subnormal steps -- and, for L2, that the band also reaches the ORACLE's key of the row: its
+// f64 sum of (q_j - v_ij)^2 in element order less |q|^2, the number the ids are decided by (queries 2^40 above and below
+// the rows, where that sum's own rounding is the whole band).  Prints the largest observed / claimed ratio; exit status 1 on a miss.
 #include <cmath>
 #include <cstdio>
 #include <random>
@@ -21,7 +23,7 @@ static float to_f16(float x) {
   return (float)(std::nearbyint((double)x / step) * step);
 }
 
-static double run(int metric, int dim, int pattern, unsigned seed) {
+static double run(int metric, int dim, int pattern, unsigned seed, int qexp = 0) {
   std::mt19937_64 rng(seed);
   std::uniform_real_distribution<double> U(0.0, 1.0);
   std::normal_distribution<double> G(0.0, 1.0);
@@ -32,7 +34,7 @@ static double run(int metric, int dim, int pattern, unsigned seed) {
     return (float)std::ldexp(1.0 + j * std::ldexp(1.0, -10) + std::ldexp(1.0, -11) + (up ? 1 : -1) * std::ldexp(1.0, -21), e);
   };
   std::vector<float> q(dim);
-  for (auto &x : q) x = pattern ? pat(false) : (float)G(rng);
+  for (auto &x : q) x = std::ldexp(pattern ? pat(false) : (float)G(rng), qexp);
   std::vector<std::vector<float>> rows(n, std::vector<float>(dim));
   float max_abs = 0.f, max_norm = 0.f, min_norm = INFINITY;
   std::vector<double> nrm(n);
@@ -56,8 +58,12 @@ static double run(int metric, int dim, int pattern, unsigned seed) {
   double worst = 0;
   for (int i = 0; i < n; ++i) {
     float lane[64] = {0};  // 64 FMA chains, then a pairwise tree: the kernel's shape
-    long double dot = 0;
+    long double dot = 0, qq = 0;
+    double oracle = 0;  // the oracle's sum: f64, element order
     for (int j = 0; j < dim; ++j) {
+      const double diff = (double)q[j] - (double)rows[i][j];
+      oracle += diff * diff;
+      qq += (long double)q[j] * q[j];
       const float h = to_f16(rows[i][j] * S);
       const int l = (j / 4) % 64;
       lane[l] = std::fmaf(q[j], h, lane[l]);
@@ -76,6 +82,10 @@ static double run(int metric, int dim, int pattern, unsigned seed) {
     const float up = key + w;  // what the kernel stores
     const double ratio = (double)std::fabs((long double)up - w - exact) / w;
     if (ratio > worst) worst = ratio;
+    if (metric == 0) {
+      const double r2 = (double)std::fabs((long double)up - w - ((long double)oracle - qq)) / w;
+      if (r2 > worst) worst = r2;
+    }
     if (!(w <= b.w_max)) ++fails;
   }
   if (!(worst <= 1.0)) ++fails;
@@ -87,6 +97,9 @@ int main() {
     for (int dim : {256, 768, 1000, 1536, 3584})
       for (int pattern = 0; pattern < 3; ++pattern)
         printf("metric %d dim %4d pattern %d: max observed / claimed = %.4f\n", metric, dim, pattern, run(metric, dim, pattern, 17u * dim + metric));
+  for (int dim : {256, 768})
+    for (int qexp : {-40, 30, 40, 46})
+      printf("metric 0 dim %4d queries x 2^%d: max observed / claimed = %.4f\n", dim, qexp, run(0, dim, 0, 23u * dim + qexp, qexp));
   // outside the model: a non-finite query, a cosine shard with a zero row
   std::vector<float> q(256, 1.f);
   q[3] = INFINITY;

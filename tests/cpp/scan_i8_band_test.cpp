@@ -5,7 +5,9 @@
 //   pattern 1  rows whose elements sit at quantisation midpoints (codes +/- 1/2), every error of the sign of its q_j
 //   pattern 2  rows with one dominant element (every other code is 0 or +/- 1)
 //   pattern 3  rows so small that their scale is at the floor (elements below 2^-126 / subnormal), among normal ones
-// with mixed-sign and all-negative queries, d = 100, 768, 1000.  Both stored sides are checked: lower <= exact <= upper.
+// with mixed-sign and all-negative queries, d = 100, 768, 1000.  Both stored sides are checked: lower <= exact <= upper --
+// and, for L2, lower <= the ORACLE's key <= upper: its f64 sum of (q_j - v_ij)^2 in element order less |q|^2, the number
+// the ids are decided by (also with queries 2^40 above and below the rows, where that sum's own rounding is the whole band).
 // Prints the largest observed / claimed ratio; exit status 1 on a miss.
 #include <cmath>
 #include <cstdio>
@@ -16,13 +18,13 @@
 
 static int fails = 0;
 
-static double run(int metric, int dim, int pattern, int qsign, unsigned seed) {
+static double run(int metric, int dim, int pattern, int qsign, unsigned seed, int qexp = 0) {
   std::mt19937_64 rng(seed);
   std::uniform_real_distribution<double> U(0.0, 1.0);
   std::normal_distribution<double> G(0.0, 1.0);
   const int n = 300, nch = ((dim + 3) / 4 + 63) / 64;
   std::vector<float> q(dim);
-  for (auto &x : q) x = qsign ? -(float)std::fabs(G(rng)) - 0.01f : (float)G(rng);
+  for (auto &x : q) x = std::ldexp(qsign ? -(float)std::fabs(G(rng)) - 0.01f : (float)G(rng), qexp);
   std::vector<std::vector<float>> rows(n, std::vector<float>(dim));
   float max_abs = 0.f, max_norm = 0.f, min_norm = INFINITY;
   std::vector<double> nrm(n);
@@ -58,8 +60,12 @@ static double run(int metric, int dim, int pattern, int qsign, unsigned seed) {
     for (int j = 0; j < dim; ++j) mx = std::fmax(mx, std::fabs(rows[i][j]));
     const float sc = tsh::scan_i8_scale(mx);
     float lane[64] = {0};  // 64 FMA chains, then a pairwise tree: the kernel's shape
-    long double dot = 0;
+    long double dot = 0, qq = 0;
+    double oracle = 0;  // the oracle's sum: f64, element order
     for (int j = 0; j < dim; ++j) {
+      const double diff = (double)q[j] - (double)rows[i][j];
+      oracle += diff * diff;
+      qq += (long double)q[j] * q[j];
       float c = std::nearbyint(rows[i][j] / sc);
       c = std::fmin(std::fmax(c, -127.f), 127.f);
       const float byte = c + 128.f;
@@ -81,6 +87,7 @@ static double run(int metric, int dim, int pattern, int qsign, unsigned seed) {
     else w = std::fmaf(b.a_s, sc, std::fmaf(b.a_v, std::sqrt(sq), b.beta));
     const float lo = key - w, up = key + w;  // what the kernel stores / folds into the tile's minimum
     if (!((long double)lo <= exact && exact <= (long double)up)) ++fails;
+    if (metric == 0 && !((long double)lo <= (long double)oracle - qq && (long double)oracle - qq <= (long double)up)) ++fails;
     const double ratio = (double)std::fabs((long double)key - exact) / w;
     if (ratio > worst) worst = ratio;
   }
@@ -95,6 +102,9 @@ int main() {
         for (int qsign = 0; qsign < 2; ++qsign)
           printf("metric %d dim %4d pattern %d query %s: max observed / claimed = %.4f\n", metric, dim, pattern, qsign ? "negative" : "mixed   ",
                  run(metric, dim, pattern, qsign, 31u * dim + 7u * pattern + metric));
+  for (int dim : {100, 768})
+    for (int qexp : {-40, 30, 40, 46})
+      printf("metric 0 dim %4d queries x 2^%d: max observed / claimed = %.4f\n", dim, qexp, run(0, dim, 0, 0, 29u * dim + qexp, qexp));
   // outside the model: a non-finite or huge query element, a cosine shard with a zero row, scales outside f32
   std::vector<float> q(256, 1.f);
   q[3] = INFINITY;

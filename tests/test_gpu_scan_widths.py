@@ -224,14 +224,19 @@ def _probe_ratio(idx, family, q, metric, exact, live, what, fails):
     return worst
 
 
+def _parity(got, ref, what, fails):
+    """counts, ids and distance bits of a search are the oracle's"""
+    _check(fails, np.array_equal(got[2], ref[2]), what + ": counts differ from the oracle's")
+    _check(fails, np.array_equal(got[0], ref[0]), what + ": ids differ from the oracle's")
+    _check(fails, np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), what + ": distance bits differ from the oracle's")
+
+
 def _search(idx, family, qs, ref, what, fails):
     """Check (a)."""
     f0, i0, c0 = idx.scan_f16_stats(), idx.scan_i8_stats(), idx.counters()
     got = idx.search(qs, K)
     f1, i1, c1 = idx.scan_f16_stats(), idx.scan_i8_stats(), idx.counters()
-    _check(fails, np.array_equal(got[2], ref[2]), what + ": counts differ from the oracle's")
-    _check(fails, np.array_equal(got[0], ref[0]), what + ": ids differ from the oracle's")
-    _check(fails, np.array_equal(got[1].view(np.uint64), ref[1].view(np.uint64)), what + ": distance bits differ from the oracle's")
+    _parity(got, ref, what, fails)
     _check(fails, f1["scans"] - f0["scans"] == (len(qs) if family == "fp16" else 0), "%s: fp16 scans %s -> %s" % (what, f0, f1))
     _check(fails, i1["scans"] - i0["scans"] == (len(qs) if family == "int8" else 0), "%s: int8 scans %s -> %s" % (what, i0, i1))
     _check(fails, f1["redone"] == f0["redone"] and i1["redone"] == i0["redone"], "%s: a query was redone: %s -> %s, %s -> %s" % (what, f0, f1, i0, i1))

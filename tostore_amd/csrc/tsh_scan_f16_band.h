@@ -16,6 +16,14 @@
 //   L2        twice the above; |sq_i - |v_i|^2| <= u |v_i|^2; the subtraction rounds once, u |key_i|, and so does the
 //             addition of w_i: together <= 2^-23 (3 |v_i|^2 + 4 |q| |v_i|) -- and |v_i|^2 <= max|v| |v_i|, which keeps
 //             the band linear in |v_i|
+//             The ids are the ORACLE's, which ranks by its own f64 sum S_i = fl(sum_j (q_j - v_ij)^2), taken in element
+//             order: |S_i - |q - v_i|^2| <= g |q - v_i|^2 with g = (d + 4) 2^-52 (the differences, the squares and the
+//             additions round once each; the square root behind them merges sums less than 2^-52 apart).  A key that is
+//             to bound the oracle's order has to be near S_i - |q|^2, not only near its exact value: g (|q|^2 + 2 |q|
+//             |v_i| + |v_i|^2) more.  Nothing beside 2^-11 |q| |v_i| while |q| < 2^30 |v_i|; with queries 2^40 above the
+//             rows it is the whole band -- every distance of the oracle is then the same number, its ids the lowest
+//             ones, and the scan has to hand every row on (tests/test_gpu_scales.py found ids of the exact reduced
+//             ranking returned there instead)
 //   IP        the addition of w_i: <= 2^-23 |q| |v_i|
 //   cosine    divided by |v_i| >= min|v| the operand and chain terms are uniform; inv_i, the product and the addition of
 //             w round once each: 2^-21 |q| covers them (the f32 kernel's model takes the same term)
@@ -55,8 +63,9 @@ inline ScanF16Band scan_f16_band(int metric, int dim, int nch, const float *q, f
   const double mx = (double)max_norm * (1.0 + 1e-6);
   double alpha, beta;
   if (metric == 0) {
-    alpha = 2.0 * dot_rel * qn + u2 * (3.0 * mx + 4.0 * qn);
-    beta = 2.0 * dot_abs;
+    const double g64 = ((double)dim + 4.0) * 2.220446049250313e-16;  // (d + 4) 2^-52: the oracle's own f64 sum
+    alpha = 2.0 * dot_rel * qn + u2 * (3.0 * mx + 4.0 * qn) + g64 * mx;
+    beta = 2.0 * dot_abs + g64 * qn * (qn + 2.0 * mx);
   } else if (metric == 1) {
     alpha = dot_rel * qn + u2 * qn;
     beta = dot_abs;

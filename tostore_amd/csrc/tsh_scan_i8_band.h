@@ -20,6 +20,8 @@
 //             are below 2^-126 as much per element: `under`
 //   L2        twice the above; sq_i, the subtraction and the addition of -/+ w_i round once each:
 //             <= 2^-23 (3 |v_i|^2 + 4 |q| |v_i|), and |v_i|^2 <= max|v| |v_i| keeps the band linear in |v_i|
+//             and the oracle's own f64 sum of |q - v_i|^2, which decides the ids: g (|q|^2 + 2 |q| |v_i| + |v_i|^2),
+//             g = (d + 4) 2^-52 (tsh_scan_f16_band.h)
 //   IP        the addition of -/+ w_i: <= 2^-23 |q| |v_i|
 //   cosine    dot's error divided by |v_i|; inv_i, the product and the addition round once each: 2^-21 |q| covers them
 // so that |key_i - exact_i| <= w_i with
@@ -68,9 +70,10 @@ inline ScanI8Band scan_i8_band(int metric, int dim, int nch, const float *q, flo
   const double mx = (double)max_norm * (1.0 + 1e-6);
   double a_s, a_v, beta;
   if (metric == 0) {
+    const double g64 = ((double)dim + 4.0) * 2.220446049250313e-16;  // (d + 4) 2^-52: the oracle's own f64 sum
     a_s = 2.0 * kap * q1;
-    a_v = u2 * (3.0 * mx + 4.0 * qn);
-    beta = 2.0 * under;
+    a_v = u2 * (3.0 * mx + 4.0 * qn) + g64 * mx;
+    beta = 2.0 * under + g64 * qn * (qn + 2.0 * mx);
   } else if (metric == 1) {
     a_s = kap * q1;
     a_v = u2 * qn;
