@@ -58,6 +58,7 @@ extern "C" {
 /*    Additive since, same version, continued: tsh_search_grouped_rows, tsh_search_grouped_rows_stats. */
 /*    Additive since, same version, continued: tsh_attr_create, tsh_attr_set, tsh_attr_destroy, tsh_mask_create_range,
  *    tsh_mask_read. */
+/*    Additive since, same version, continued: tsh_mask_create_where (tsh_where_term, TSH_TERM_*, TSH_WHERE_MAX_*). */
 
 /* status codes */
 #define TSH_OK 0
@@ -364,7 +365,8 @@ int32_t tsh_search_submit_masked(tsh_index *idx, const float *query, int32_t k, 
  *   is given -- W is with's bitmap, zero-extended to the current rows.  So a NULL row, or a row beyond the column, is
  *   kept by no term, negated or not (`with` under OR can still keep it); lo > hi is the empty range: nothing without
  *   negate, every non-NULL row with it.  The answer is exact: NumPy on the host is the specification.  Conjunctions,
- *   IN-lists and NOT are chains of calls; each returns a new handle and the caller destroys the intermediates.  `with`
+ *   IN-lists and NOT are chains of calls (or one tsh_mask_create_where, below); each returns a new handle and the
+ *   caller destroys the intermediates.  `with`
  *   may be any handle of the same index, made from a bitmap or from a range, and is left as it was.
  *   The handle is a SNAPSHOT: a later tsh_attr_set or tsh_attr_destroy does not change it, and rows appended later are
  *   not kept -- after a rebuild for a grown shard it keeps exactly the rows it kept before (the handle contract above).
@@ -390,7 +392,7 @@ int32_t tsh_search_submit_masked(tsh_index *idx, const float *query, int32_t k, 
  *   launch of its own: folding it into the range kernel would save under a tenth of the call.
  * The attribute handle is a tsh_attr * (typedef below) and travels as `void *`, tsh_attr_create's `out` -- the address
  *   of the caller's tsh_attr * -- too, exactly as a tsh_groups * does (see tsh_groups_create below).
- * Not here: string or multi-valued attributes; several terms in one launch; a predicate evaluated inside the scan
+ * Not here: string or multi-valued attributes; a predicate evaluated inside the scan
  *   kernels without a handle; a column that follows appends on its own; collective (sharded) creation -- every rank
  *   makes its own handle from its own column, as with bitmaps. */
 #define TSH_ATTR_NULL INT64_MIN
@@ -403,6 +405,62 @@ int32_t tsh_attr_destroy(void *attr);
 int32_t tsh_mask_create_range(tsh_index *idx, void *attr, int64_t lo, int64_t hi, int32_t negate, tsh_mask *with,
                               int32_t combine, tsh_mask **out);
 int32_t tsh_mask_read(tsh_mask *mask, uint8_t *out_bits, int64_t n_bytes);
+
+/* ---- a whole WHERE clause in one launch (additive since ABI 5) --------------------------------------------------------
+ * A real WHERE is not one term: `tenant = 7 AND ts BETWEEN a AND b AND NOT flag = 1`, `category IN (3, 5, 8, 13, ...)`.
+ * As a chain of tsh_mask_create_range calls every term, and every value of an IN-list, pays a whole call: a new handle
+ * with its device buffers, a launch, the copy of the words back, the host prefix, the list kernels and their
+ * synchronise, the un-slicing -- for handles nobody looks at.  tsh_mask_create_where evaluates the clause in ONE launch
+ * and one finish per shard (W2 mask_where_kernel, tostore_amd/csrc/tsh_where.hip.h, planned by tsh_where_plan.h): each
+ * distinct column is read once per row however many terms name it, and an IN-list is a sorted set in LDS that a lane
+ * searches in at most 12 steps, not n equality terms.  The result is an ordinary tsh_mask.
+ *
+ * terms: n_terms tsh_where_term records (the array travels as `const void *`, as tsh_attr_create's out does).
+ *   A term keeps row i iff  v[i] != TSH_ATTR_NULL  and  hit != (negate != 0),  v the term's column: for TSH_TERM_RANGE
+ *   hit is lo <= v <= hi (set / n_set are not read, but must be well-formed); for TSH_TERM_IN hit is v in
+ *   set[0, n_set) (lo / hi are not read).  Rows at or beyond the column read as NULL; a NULL row is kept by no term,
+ *   negated or not.  The set's values come in any order, duplicates allowed; a TSH_ATTR_NULL among them is ignored;
+ *   n_set == 0 is the empty set and lo > hi the empty range: nothing plain, every non-NULL row negated.  The library
+ *   copies the sets: they need only live for the call.
+ *   Terms of equal `clause` are OR-ed, and the clauses AND-ed; clause numbers start at 0 and never decrease or skip a
+ *   number along the array.  If `with` is given the result is then and-ed / or-ed with its bitmap, zero-extended to the
+ *   current rows, exactly as by tsh_mask_create_range; a call of one range term gives that entry's handle bit for bit.
+ *   Limits: TSH_WHERE_MAX_TERMS terms, TSH_WHERE_MAX_COLUMNS distinct attribute handles, TSH_WHERE_MAX_SET_VALUES set
+ *   values -- every IN term's own distinct non-NULL values, summed over the call.  Anything larger is written as
+ *   chained calls through `with`.
+ *   Snapshot, tsh_mask_read, rebuilds after appends, tombstones, quarantined rows, several devices and shard handles
+ *   with global ids: as for a range-made handle.
+ *   TSH_E_BAD_ARG (each clears *out, each answered before any device work): a NULL idx, terms or out; n_terms < 1 or
+ *   > TSH_WHERE_MAX_TERMS; a NULL attr, or one made for another index, or orphaned; a `with` of another index; combine
+ *   neither TSH_MASK_AND nor TSH_MASK_OR, even with with == NULL; a kind that is neither constant; reserved != 0;
+ *   n_set < 0; a NULL set with n_set > 0; more than TSH_WHERE_MAX_COLUMNS distinct handles; more than
+ *   TSH_WHERE_MAX_SET_VALUES set values; clause numbers out of order.
+ * Threads: any number of calls may share attribute handles; a call takes every distinct handle's use lock shared, in
+ *   the order of the handles' addresses, so two calls naming the same handles in opposite orders cannot deadlock against
+ *   a waiting tsh_attr_set.
+ * Cost, measured on 1 M x 768, L2, k = 100 ("A whole clause in one launch"; profiles/mask_where_terms_ab.json,
+ *   written by tools/ab_mask_where_terms.py), medians by the host clock, the chain of tsh_mask_create_range calls with its
+ *   intermediates destroyed against the one call: `tenant = 7 AND ts BETWEEN a AND b AND NOT flag = 1` (three calls) 241
+ *   -> 88 us; `tenant IN (16 values)` (sixteen calls) 945 -> 58 us; `tenant IN (1024 values)` against the host route
+ *   (NumPy isin, packbits, tsh_mask_create) 2552 -> 65 us.  A lone query including make and destroy: 292 -> 136, 1046 ->
+ *   156 and 2709 -> 157 us.  The kernel runs 8.8 us on average over the three (W1 6.7); the call costs about one
+ *   tsh_mask_create_range. */
+#define TSH_TERM_RANGE 0
+#define TSH_TERM_IN 1
+#define TSH_WHERE_MAX_TERMS 32
+#define TSH_WHERE_MAX_COLUMNS 8     /* distinct attribute handles in one call */
+#define TSH_WHERE_MAX_SET_VALUES 4096 /* all IN terms of one call together, after the library's sort + dedupe */
+typedef struct tsh_where_term {
+  void *attr;         /* tsh_attr * of the same index */
+  int64_t lo, hi;     /* TSH_TERM_RANGE */
+  const int64_t *set; /* TSH_TERM_IN: n_set values, any order, duplicates allowed; may be NULL iff n_set == 0 */
+  int64_t n_set;
+  int32_t kind, negate;
+  int32_t clause;     /* terms of equal clause are OR-ed; the clauses are AND-ed */
+  int32_t reserved;   /* 0 */
+} tsh_where_term;
+int32_t tsh_mask_create_where(tsh_index *idx, const void *terms, int32_t n_terms, tsh_mask *with, int32_t combine,
+                              tsh_mask **out);
 
 /* Asynchronous form of a single-query tsh_search, for callers that keep several
  * independent queries in flight (the reference serves concurrent vectorSearch

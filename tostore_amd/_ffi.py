@@ -32,6 +32,8 @@ ABI_VERSION = 5
 METRIC_L2, METRIC_IP, METRIC_COSINE = 0, 1, 2
 TSH_ATTR_NULL = -(1 << 63)  # an attribute column's "no value" (tsh_attr_create)
 TSH_MASK_AND, TSH_MASK_OR = 0, 1
+TSH_TERM_RANGE, TSH_TERM_IN = 0, 1  # tsh_where_term.kind (tsh_mask_create_where)
+TSH_WHERE_MAX_TERMS, TSH_WHERE_MAX_COLUMNS, TSH_WHERE_MAX_SET_VALUES = 32, 8, 4096
 
 c_i32, c_i64, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 p_f32 = ctypes.POINTER(ctypes.c_float)
@@ -75,6 +77,14 @@ class TshCommTimeline(ctypes.Structure):
     ]
 
 
+class TshWhereTerm(ctypes.Structure):
+    """tsh_where_term: one term of a tsh_mask_create_where call (the array goes in as void *)."""
+    _fields_ = [
+        ("attr", p_void), ("lo", c_i64), ("hi", c_i64), ("set", p_i64), ("n_set", c_i64),
+        ("kind", c_i32), ("negate", c_i32), ("clause", c_i32), ("reserved", c_i32),
+    ]
+
+
 # every symbol include/tostore_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "tsh_abi_version": (c_i32, []),
@@ -104,6 +114,7 @@ SIGNATURES = {
     "tsh_attr_destroy": (c_i32, [p_void]),
     "tsh_mask_create_range": (c_i32, [p_void, p_void, c_i64, c_i64, c_i32, p_void, c_i32, ctypes.POINTER(p_void)]),
     "tsh_mask_read": (c_i32, [p_void, p_u8, c_i64]),
+    "tsh_mask_create_where": (c_i32, [p_void, p_void, c_i32, p_void, c_i32, ctypes.POINTER(p_void)]),  # (terms: TshWhereTerm[])
     "tsh_search_masked": (c_i32, [p_void, p_f32, c_i32, c_i32, c_f64, p_void, p_i64, p_f64, p_i32]),
     "tsh_search_submit_masked": (c_i32, [p_void, p_f32, c_i32, p_void, p_i32]),
     "tsh_max_inflight": (c_i32, []),

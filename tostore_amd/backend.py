@@ -68,6 +68,40 @@ class HipMask:
         index._live_masks().add(self)
         return self
 
+    @classmethod
+    def _where_clauses(cls, index: "HipVectorIndex", clauses, with_mask, combine) -> "HipMask":
+        """A handle made on the device from a whole clause in one launch (`tsh_mask_create_where`)."""
+        ops = {"and": _ffi.TSH_MASK_AND, "or": _ffi.TSH_MASK_OR, _ffi.TSH_MASK_AND: _ffi.TSH_MASK_AND, _ffi.TSH_MASK_OR: _ffi.TSH_MASK_OR}
+        if combine not in ops:
+            raise ValueError("combine is 'and' or 'or'")
+        flat = [(c, t) for c, clause in enumerate(clauses) for t in clause]
+        if any(len(clause) == 0 for clause in clauses):
+            raise ValueError("an empty clause: every clause is the OR of at least one term")
+        terms = (_ffi.TshWhereTerm * max(len(flat), 1))()
+        sets = []  # (the IN terms' arrays: alive until the call returns; the library copies them)
+        for rec, (c, t) in zip(terms, flat):
+            if not isinstance(t, (WhereRange, WhereIn)):
+                raise TypeError("a term is a WhereRange or a WhereIn")
+            # (a closed attr raises here: NULL would read as "no attr")
+            rec.attr = t.attr.handle()
+            rec.negate, rec.clause, rec.reserved = (1 if t.negate else 0), c, 0
+            if isinstance(t, WhereIn):
+                v = np.ascontiguousarray(t.values, dtype=np.int64).reshape(-1)
+                sets.append(v)
+                rec.kind, rec.n_set = _ffi.TSH_TERM_IN, v.shape[0]
+                rec.set = v.ctypes.data_as(_ffi.p_i64) if v.shape[0] else None
+            else:
+                rec.kind, rec.lo, rec.hi = _ffi.TSH_TERM_RANGE, int(t.lo), int(t.hi)
+        w = with_mask.handle() if with_mask is not None else None
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.index = index
+        _ffi.check(_ffi.lib().tsh_mask_create_where(index._h, ctypes.cast(terms, _ffi.p_void), len(flat), w, ops[combine],
+                                                    ctypes.byref(self._h)))
+        del sets
+        index._live_masks().add(self)
+        return self
+
     def handle(self):
         """The `tsh_mask*` to pass to the library; ValueError once the mask (or its index) was closed."""
         if not self._h:
@@ -161,6 +195,26 @@ class HipGroups:
 
 
 ATTR_NULL = _ffi.TSH_ATTR_NULL
+
+
+@dataclass
+class WhereRange:
+    """A term of `HipVectorIndex.make_mask_clauses`: keeps the rows whose `attr` is not NULL and for which
+    (lo <= value <= hi) != negate.  lo > hi is the empty range."""
+    attr: "HipAttr"
+    lo: int
+    hi: int
+    negate: bool = False
+
+
+@dataclass
+class WhereIn:
+    """A term of `HipVectorIndex.make_mask_clauses`: keeps the rows whose `attr` is not NULL and for which
+    (value in values) != negate.  `values` (int64) come in any order, duplicates allowed, an ATTR_NULL among them is
+    ignored; no values: the empty set."""
+    attr: "HipAttr"
+    values: Sequence[int]
+    negate: bool = False
 
 
 def f64_order_key(a) -> np.ndarray:
@@ -276,6 +330,15 @@ class HipVectorIndex:
         empty range.  Conjunctions, IN-lists and NOT are chains of calls; close the intermediates.  A snapshot: later
         `attr.set()` calls and appends do not change it."""
         return HipMask._where(self, attr, lo, hi, negate, with_mask, combine)
+
+    def make_mask_clauses(self, clauses, with_mask: Optional["HipMask"] = None, combine="and") -> "HipMask":
+        """A mask handle made ON the device from a whole WHERE in one launch (`tsh_mask_create_where`): `clauses` is a list
+        of clauses, each a list of `WhereRange` / `WhereIn` terms; a clause is the OR of its terms, the result the AND of
+        the clauses, and-ed / or-ed (`combine`) with `with_mask` when one is given.  `tenant = 7 AND ts BETWEEN a AND b AND
+        NOT flag = 1` is `[[WhereRange(t, 7, 7)], [WhereRange(ts, a, b)], [WhereRange(f, 1, 1, negate=True)]]`.  At most 32
+        terms over 8 attributes and 4096 set values in one call; more is chained through `with_mask`.  A snapshot, as
+        `make_mask_where`'s."""
+        return HipMask._where_clauses(self, clauses, with_mask, combine)
 
     def _live_masks(self) -> "weakref.WeakSet":
         """The masks and groups handles made for this index and not yet closed: close() closes them before it destroys

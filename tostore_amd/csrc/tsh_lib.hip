@@ -2756,7 +2756,7 @@ struct tsh_groups {
 struct tsh_attr {
   tsh_index *idx = nullptr;     // nullptr: orphaned -- its index was destroyed first (parts freed then)
   std::vector<int64_t> values;  // the caller's column by GLOBAL row id (its own copy: the parts are sliced from it)
-  std::shared_mutex use_mu;     // tsh_mask_create_range: shared, for the whole call; tsh_attr_set: exclusive
+  std::shared_mutex use_mu;     // tsh_mask_create_range / _where: shared, for the whole call; tsh_attr_set: exclusive
   std::mutex mu;                // builds / rebuilds of the parts
   std::vector<std::unique_ptr<AttrPart>> parts;  // one per shard of the index
 };
@@ -3028,6 +3028,47 @@ int mask_range_part(MaskPart *p, Shard *s, const AttrPart *ap, int64_t lo, int64
     // (wp was built for the same rows: n_tiles words, the bits at or past the last row 0)
     mask_range_kernel<<<where_grid(n_tiles), WHERE_BLOCK, 0, st>>>(ap->d_vals, rows, n_tiles, lo, hi, negate ? 1 : 0,
                                                                    wp ? wp->d_words : nullptr, combine, p->d_words);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return mask_finish_part(p, s, rows, n_tiles);
+}
+
+// ... and the same for a whole clause (tsh_mask_create_where): one launch of mask_where_kernel over the shard's slices of
+// the plan's columns (aps[c] for plan.columns[c]), one copy of the words back, one mask_finish_part.  The plan's sets go
+// up in one copy ahead of the launch, into the tail of the part's own word allocation (both are 8-byte entries; the
+// part is new, so the allocation is made here anyway): a call without IN terms stages nothing and allocates no more
+// than the range entry does.  plan.set outlives the synchronise below.  Locks as for mask_range_part, every column's
+// use_mu shared
+int mask_where_part(MaskPart *p, Shard *s, const WherePlan &plan, const AttrPart *const *aps, const MaskPart *wp,
+                    int32_t combine) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  const int64_t rows = s->rows;
+  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
+  const int32_t n_set = (int32_t)plan.set.size();
+  try {
+    p->h_words.assign((size_t)n_tiles, 0);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %d mask words", n_tiles);
+  }
+  int rc = mask_reserve_words(p, n_tiles + (n_tiles > 0 ? n_set : 0));
+  if (rc) return rc;
+  if (n_tiles > 0) {
+    hipStream_t st = s->aux_stream;
+    WhereArgs a{};
+    for (int c = 0; c < WHERE_MAX_COLUMNS; ++c) a.cols[c] = c < plan.n_cols ? aps[c]->d_vals : nullptr;
+    memcpy(a.terms, plan.terms, sizeof(a.terms[0]) * (size_t)plan.n_terms);
+    a.n_terms = plan.n_terms;
+    a.n_cols = plan.n_cols;
+    a.n_set = n_set;
+    a.combine = combine;
+    int64_t *d_set = reinterpret_cast<int64_t *>(p->d_words + n_tiles);
+    if (n_set > 0) HIPCHK(hipMemcpyAsync(d_set, plan.set.data(), (size_t)n_set * 8, hipMemcpyHostToDevice, st));
+    // (wp was built for the same rows: n_tiles words, the bits at or past the last row 0)
+    mask_where_kernel<<<where_grid(n_tiles), WHERE_BLOCK, (size_t)n_set * 8, st>>>(a, rows, n_tiles, d_set,
+                                                                                   wp ? wp->d_words : nullptr, p->d_words);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -4092,6 +4133,96 @@ int32_t tsh_mask_create_range(tsh_index *idx, void *attr_p, int64_t lo, int64_t 
       if (rc) break;
       // the handle's GLOBAL bitmap, as a bitmap-made handle holds it: what a rebuild after an append slices (the rows it
       // keeps then are the rows it keeps now) and what tsh_mask_read copies
+      try {
+        const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
+        if (m->bits.size() < need) m->bits.resize(need, 0);
+      } catch (...) {
+        rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
+        break;
+      }
+      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
+    }
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    for (auto &p : m->parts) mask_part_free(p.get());
+    g_err = keep;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->masks.push_back(m.get());
+  }
+  *out = m.release();
+  return TSH_OK;
+}
+
+// A whole WHERE clause in one launch and one finish per shard (tsh_where_plan.h plans it, W2 of tsh_where.hip.h runs it).
+// Modelled on tsh_mask_create_range line for line; what differs is the plan in front and one attr_part per distinct
+// column.  Everything that can be refused is refused before any device work.  (terms travels as void *: see the header)
+int32_t tsh_mask_create_where(tsh_index *idx, const void *terms_p, int32_t n_terms, tsh_mask *with, int32_t combine,
+                              tsh_mask **out) {
+  const tsh_where_term *terms = static_cast<const tsh_where_term *>(terms_p);
+  if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (combine != TSH_MASK_AND && combine != TSH_MASK_OR) return set_err(TSH_E_BAD_ARG, "combine %d is neither TSH_MASK_AND nor TSH_MASK_OR", combine);
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (!terms) return set_err(TSH_E_BAD_ARG, "terms is NULL");
+  if (n_terms < 1 || n_terms > TSH_WHERE_MAX_TERMS) return set_err(TSH_E_BAD_ARG, "n_terms %d is not in 1 .. TSH_WHERE_MAX_TERMS", n_terms);
+  WhereTermIn in[WHERE_MAX_TERMS];
+  for (int32_t t = 0; t < n_terms; ++t) {
+    if (terms[t].reserved != 0) return set_err(TSH_E_BAD_ARG, "term %d: reserved is not 0", t);
+    in[t].column = terms[t].attr;
+    in[t].lo = terms[t].lo;
+    in[t].hi = terms[t].hi;
+    in[t].set = terms[t].set;
+    in[t].n_set = terms[t].n_set;
+    in[t].kind = terms[t].kind;
+    in[t].negate = terms[t].negate;
+    in[t].clause = terms[t].clause;
+  }
+  WherePlan plan;
+  try {
+    if (const int e = where_plan(in, n_terms, &plan)) return set_err(TSH_E_BAD_ARG, "%s", where_plan_error(e));
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for the terms' sets");
+  }
+  tsh_attr *attrs[WHERE_MAX_COLUMNS];
+  for (int c = 0; c < plan.n_cols; ++c) {
+    attrs[c] = static_cast<tsh_attr *>(const_cast<void *>(plan.columns[c]));
+    if (attrs[c]->idx != idx) return set_err(TSH_E_BAD_ARG, "the attribute handle was made for another index (or its index was destroyed)");
+  }
+  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
+  std::unique_ptr<tsh_mask> m(new tsh_mask());
+  m->idx = idx;
+  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
+  int rc = TSH_OK;
+  {
+    // every column stays as it is until every part is made.  The handles are taken in one order, by address: two calls
+    // that name the same handles in opposite orders cannot hold one each while a tsh_attr_set waits between them.  (All
+    // given up before g_mask_mu is taken below: tsh_attr_set holds that one while it waits for these)
+    tsh_attr *order[WHERE_MAX_COLUMNS];
+    std::copy(attrs, attrs + plan.n_cols, order);
+    std::sort(order, order + plan.n_cols, std::less<tsh_attr *>());
+    std::vector<std::shared_lock<std::shared_mutex>> use;
+    use.reserve((size_t)plan.n_cols);
+    for (int c = 0; c < plan.n_cols; ++c) use.emplace_back(order[c]->use_mu);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
+      Shard *s = idx->shards[g].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      const AttrPart *aps[WHERE_MAX_COLUMNS] = {};
+      for (int c = 0; c < plan.n_cols; ++c) {
+        aps[c] = attr_part(attrs[c], g, s, &rc);
+        if (!aps[c]) break;
+      }
+      if (rc) break;
+      const MaskPart *wp = with ? mask_part(with, g, s, &rc) : nullptr;
+      if (with && !wp) break;
+      MaskPart *p = m->parts[g].get();
+      rc = mask_where_part(p, s, plan, aps, wp, combine);
+      if (rc) break;
+      // the handle's GLOBAL bitmap, as for a range-made handle
       try {
         const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
         if (m->bits.size() < need) m->bits.resize(need, 0);

@@ -79,6 +79,8 @@ typedef _MaskCreateRangeD = int Function(
     Pointer<Void>, Pointer<Void>, int, int, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
 typedef _MaskReadC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Int64);
 typedef _MaskReadD = int Function(Pointer<Void>, Pointer<Uint8>, int);
+typedef _MaskCreateWhereC = Int32 Function(Pointer<Void>, Pointer<Void>, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
+typedef _MaskCreateWhereD = int Function(Pointer<Void>, Pointer<Void>, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
 typedef _SearchMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double,
     Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, double,
@@ -381,6 +383,40 @@ final class TshNghInfo extends Struct {
   external int rowEnd;
 }
 
+/// `tsh_where_term` (include/tostore_hip.h): one term of a tsh_mask_create_where call, 56 bytes.  Field order and
+/// widths are checked against the header by tests/test_abi_mask_where_terms.py.
+final class TshWhereTerm extends Struct {
+  external Pointer<Void> attr;
+  @Int64()
+  external int lo;
+  @Int64()
+  external int hi;
+  external Pointer<Int64> set;
+  @Int64()
+  external int nSet;
+  @Int32()
+  external int kind;
+  @Int32()
+  external int negate;
+  @Int32()
+  external int clause;
+  @Int32()
+  external int reserved;
+}
+
+/// A term of [HipRowMask.whereClauses]: a range term keeps the node ids whose attribute is not NULL and for which
+/// (lo <= value <= hi) != negate; a set term ([HipWhereTerm.inSet]) those for which (value in values) != negate.
+final class HipWhereTerm {
+  final HipRowAttr attr;
+  final int lo, hi;
+  final Int64List? values;
+  final bool negate;
+  const HipWhereTerm.range(this.attr, this.lo, this.hi, {this.negate = false}) : values = null;
+  HipWhereTerm.inSet(this.attr, Int64List this.values, {this.negate = false})
+      : lo = 0,
+        hi = 0;
+}
+
 /// One device-resident copy of an NGH index's raw-vector column.
 ///
 /// Lifetime: created lazily on the first vectorSearch / writeChanges of
@@ -467,6 +503,7 @@ final class HipVectorBackend {
   static late final _AttrDestroyD _attrDestroy;
   static late final _MaskCreateRangeD _maskCreateRange;
   static late final _MaskReadD _maskRead;
+  static late final _MaskCreateWhereD _maskCreateWhere;
   static late final _SearchMaskedD _searchMasked;
   static late final _SubmitMaskedD _submitMasked;
 
@@ -578,6 +615,7 @@ final class HipVectorBackend {
       _attrDestroy = lib.lookupFunction<_AttrDestroyC, _AttrDestroyD>('tsh_attr_destroy');
       _maskCreateRange = lib.lookupFunction<_MaskCreateRangeC, _MaskCreateRangeD>('tsh_mask_create_range');
       _maskRead = lib.lookupFunction<_MaskReadC, _MaskReadD>('tsh_mask_read');
+      _maskCreateWhere = lib.lookupFunction<_MaskCreateWhereC, _MaskCreateWhereD>('tsh_mask_create_where');
       _searchMasked = lib.lookupFunction<_SearchMaskedC, _SearchMaskedD>('tsh_search_masked');
       _submitMasked =
           lib.lookupFunction<_SubmitMaskedC, _SubmitMaskedD>('tsh_search_submit_masked');
@@ -761,6 +799,78 @@ final class HipVectorBackend {
       calloc.free(out);
     }
   }
+
+  /// A mask made ON the device from a whole WHERE in one launch (tsh_mask_create_where): `clauses` is a list of clauses,
+  /// each a list of [HipWhereTerm]s; a clause is the OR of its terms and the result the AND of the clauses, and-ed (or,
+  /// with `or: true`, or-ed) with `withMask` when one is given.  At most [whereMaxTerms] terms over [whereMaxColumns]
+  /// attributes and [whereMaxSetValues] set values; more is chained through `withMask`.  A snapshot, as
+  /// [createMaskWhere]'s.  Null on any native failure; a disposed [HipRowAttr] or `withMask` is refused (null, with a
+  /// warning), never sent as NULL.
+  HipRowMask? createMaskWhereClauses(List<List<HipWhereTerm>> clauses, {HipRowMask? withMask, bool or = false}) {
+    final flat = <HipWhereTerm>[];
+    final clauseOf = <int>[];
+    for (var c = 0; c < clauses.length; c++) {
+      for (final t in clauses[c]) {
+        if (t.attr._attr == nullptr) {
+          Logger.warn('createMaskWhereClauses with a disposed HipRowAttr', label: 'HipVectorBackend');
+          return null;
+        }
+        flat.add(t);
+        clauseOf.add(c);
+      }
+    }
+    if (withMask != null && withMask._mask == nullptr) {
+      Logger.warn('createMaskWhereClauses with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    final terms = calloc<TshWhereTerm>(flat.isEmpty ? 1 : flat.length);
+    final sets = <Pointer<Int64>>[];
+    final out = calloc<Pointer<Void>>();
+    try {
+      for (var i = 0; i < flat.length; i++) {
+        final t = flat[i];
+        final rec = terms[i];
+        rec.attr = t.attr._attr;
+        rec.lo = t.lo;
+        rec.hi = t.hi;
+        rec.negate = t.negate ? 1 : 0;
+        rec.clause = clauseOf[i];
+        rec.reserved = 0;
+        final v = t.values;
+        if (v == null) {
+          rec.kind = termRange;
+          rec.set = nullptr;
+          rec.nSet = 0;
+        } else {
+          final buf = calloc<Int64>(v.isEmpty ? 1 : v.length);
+          buf.asTypedList(v.length).setAll(0, v);
+          sets.add(buf);
+          rec.kind = termIn;
+          rec.set = buf;
+          rec.nSet = v.length;
+        }
+      }
+      final rc = _maskCreateWhere(_handle, terms.cast<Void>(), flat.length, withMask?._mask ?? nullptr, or ? 1 : 0, out);
+      if (rc != 0) {
+        Logger.warn('tsh_mask_create_where failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return HipRowMask._(out.value);
+    } finally {
+      for (final s in sets) {
+        calloc.free(s);
+      }
+      calloc.free(terms);
+      calloc.free(out);
+    }
+  }
+
+  /// TSH_TERM_RANGE / TSH_TERM_IN and the limits of one tsh_mask_create_where call (include/tostore_hip.h).
+  static const int termRange = 0;
+  static const int termIn = 1;
+  static const int whereMaxTerms = 32;
+  static const int whereMaxColumns = 8;
+  static const int whereMaxSetValues = 4096;
 
   int get size => _size(_handle);
 
@@ -1989,6 +2099,11 @@ final class HipRowMask {
   static HipRowMask? where(HipVectorBackend backend, HipRowAttr attr, int lo, int hi,
           {bool negate = false, HipRowMask? withMask, bool or = false}) =>
       backend.createMaskWhere(attr, lo, hi, negate: negate, withMask: withMask, or: or);
+
+  /// [HipVectorBackend.createMaskWhereClauses] by its other name: the mask of a whole WHERE, made in one launch.
+  static HipRowMask? whereClauses(HipVectorBackend backend, List<List<HipWhereTerm>> clauses,
+          {HipRowMask? withMask, bool or = false}) =>
+      backend.createMaskWhereClauses(clauses, withMask: withMask, or: or);
 
   /// The first `nBytes` bytes of the mask's bitmap as it stands (tsh_mask_read): bit i (LSB first) = node id i, bytes
   /// past what the mask knows read 0.  Null on failure, or on a disposed mask.
