@@ -22,7 +22,7 @@ CSRC = os.path.join(_HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 OUT = os.path.join(_HERE, "libtostore_hip.so")
 _HDR = os.path.join("..", "..", "include", "tostore_hip.h")
-_KERN = ["tsh_kernels.hip.h", "tsh_block.h", "tsh_scan_tile.inc.h", "tsh_batch.hip.h", "tsh_batch_tiles.h", "tsh_launch.h", "tsh_scan_overlap.h", "tsh_scan_widths.h", _HDR]
+_KERN = ["tsh_kernels.hip.h", "tsh_block.h", "tsh_scan_tile.inc.h", "tsh_batch.hip.h", "tsh_batch_tiles.h", "tsh_launch.h", "tsh_scan_overlap.h", "tsh_scan_widths.h", "tsh_select_plan.h", _HDR]
 # translation unit -> what it includes
 UNITS = {
     "tsh_scan_tu.hip": _KERN,

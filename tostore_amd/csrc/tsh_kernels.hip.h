@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "tsh_block.h"
+#include "tsh_select_plan.h"
 
 namespace tsh {
 
@@ -614,10 +615,7 @@ struct SelectArgs {
   float w_alpha, w_beta;
 };
 
-constexpr int SEL_THREADS = 1024;   // one whole CU; tile minima stay in registers
-constexpr int SEL_VPT = 16;         // tile minima a thread keeps in registers (16384 tiles = 1M rows)
-constexpr int SEL_LIST_CAP = 4096;  // LDS lists (short list of tile minima / tile ids)
-constexpr int SEL_PREFILTER_MIN = 512;  // above this many tiles, bound the list by the thread-minima bisect first
+// (SEL_THREADS, SEL_VPT, SEL_LIST_CAP, SEL_PREFILTER_MIN and every branch condition of K2: tsh_select_plan.h)
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
@@ -781,12 +779,11 @@ __device__ __forceinline__ void select_tau(const uint32_t *gmin, int M, uint32_t
       if (it & 1) lodd = x < lodd ? x : lodd;
     }
   }
-  const bool narrow = !force_all && (uint32_t)M >= k && k <= (uint32_t)SEL_THREADS;
-  const bool groups4 = NT == 1024 && k <= 128;  // 256 group minima are plenty for small k
-  // above k = 512 the k-th of 1024 thread minima gets loose (G ln(G/(G-k)) entries below
-  // it): split every thread into its even and odd elements, 2048 groups
-  const bool groups2k = k > 512;
-  if (narrow && M > SEL_PREFILTER_MIN) {
+  const bool narrow = sel_narrow(NT, M, k, force_all);
+  const bool groups4 = sel_groups4(NT, k);  // 256 group minima are plenty for small k
+  // above k = 512 the k-th of 1024 thread minima gets loose: every thread split into its even and odd elements
+  const bool groups2k = sel_groups2k(k);
+  if (sel_prefilter(narrow, M)) {
     uint32_t m = lmin;
     if (groups4) {
       uint32_t t1 = (uint32_t)__shfl_xor((int)m, 1);
@@ -813,7 +810,7 @@ __device__ __forceinline__ void select_tau(const uint32_t *gmin, int M, uint32_t
     }
   }
   __syncthreads();
-  if (narrow && M > SEL_PREFILTER_MIN && wave == 0) {
+  if (sel_prefilter(narrow, M) && wave == 0) {
     uint32_t U;
     if (groups2k) {
       uint32_t v[2 * NT / 64];
@@ -858,9 +855,9 @@ __device__ __forceinline__ void select_tau(const uint32_t *gmin, int M, uint32_t
   if (narrow && wave == 0) {
     const uint32_t n = s.n;
     uint32_t tau;
-    if (n > SEL_LIST_CAP) {
+    if (sel_flooded(n)) {
       tau = s.U;  // ties flooded the list: U is still a valid (looser) bound
-    } else if (n <= 512) {
+    } else if (sel_short_small(n)) {
       uint32_t v[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = (uint32_t)(lane + i * 64) < n ? s.list[lane + i * 64] : KEY_DEAD;
@@ -906,7 +903,7 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
   // tile would be a hit and step (f) would bisect for the k-th key in up to 32 block-wide rounds.  The list-ordered keys
   // are one short contiguous array, every entry written (padding = KEY_DEAD): take the k-th smallest KEY directly,
   // four radix rounds by the whole workgroup.  (79 tiles, k = 100: 60 -> 25 us per query.)
-  if (a.list && !a.force_all && (uint32_t)M < k && (uint32_t)M * 64u >= k) {  // workgroup-uniform (fewer entries than k: all)
+  if (a.list && !a.force_all && sel_list_shortcut(M, k)) {  // workgroup-uniform (fewer entries than k: all)
     __shared__ RadixSelScratch s_rs;
     const uint32_t x = block_kth_radix<NT>(a.keys, (uint32_t)M * 64u, k, &s_rs);
     if (tid == 0) s_t.tau = x >= KEY_DEAD ? KEY_NAN : x;  // fewer than k live rows: every live row
@@ -934,7 +931,7 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
   }
   __syncthreads();
   const uint32_t nt = s_tiles;
-  const bool over = nt > SEL_LIST_CAP;
+  const bool over = sel_over(nt);
   constexpr int NW = SEL_THREADS / 64;
   // (e) four tiles per wave per round so their (L2-resident) key loads overlap
   // (tk: the bound the band was widened FROM -- the rows' own bands are applied against it)
@@ -979,10 +976,10 @@ __device__ __forceinline__ void select_body(const SelectArgs &a) {
   // smallest key of the shard: bisect for it (block-wide counts; keys in registers when the
   // hit tiles fit, otherwise re-read from L2) and emit again with the tight band.
   // (tau == KEY_NAN, fewer than k live tiles, is covered too: more than cand_cap >= k live keys exist)
-  if (!over && !a.force_all && first_count > (uint32_t)a.cand_cap) {
+  if (!over && !a.force_all && sel_refines(first_count, a.cand_cap)) {
     __shared__ uint32_t s_cnt[3], s_lo;
-    constexpr int RV = 16;  // tiles a wave keeps in registers
-    const bool in_regs = nt <= (uint32_t)(NW * RV);
+    constexpr int RV = SEL_REFINE_RV;  // tiles a wave keeps in registers
+    const bool in_regs = sel_refine_in_regs(NT, nt);
     uint32_t kr[RV];
     uint32_t lo = KEY_DEAD;
     if (in_regs) {

@@ -1047,19 +1047,12 @@ struct Job {
 };
 
 void launch_select(const SelectArgs &se, int32_t n_tiles, hipStream_t st) {
-  // a few hundred tiles (an index of some ten thousand rows): four waves instead of sixteen synchronise
-  // faster (10 k x 128: p50 42.8 -> 39.8 us); from a few thousand tiles on the wide workgroup wins
-  // (fewer tiles than k: the tile-minimum bound says nothing, every tile is a hit and step (f) bisects over all of
-  // them -- from registers only while they fit a workgroup's: 64 tiles for four waves, 256 for sixteen.  A list scan
-  // of a few thousand kept rows lands exactly there: 79 tiles, k = 100 took 85 us per query instead of 30)
-  const bool all_hit = n_tiles < se.k && n_tiles > 64;
-  // (a list scan's tile minima bound the k-th key loosely -- its tiles hold the kept rows in id order, every one of them
-  // a mix of near and far rows: a 1 % mask of 1 M rows is 157 tiles of which ~100 are hits, and step (f) bisects over
-  // them from registers only with sixteen waves)
-  const bool list_many_hits = se.list != nullptr && n_tiles > 64;
-  if (n_tiles <= 512 && se.k <= 256 && !all_hit && !list_many_hits) select_kernel<256, true><<<1, 256, 0, st>>>(se);
-  else if (n_tiles <= SEL_VPT * SEL_THREADS) select_kernel<SEL_THREADS, true><<<1, SEL_THREADS, 0, st>>>(se);
-  else select_kernel<SEL_THREADS, false><<<1, SEL_THREADS, 0, st>>>(se);
+  // (which of the three, and why: select_variant, tsh_select_plan.h)
+  switch (select_variant(n_tiles, se.k, se.list != nullptr)) {
+    case SEL_NT256_REGS: select_kernel<SEL_THREADS_SMALL, true><<<1, SEL_THREADS_SMALL, 0, st>>>(se); break;
+    case SEL_NT1024_REGS: select_kernel<SEL_THREADS, true><<<1, SEL_THREADS, 0, st>>>(se); break;
+    case SEL_NT1024_MEM: select_kernel<SEL_THREADS, false><<<1, SEL_THREADS, 0, st>>>(se); break;
+  }
 }
 
 // host mode: the quarantined rows' sums go to the context's pinned h_quar (the host picks the query's: Job::quar_sel)
@@ -3381,9 +3374,7 @@ int64_t tsh_candidate_block_bytes(int32_t entries) {
   return (int64_t)sizeof(BlockHeader) + (int64_t)std::max(entries, 0) * (int64_t)sizeof(BlockEntry);
 }
 int32_t tsh_default_block_entries(int32_t k) {
-  int64_t e = (int64_t)std::max(k, 1) + 156;
-  e = round_up(e, 64);
-  return (int32_t)std::min<int64_t>(e, 1 << 20);
+  return select_default_entries(k);
 }
 
 // after: a cursor per query (tsh_search_after), or none
