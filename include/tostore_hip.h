@@ -48,7 +48,7 @@ extern "C" {
  *    exchanges instead of a constant.
  *    Additive since, same version: TSH_OPT_SCAN_F16, tsh_scan_f16_stats, tsh_probe_scan_f16_keys;
  *    TSH_OPT_SCAN_F16_MASKED; TSH_OPT_SCAN_I8, tsh_scan_i8_stats, tsh_probe_scan_i8_keys; TSH_OPT_SCAN_STREAMS;
- *    TSH_OPT_SCAN_I8_MASKED; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats;
+ *    TSH_OPT_SCAN_I8_MASKED; TSH_OPT_SCAN_I4, tsh_scan_i4_stats, tsh_probe_scan_i4_keys; tsh_search_after, tsh_search_submit_after, tsh_search_after_stats;
  *    tsh_search_shard_after, tsh_search_shard_begin_after, tsh_merge_candidates_after, tsh_search_sharded_after;
  *    tsh_search_shard_masked, tsh_search_shard_begin_masked, tsh_search_sharded_masked;
  *    tsh_search_count, tsh_search_count_stats;
@@ -1039,6 +1039,14 @@ int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lo
 /* tsh_scan_i8_stats: out[0] scans over the int8 copy (dense and masked ones alike), out[1] queries redone through
  * another scan (survivor list overflow), out[2] rows converted into the copy, out[3] device bytes the copy holds. */
 int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
+/* tsh_probe_scan_i4_keys: the 4-bit first pass's (TSH_OPT_SCAN_I4 and TSH_OPT_SCAN_I8, which must both allow it: a dense
+ * L2 index) two sides of every row's ranking key, out_lower[i] <= exact key of row i <= out_upper[i] being what its band
+ * claims (single-shard indexes; rows floats each).  For the band test. */
+int32_t tsh_probe_scan_i4_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper);
+/* tsh_scan_i4_stats: out[0] scans whose 4-bit pass ran in front of the int8 scan, out[1] rows those passes left to the
+ * int8 scan (their sum), out[2] rows converted into the 4-bit plane, out[3] device bytes the plane holds, out[4] times the
+ * route was denied because too many rows survived, out[5] eligible scans a denial still covers. */
+int32_t tsh_scan_i4_stats(tsh_index *idx, int64_t *out);
 
 /* Tuning knobs (no reference counterpart).  TSH_OPT_BATCH_MIN_NQ: when tsh_search /
  * tsh_search_shard answer a multi-query call on the batched matrix-core path:
@@ -1152,6 +1160,19 @@ int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out);
  * tombstone 228.3 -> 123.7 us per query, a keep-50 % mask 123.9 -> 66.9 (pointer) and 123.2 -> 66.3 (handle) against the
  * fp16 masked scans, spread at most 2.5 %: hence 1 by default. */
 #define TSH_OPT_SCAN_I8_MASKED 13
+/* TSH_OPT_SCAN_I4 (default 1; additive since ABI 5): a 4-bit first pass in front of the coarse int8 scan of a dense L2
+ * single-query scan.  It reads a plane of the int8 copy's high nibbles -- half a byte per element -- and one float per
+ * row, bounds every row's key from below, and the int8 scan then reads only the rows whose lower bound does not exceed
+ * the k-th smallest upper bound: on corpora whose norms differ about a tenth of the rows.  0 = never; 1 = auto: L2 shards
+ * whose row store is larger than 1400 MiB (smaller ones lose: the pass has a fixed cost of three launches); 2 = every eligible scan whatever the size (tests, A/B runs).  It runs only
+ * where the dense int8 route runs (TSH_OPT_SCAN_I8) and never behind a mask, tombstones, quarantined rows or gaps, for
+ * cursor, count or grouped searches, or for inner product and cosine.  Two scans in a row that leave more than 32 % of the
+ * rows to the int8 scan keep the shard's next 256 eligible scans on the plain int8 route; repeated denials double, up to
+ * 65 536 scans (the plane -- half a byte per element -- stays resident meanwhile).  Results are identical either way; the scans count in tsh_scan_i4_stats.  Measured on one MI355X, 1 M x 768,
+ * norms U(0.5, 2), k = 100 (profiles/scan_i4_bench_ab.json): a step of bench.py 0.1138 -> 0.0927 ms, five processes a side,
+ * spreads 0.0006 and 0.0004 ms; unit-norm rows, where the pass prunes nothing and is denied after two scans: no difference.
+ * The 32 % and the 1400 MiB are measured break-evens less their spreads (tools/ab_scan_i4.py, same file).  Hence 1 by default. */
+#define TSH_OPT_SCAN_I4 14
 /* TSH_OPT_TEST_HOOKS (process-wide; idx is ignored and may be NULL): value TSH_TEST_HOOKS_MAGIC switches the
  * library's TEST hooks on, 0 off.  Only then does it read the environment variables that change what it loads or make
  * it fail on purpose -- TSH_RCCL_LIB (a stand-in for librccl: tests/fake_rccl), TSH_TEST_FAIL_ALLOC_OVER (device

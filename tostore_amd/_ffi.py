@@ -181,6 +181,8 @@ SIGNATURES = {
     "tsh_scan_f16_stats": (c_i32, [p_void, p_i64]),
     "tsh_probe_scan_i8_keys": (c_i32, [p_void, p_f32, p_f32, p_f32]),
     "tsh_scan_i8_stats": (c_i32, [p_void, p_i64]),
+    "tsh_probe_scan_i4_keys": (c_i32, [p_void, p_f32, p_f32, p_f32]),
+    "tsh_scan_i4_stats": (c_i32, [p_void, p_i64]),
     "tsh_index_set_option": (c_i32, [p_void, c_i32, c_i64]),
 }
 
@@ -230,6 +232,7 @@ TSH_OPT_SCAN_F16_MASKED = 9
 TSH_OPT_SCAN_I8 = 10
 TSH_OPT_SCAN_STREAMS = 12
 TSH_OPT_SCAN_I8_MASKED = 13
+TSH_OPT_SCAN_I4 = 14
 TSH_OPT_TEST_HOOKS = 1000
 TSH_TEST_HOOKS_MAGIC = 0x7465737468
 

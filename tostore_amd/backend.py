@@ -766,6 +766,29 @@ class HipVectorIndex:
         set_scan_i8(2) does not force this one.  Results are identical."""
         _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_I8_MASKED, int(mode)))
 
+    def set_scan_i4(self, mode: int) -> None:
+        """A 4-bit first pass in front of the dense L2 int8 scan (half a byte per element; the int8 scan then reads only the
+        rows it could not rule out): 0 never, 1 auto (default: L2 shards whose row store is larger than 1400 MiB), 2 every
+        eligible scan whatever the size.  Denied for a while when too many rows survive it.  Results are identical."""
+        _ffi.check(_ffi.lib().tsh_index_set_option(self._h, _ffi.TSH_OPT_SCAN_I4, int(mode)))
+
+    def scan_i4_stats(self) -> dict:
+        """The 4-bit pass's counters: scans it ran in, rows it left to the int8 scan, rows converted, plane bytes, times
+        the route was denied, eligible scans a denial still covers."""
+        out = (ctypes.c_int64 * 6)()
+        _ffi.check(_ffi.lib().tsh_scan_i4_stats(self._h, out))
+        return {"scans": out[0], "survivors": out[1], "rows_converted": out[2], "copy_bytes": out[3], "denials": out[4],
+                "denied_left": out[5]}
+
+    def probe_scan_i4_keys(self, query):
+        """(lower side, upper side) of every row's key from the 4-bit scan kernel: tests of the error model."""
+        q = _f32c(query).reshape(-1)
+        lo = np.empty(self.size - self.row_base, dtype=np.float32)
+        up = np.empty(self.size - self.row_base, dtype=np.float32)
+        _ffi.check(_ffi.lib().tsh_probe_scan_i4_keys(self._h, q.ctypes.data_as(_ffi.p_f32), lo.ctypes.data_as(_ffi.p_f32),
+                                                     up.ctypes.data_as(_ffi.p_f32)))
+        return lo, up
+
     def set_scan_streams(self, mode: int) -> None:
         """On how many streams the scans of overlapping single queries run: 0 by the scan's drain share (default: two for
         scans of fewer than 6144 tiles and for a big shard's scans over its int8 or fp16 copy), 1 always one, 2 two

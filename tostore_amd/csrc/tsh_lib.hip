@@ -50,6 +50,7 @@
 #include "tsh_scan_f16_band.h"
 #include "tsh_scan_i8.hip.h"
 #include "tsh_scan_i8_band.h"
+#include "tsh_scan_i4.hip.h"
 #include "tsh_where.hip.h"
 
 using namespace tsh;
@@ -137,6 +138,12 @@ struct Ctx {
   int64_t x_cap = 0;
   // the coarse int8 scan's tail (tsh_scan_i8.hip.h): [tau, survivor total] and the survivor list of I8_LIST_CAP ids
   uint32_t *d_i8 = nullptr, *d_i8_list = nullptr;
+  // the 4-bit first pass in front of it (tsh_scan_i4.hip.h): A's lower sides and tile minima, W's mask words, tau,
+  // and, pinned + mapped, the survivors' total as the host reads it
+  uint32_t *d_i4_keys = nullptr, *d_i4_gmin = nullptr, *d_i4_ctl = nullptr;
+  uint64_t *d_i4_mask = nullptr;
+  uint32_t *h_i4 = nullptr, *h_i4_dev = nullptr;
+  int64_t i4_tiles_cap = 0;
   // cursor searches (tsh_after.hip.h): the side list of the rows the floor pass could not decide, its two count words
   // (side_flip: the one the next cursor job counts in -- the job before it left it at zero) and, pinned + mapped, their
   // count and entries: [0].id = count, [1 ..] the entries.  Count jobs (tsh_count.hip.h) use the same list and words, and a
@@ -243,6 +250,39 @@ struct RowCopyI8 : RowCopy {
   int mode_masked = TSH_SCAN_I8_MASKED_DEFAULT;  // TSH_OPT_SCAN_I8_MASKED: the same three for tile scans behind a mask, tombstones,
                                                  // quarantined rows or gaps (none of them while mode == 0)
 };
+// The 4-bit plane (tsh_scan_i4.hip.h): groups x 16 bytes per row, tile-blocked, and behind the rows, in the same
+// allocation, rho per row.  Made from the int8 copy.  Its route is denied by the survivors' share, not by overflows:
+// two scans in a row that keep more than SCAN_I4_MAX_SHARE of the rows and the shard's next `deny_len` eligible scans take
+// the plain int8 route; a denial that follows the previous one's end directly doubles, up to SCAN_I4_DENY_CAP scans.
+#ifndef TSH_SCAN_I4_MAX_SHARE
+// measured break-even 0.336 less the larger spread's 0.012 (profiles/scan_i4_bench_ab.json; tools/ab_scan_i4.py)
+#define TSH_SCAN_I4_MAX_SHARE 0.32  // (A/B builds: -DTSH_SCAN_I4_MAX_SHARE=2.0 never denies)
+#endif
+#ifndef TSH_SCAN_I4_MIN_BYTES
+// auto: row stores above this take the route.  T, W and three more launches are a fixed cost in front of a scan that saves
+// bytes: at 768 f32 the route loses at 125 k and 250 k rows (27.6 -> 43.4, 32.3 -> 42.6 us per query), breaks even near
+// 410 k and wins at 500 k (1.54 GB: 59.6 -> 53.9) and 1 M (113.9 -> 90.0)
+#define TSH_SCAN_I4_MIN_BYTES (1400ll << 20)
+#endif
+constexpr double SCAN_I4_MAX_SHARE = TSH_SCAN_I4_MAX_SHARE;
+constexpr int64_t SCAN_I4_MIN_BYTES = TSH_SCAN_I4_MIN_BYTES;
+constexpr int SCAN_I4_DENY_CAP = 1 << 16;
+struct RowCopyI4 : RowCopy {
+  using RowCopy::RowCopy;
+  std::atomic<int64_t> survivors{0};   // rows A left to B, over all scans
+  std::atomic<int64_t> denials{0};     // times the route was denied
+  std::atomic<int> deny_len{SCAN_ROUTE_DENIED_SCANS};
+  std::atomic<bool> probation{false};  // a denial has run out and no scan under the share was seen since: another denial now doubles
+  // an eligible scan uses up a denial, if any are left; the one that uses up the last starts the probation
+  bool take_denial() {
+    if (!route.take_denial()) return false;
+    if (route.denied.load() <= 0) probation.store(true);
+    return true;
+  }
+};
+inline float *rows4_rho(const RowCopy &c, int groups) {
+  return c.d ? reinterpret_cast<float *>(static_cast<uint8_t *>(c.d) + c.cap * groups * 16) : nullptr;
+}
 inline float *rows8_scales(const RowCopy &c, int64_t ld) {
   return c.d ? reinterpret_cast<float *>(static_cast<uint8_t *>(c.d) + c.cap * ld) : nullptr;
 }
@@ -392,6 +432,10 @@ struct Shard {
 #endif
   RowCopyF16 rows16{1};
   RowCopyI8 rows8{TSH_SCAN_I8_DEFAULT};
+#ifndef TSH_SCAN_I4_DEFAULT
+#define TSH_SCAN_I4_DEFAULT 1  // (A/B builds: -DTSH_SCAN_I4_DEFAULT=0)
+#endif
+  RowCopyI4 rows4{TSH_SCAN_I4_DEFAULT};  // TSH_OPT_SCAN_I4: the 4-bit first pass in front of a dense L2 int8 scan
   std::mutex row_copies_mu;
   RowCopy *row_copy(RowStore st) {
     if (st == RowStore::F16) return &rows16;
@@ -591,6 +635,7 @@ int shard_reserve(Shard *s, int64_t want_rows) {
   if (s->d_live) hipFree(s->d_live);
   s->rows16.release(s);
   s->rows8.release(s);
+  s->rows4.release(s);
   s->d_rows = nrows;
   s->d_inv_norm = ninv;
   s->d_sqnorm = nsq;
@@ -689,6 +734,7 @@ int shard_append(Shard *s, int64_t first, int64_t n, const float *src, bool src_
   s->split_valid = std::min(s->split_valid, first);  // overwritten / new rows need re-splitting
   s->rows16.overwritten(first);
   s->rows8.overwritten(first);
+  s->rows4.overwritten(first);
   if (first < s->hub_rows_built) s->hub_rows_built = -1;  // (an overwritten row may be a hub row: its copy is stale)
   return TSH_OK;
 }
@@ -719,6 +765,11 @@ void ctx_free_all(Ctx *c) {
   hipFree(c->d_xpick);
   hipFree(c->d_i8);
   hipFree(c->d_i8_list);
+  hipFree(c->d_i4_keys);
+  hipFree(c->d_i4_gmin);
+  hipFree(c->d_i4_ctl);
+  hipFree(c->d_i4_mask);
+  hipHostFree(c->h_i4);
   hipFree(c->d_side_rows);
   hipFree(c->d_side_cnt);
   hipHostFree(c->h_side);
@@ -900,6 +951,8 @@ struct Route {
   ScanF16Band fb;
   bool i8_eligible = false;  // the coarse int8 scan + the exact path over its survivors may run (the caller still owes
   ScanI8Band ib;             // the denial counter and rows8_ensure); `picked`: E2' behind it instead of E2
+  bool i4_eligible = false;  // ... with the 4-bit pass in front of it (dense L2 only; the caller owes its denial counter,
+  ScanI4Band i4b;            // rows4_ensure and the context's buffers)
 };
 
 // A selective caller mask as a list: local ids of the kept rows, ascending, padded with 0xFFFFFFFF to whole tiles of
@@ -1000,6 +1053,7 @@ struct Job {
                                 // header over old entries); it keeps FLAG_LIST_OVERFLOW, which every rank answers by
                                 // redoing the group with larger blocks, not ahead
   bool no_i8 = false;  // enqueued as the redo of an int8 scan (JobReq::no_i8): a further redo stays off that route
+  bool i4 = false;     // store == I8 and the 4-bit pass ran in front of the int8 scan, which then read rows behind its mask
   RowStore store = RowStore::F32;  // the copy of the rows its tile scan read (I8: survivors through the exact path).
                                    // A list overflow of an F16 / I8 scan is redone through another scan (redo_overflowed_scan),
   std::vector<float> redo_q;  // from this copy of the query, with this tag
@@ -1387,6 +1441,89 @@ bool scan_i8_applies(const Shard *s, bool masked, int32_t k, int32_t entries) {
   return true;
 }
 
+// The 4-bit plane and rho, from the int8 copy -- which the caller has just brought up to the shard's rows (rows8_ensure)
+bool rows4_ensure(Shard *s, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(s->row_copies_mu);
+  const int groups = scan_i4_groups(s->ld);
+  if (!s->rows8.d || s->rows8.cap != s->cap || s->rows8.valid != s->rows) return false;
+  return row_copy_ensure(s, s->rows4, s->cap * groups * 16 + s->cap * 4, false, st, [&](int64_t r0, int64_t r1) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((r1 - r0 + 3) / 4, 16384));
+    rows4_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, static_cast<const uint8_t *>(s->rows8.d), rows8_scales(s->rows8, s->ld),
+                                               static_cast<uint32_t *>(s->rows4.d), rows4_rho(s->rows4, groups), s->ld, groups, r0, r1);
+  });
+}
+
+// Could a scan that takes the coarse int8 route (scan_i8_applies said so) run the 4-bit pass in front of it?  Dense L2
+// scans only: behind a mask, tombstones or gaps, and for inner product and cosine, the int8 scan runs alone.
+bool scan_i4_applies(const Shard *s, bool masked) {
+  const int mode = s->rows4.mode;
+  if (mode == 0 || s->rows4.denied || masked || s->metric != TSH_METRIC_L2) return false;
+  if (mode == 1 && s->rows * s->ld * 4 <= SCAN_I4_MIN_BYTES) return false;
+  return true;
+}
+
+// the device buffers of the 4-bit pass: A's keys and minima, W's words, the control words and the host's total
+int ctx_reserve_i4(Ctx *c, int64_t tiles) {
+  if (!c->d_i4_ctl) {
+    HIPCHK(hipMalloc(&c->d_i4_ctl, 16));
+    HIPCHK(hipHostMalloc(&c->h_i4, 64, hipHostMallocMapped));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_i4_dev), c->h_i4, 0));
+    c->bytes += 16;
+  }
+  if (tiles > c->i4_tiles_cap) {
+    hipFree(c->d_i4_keys);
+    hipFree(c->d_i4_gmin);
+    hipFree(c->d_i4_mask);
+    c->d_i4_keys = c->d_i4_gmin = nullptr;
+    c->d_i4_mask = nullptr;
+    c->bytes -= c->i4_tiles_cap * (64 * 4 + 4 + 8);
+    c->i4_tiles_cap = 0;
+    HIPCHK(hipMalloc(&c->d_i4_keys, (size_t)tiles * 64 * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&c->d_i4_gmin, (size_t)tiles * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&c->d_i4_mask, (size_t)tiles * sizeof(uint64_t)));
+    c->i4_tiles_cap = tiles;
+    c->bytes += tiles * (64 * 4 + 4 + 8);
+  }
+  return TSH_OK;
+}
+
+// A's arguments; q: the staged query, ld floats (rides in the argument segment where it fits)
+void fill_scan_i4_args(const Shard *s, const Ctx *c, const ScanI4Band &b, const float *q, ScanI4ArgsQ *aq) {
+  ScanI4Args &a = aq->a;
+  const int groups = scan_i4_groups(s->ld);
+  a.plane = static_cast<const u32x4_i4 *>(s->rows4.d);
+  a.query = s->ld <= SCAN_Q_INLINE ? nullptr : c->d_query;
+  a.scale8 = rows8_scales(s->rows8, s->ld);
+  a.rho = rows4_rho(s->rows4, groups);
+  a.sqnorm = s->d_sqnorm;
+  a.keys = c->d_i4_keys;
+  a.gmin = c->d_i4_gmin;
+  a.n = s->rows;
+  a.n_tiles = (int32_t)((s->rows + 63) / 64);
+  a.ld = (int32_t)s->ld;
+  a.groups = groups;
+  a.pad_ = 0;
+  a.qbias = b.qbias;
+  a.a_s = b.a_s;
+  a.a_r = b.a_r;
+  a.a_c = b.a_c;
+  a.a_v = b.a_v;
+  a.beta = b.beta;
+  if (s->ld <= SCAN_Q_INLINE && q != aq->q) memcpy(aq->q, q, (size_t)s->ld * sizeof(float));
+}
+
+// A, T and W on st: afterwards c->d_i4_mask holds the survivors' words (their total: i4_total_kernel, launch_job_tail)
+void launch_scan_i4(const ScanI4ArgsQ &aq, Ctx *c, int32_t k, hipStream_t st, hipEvent_t start) {
+  const int32_t n_tiles = aq.a.n_tiles;
+  const unsigned grid = (unsigned)((n_tiles + 3) / 4);
+  const hipEvent_t none = nullptr;
+  if (start) hipExtLaunchKernelGGL(scan_i4_kernel<4>, dim3(grid), dim3(256), 0, st, start, none, 0, aq);
+  else scan_i4_kernel<4><<<grid, 256, 0, st>>>(aq);
+  if (n_tiles <= SEL_VPT * SEL_THREADS) i4_tau_kernel<true><<<1, SEL_THREADS, 0, st>>>(c->d_i4_gmin, n_tiles, k, c->d_i4_ctl);
+  else i4_tau_kernel<false><<<1, SEL_THREADS, 0, st>>>(c->d_i4_gmin, n_tiles, k, c->d_i4_ctl);
+  i4_mask_kernel<<<grid, 256, 0, st>>>(c->d_i4_keys, n_tiles, c->d_i4_mask, c->d_i4_ctl);
+}
+
 // the int8 scan's arguments on top of the f32 scan's (fill_scan_args)
 void fill_scan_i8_args(const Shard *s, const ScanI8Band &ib, ScanArgsQ *aq) {
   aq->a.rows16 = s->rows8.d;
@@ -1459,6 +1596,10 @@ Route choose_route(const Shard *s, const ShardMask &m, bool masked, int32_t k, i
     // mask not even k rows need be alive (a tombstoned index of five rows, or of none): always E2, which writes
     // min(k, live rows) entries
     r.picked = !masked && s->exact_pick && (k + EX_R - 1) / EX_R >= k;
+    if (r.ib.ok && scan_i4_applies(s, masked)) {
+      r.i4b = scan_i4_band(s->dim, scan_i4_groups(s->ld), q, s->max_norm, s->max_abs);
+      r.i4_eligible = r.i4b.ok;
+    }
   }
   if (r.exact) {
     // E2' (the wide pick) bounds the k-th key by the k-th smallest wave minimum: it needs clearly more waves than k
@@ -1498,6 +1639,7 @@ struct JobReq {
 // the arguments of a job's kernels (8 KiB: job_enqueue keeps them off the stack)
 struct JobArgs {
   ScanArgsQ sa;
+  ScanI4ArgsQ s4;  // (the 4-bit pass in front of an int8 scan: Job::i4)
   ExactArgsQ xa;
   SelectArgs se;
   RerankArgs ra;
@@ -1604,6 +1746,10 @@ void fill_job_args(const Shard *s, Job *j, const JobReq &rq, const float *q, Job
     // the coarse scan, then E1 + E2 / E2' over the survivor list: I8_LIST_CAP entries, the padding dead.  E1 reads the
     // query's device copy (the scan's workgroup 0 leaves it, or it was uploaded in front of the scan)
     fill_scan_i8_args(s, r.ib, &ka->sa);
+    if (j->i4) {  // A, T, W, then the int8 scan as a masked one behind W's words
+      fill_scan_i4_args(s, c, r.i4b, q, &ka->s4);
+      ka->sa.a.mask = c->d_i4_mask;
+    }
     fill_exact_args(s, c, nullptr, c->d_i8_list, I8_LIST_CAP, q, &ka->xa);
     if (r.picked) ka->xa.a.wmin = c->d_xpick + 1;
     j->xsel = ExactSelArgs{c->d_xkey, c->d_xsum, c->d_i8_list, hdr, hdr_host, out, s->row_base, /*shard_rows*/ s->rows, I8_LIST_CAP,
@@ -1615,7 +1761,7 @@ void fill_job_args(const Shard *s, Job *j, const JobReq &rq, const float *q, Job
 // ---- on which streams a job's kernels run (all of it under the device's scan_mu) ------------------------------------
 // The scan's stream; *which >= 0: one of the two scan streams, for a scan that alternates between them (small shards,
 // big shards' scans with a large drain share), booked in DeviceStreams::scan_out once the scan is enqueued
-hipStream_t pick_scan_stream(Shard *s, RowStore store, bool overlap, int64_t rows_est, int *which) {
+hipStream_t pick_scan_stream(Shard *s, RowStore store, bool overlap, int64_t rows_est, int *which, bool i4 = false) {
   *which = -1;
   // Between two scans on one in-order stream the slots of the finished launch empty over one wave life and nothing
   // refills them: half a wave life per scan, a share
@@ -1629,8 +1775,10 @@ hipStream_t pick_scan_stream(Shard *s, RowStore store, bool overlap, int64_t row
   const int32_t n_tiles = (int32_t)((s->rows + 63) / 64);
   const int64_t tiles_read = rows_est > 0 ? std::min<int64_t>(n_tiles, (rows_est + 63) / 64) : n_tiles;
   // (two scan streams exist on a split device only: the scans' CUs are those the tails' mask leaves)
+  // (a scan with the 4-bit pass in front: its threshold kernel is one workgroup, in order between the two passes --
+  // whatever the shard's size the other stream's pass keeps the HBM busy meanwhile)
   const bool two = s->scan_streams == 2 ||
-                   (s->scan_streams == 0 && scan_two_streams(store, s->nch, s->ld, tiles_read, s->cus - TAIL_CUS));
+                   (s->scan_streams == 0 && (i4 || scan_two_streams(store, s->nch, s->ld, tiles_read, s->cus - TAIL_CUS)));
   if (!(overlap && two && s->scan_stream2)) return s->scan_stream;
   DeviceStreams *ds = s->dstreams;
   for (size_t i = 0; i < ds->scan_out.size();) {  // scans that have finished since the last look
@@ -1704,6 +1852,15 @@ int launch_job_scan(Shard *s, Job *j, const JobReq &rq, const JobArgs &ka, hipSt
     HIPCHK(hipMemcpyAsync(c->d_list, c->h_list, (size_t)rq.mask.list.padded * sizeof(uint32_t), hipMemcpyHostToDevice, ps));
   if (s->ld > SCAN_Q_INLINE)
     HIPCHK(hipMemcpyAsync(c->d_query, c->h_query, (size_t)s->ld * sizeof(float), hipMemcpyHostToDevice, ps));
+  if (j->i4) {
+    // the 4-bit pass, its threshold and its mask, then the int8 scan over the survivors in the scattered-mask grid: all in
+    // order on this stream (the job's timing events bracket the four)
+    launch_scan_i4(ka.s4, c, j->k, ps, ev.start);
+    LaunchEv evb;
+    evb.stop = ev.stop;
+    launch_scan_i8(ka.sa, s->nch, s->metric, /*masked*/ true, ps, evb, /*mostly_live*/ false);
+    return TSH_OK;
+  }
   launch_route_scan(s, j->route, j->store, j->masked, rq.mask.rows_est, ka.sa, ka.xa, ps, ev);
   return TSH_OK;
 }
@@ -1730,6 +1887,8 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
   const bool quar = !j->quar_sel.empty();
   const hipEvent_t none = nullptr, done = quar ? none : c->ev_done;
   const bool i8 = j->store == RowStore::I8;
+  // (the 4-bit pass's survivors, counted for the host beside the tail: nothing on the scan streams waits for it)
+  if (j->i4) i4_total_kernel<<<1, 1024, 0, ts>>>(c->d_i4_mask, ka.sa.a.n_tiles, c->h_i4_dev);
   if (i8) {
     // threshold, candidate tiles, the survivors' ascending list (capped and padded) and their total; E1 over the list
     const int32_t n_tiles = ka.sa.a.n_tiles;
@@ -2001,9 +2160,15 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
   // (an eligible scan uses up a denial of its route, if any are left, whatever its band; a scan that takes the int8
   // route neither asks for the fp16 copy nor touches the fp16 route's denials)
   j->store = RowStore::F32;
+  j->i4 = false;
   if (r.i8_eligible && !s->rows8.route.take_denial() && r.ib.ok && rows8_ensure(s, s->scan_stream)) {
     j->store = RowStore::I8;
     if ((rc = ctx_reserve_exact(c, I8_LIST_CAP)) || (rc = ctx_reserve_i8(c))) return rc;
+    // (the 4-bit pass in front of it: an eligible scan uses up a denial of ITS route, if any are left)
+    if (r.i4_eligible && !s->rows4.take_denial() && rows4_ensure(s, s->scan_stream)) {
+      if ((rc = ctx_reserve_i4(c, s->cap / 64))) return rc;
+      j->i4 = true;
+    }
   } else {
     if (!r.exact) j->route.picked = false;
     if (r.f16_eligible && !s->rows16.route.take_denial() && r.fb.ok && rows16_ensure(s, s->scan_stream, r.v_exp)) j->store = RowStore::F16;
@@ -2034,7 +2199,7 @@ int job_enqueue(Shard *s, Job *j, const JobReq &rq) {
     int which;
     // (a first scan on the second stream needs no wait for the copy it reads: rows8_ensure / rows16_ensure above
     // converted on scan_stream and synchronised on the host before they returned -- row_copy_ensure)
-    hipStream_t ps = pick_scan_stream(s, j->store, overlap, rq.mask.rows_est, &which), ts;
+    hipStream_t ps = pick_scan_stream(s, j->store, overlap, rq.mask.rows_est, &which, j->i4), ts;
     j->timed = (s->c_scans.load() & 3) == 0;  // sample every 4th scan with timing events
     LaunchEv ev;  // start / stop ride on the scan's own packet: no barrier packets between scans
     if (j->timed) {
@@ -2171,6 +2336,33 @@ int run_fallback(Shard *s, Job *j, uint32_t band_key, std::vector<BlockEntry> *s
   return TSH_OK;
 }
 
+// A finished scan whose 4-bit pass ran (Job::i4): the survivors it left, and the deny rule -- the pass pays only while few
+// rows survive it.  Two scans in a row above SCAN_I4_MAX_SHARE deny the route for deny_len eligible scans.  Scans that
+// were already in flight when the denial fell (a pipelined call) are counted and otherwise ignored.  When a denial has
+// run out (RowCopyI4::take_denial) and the scans after it are over the share again, the next denial is twice as long,
+// up to SCAN_I4_DENY_CAP; a scan at or below the share ends that.
+void scan_i4_account(Shard *s, Job *j) {
+  RowCopyI4 &c4 = s->rows4;
+  const int64_t kept = (int64_t)j->c->h_i4[0];
+  j->i4 = false;
+  c4.route.scans++;
+  c4.survivors += kept;
+  if (c4.route.denied.load() > 0) return;
+  if ((double)kept <= SCAN_I4_MAX_SHARE * (double)s->rows) {
+    c4.route.strikes.store(0);
+    c4.probation.store(false);
+    c4.deny_len.store(SCAN_ROUTE_DENIED_SCANS);
+    return;
+  }
+  if (c4.route.strikes.fetch_add(1) + 1 < 2) return;
+  c4.route.strikes.store(0);
+  const int len = c4.probation.load() ? std::min(2 * c4.deny_len.load(), SCAN_I4_DENY_CAP) : SCAN_ROUTE_DENIED_SCANS;
+  c4.deny_len.store(len);
+  c4.probation.store(false);
+  c4.route.denied.store(len);
+  c4.denials++;
+}
+
 // A finished fp16 or int8 scan (j->store) whose list overflowed -- the fp16 scan's candidate list (crowded neighbours:
 // ties, near-duplicates), the int8 scan's survivor list (the same, or fewer live tiles than k in a big shard) -- is NOT
 // widened over its reduced keys: the query is redone through the f32 scan, from the job's saved query, tag and mask, and
@@ -2274,6 +2466,7 @@ int job_finish(Shard *s, Job *j, std::vector<BlockEntry> *spill, std::vector<Blo
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipEventSynchronize(c->ev_done));
   HIPCHK(hipGetLastError());
+  if (j->i4) scan_i4_account(s, j);
   if (j->store != RowStore::F32) {
     int rc = redo_overflowed_scan(s, j);
     if (rc) return rc;
@@ -2660,6 +2853,7 @@ void shard_destroy(Shard *s) {
   hipFree(s->d_split);
   s->rows16.release(s);
   s->rows8.release(s);
+  s->rows4.release(s);
   hipFree(s->d_perm);
   hipFree(s->d_psq);
   hipFree(s->d_hub);
@@ -5009,6 +5203,8 @@ int32_t tsh_index_set_option(tsh_index *idx, int32_t option, int64_t value) {
        [](Shard *sh, int64_t v) { sh->rows8.mode = (int)v; }},
       {TSH_OPT_SCAN_I8_MASKED, 0, 2, "scan i8 masked must be 0 (never), 1 (auto: shards above 256 MiB) or 2 (every eligible masked scan)",
        [](Shard *sh, int64_t v) { sh->rows8.mode_masked = (int)v; }},
+      {TSH_OPT_SCAN_I4, 0, 2, "scan i4 must be 0 (never), 1 (auto: L2 shards above 256 MiB) or 2 (every eligible scan)",
+       [](Shard *sh, int64_t v) { sh->rows4.mode = (int)v; }},
       {TSH_OPT_SCAN_STREAMS, 0, 2, "scan streams must be 0 (by the scan's drain share), 1 (one stream) or 2 (two whenever queries overlap)",
        [](Shard *sh, int64_t v) { sh->scan_streams = (int)v; }},
       {TSH_OPT_BATCH_KERNEL, 0, 3, "batch kernel must be 0 (f32 MFMA), 1 (bf16x3), 2 (f16) or 3 (auto)",
@@ -5092,6 +5288,56 @@ int32_t row_copy_stats(tsh_index *idx, RowStore store, int64_t *out) {
 }
 int32_t tsh_scan_f16_stats(tsh_index *idx, int64_t *out) { return row_copy_stats(idx, RowStore::F16, out); }
 int32_t tsh_scan_i8_stats(tsh_index *idx, int64_t *out) { return row_copy_stats(idx, RowStore::I8, out); }
+
+// scans whose 4-bit pass ran, rows those passes left to the int8 scan, rows converted, bytes of the plane, times the route
+// was denied, eligible scans a denial still covers: over the shards
+int32_t tsh_scan_i4_stats(tsh_index *idx, int64_t *out) {
+  if (!idx || !out) return set_err(TSH_E_BAD_ARG, "NULL pointer");
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  for (auto &sp : idx->shards) {
+    Shard *s = sp.get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    const RowCopyI4 &c = s->rows4;
+    out[0] += c.route.scans.load();
+    out[1] += c.survivors.load();
+    out[2] += c.converted.load();
+    out[4] += c.denials.load();
+    out[5] += std::max(0, c.route.denied.load());
+    std::lock_guard<std::mutex> lk(s->row_copies_mu);
+    out[3] += c.bytes;
+  }
+  return TSH_OK;
+}
+
+int32_t tsh_probe_scan_i4_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper) {
+  ScanHook h;
+  int rc = scan_hook_begin(&h, idx, query, out_lower && out_upper);
+  if (rc) return rc;
+  Shard *s = h.s;
+  Ctx *c = h.c;
+  hipStream_t st = h.st;
+  const bool masked = !s->all_live || !s->quar_ids.empty();
+  if (!scan_i8_applies(s, masked, 1, 1) || !scan_i4_applies(s, masked) || compute_band(s, c->h_query).force_all)
+    return set_err(TSH_E_BAD_ARG, "no 4-bit scan for this index / query (TSH_OPT_SCAN_I8, TSH_OPT_SCAN_I4, metric, dead rows, row width, error model)");
+  const ScanI4Band b = scan_i4_band(s->dim, scan_i4_groups(s->ld), c->h_query, s->max_norm, s->max_abs);
+  if (!b.ok) return set_err(TSH_E_BAD_ARG, "the query is outside the 4-bit scan's error model");
+  if (!rows8_ensure(s, st) || !rows4_ensure(s, st)) return set_err(TSH_E_OOM, "no room on the device for the 4-bit copy of the rows");
+  if ((rc = ctx_reserve_i4(c, s->cap / 64))) return rc;
+  static thread_local ScanI4ArgsQ sa;
+  fill_scan_i4_args(s, c, b, c->h_query, &sa);
+  // (the hook's helpers read the context's keys buffer: A writes there)
+  sa.a.keys = c->d_keys;
+  scan_i4_kernel<4><<<(unsigned)((sa.a.n_tiles + 3) / 4), 256, 0, st>>>(sa);
+  if ((rc = scan_hook_keys(h, out_lower))) return rc;
+  std::vector<float> w((size_t)s->rows);
+  float *d_w = reinterpret_cast<float *>(c->d_keys);
+  scan_i4_w_kernel<<<(unsigned)((s->rows + 255) / 256), 256, 0, st>>>(sa.a, d_w);
+  HIPCHK(hipMemcpyAsync(w.data(), d_w, (size_t)s->rows * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  for (int64_t i = 0; i < s->rows; ++i) out_upper[i] = out_lower[i] + 2.0f * w[(size_t)i];
+  return TSH_OK;
+}
 
 int32_t tsh_probe_scan_i8_keys(tsh_index *idx, const float *query, float *out_lower, float *out_upper) {
   ScanHook h;

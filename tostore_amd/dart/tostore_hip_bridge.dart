@@ -167,6 +167,10 @@ typedef _SearchGroupedRowsStatsC = Int32 Function(Pointer<Void>, Pointer<Int64>)
 typedef _SearchGroupedRowsStatsD = int Function(Pointer<Void>, Pointer<Int64>);
 typedef _ProbeScanI8C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _ProbeScanI8D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _ScanI4StatsC = Int32 Function(Pointer<Void>, Pointer<Int64>);
+typedef _ScanI4StatsD = int Function(Pointer<Void>, Pointer<Int64>);
+typedef _ProbeScanI4C = Int32 Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _ProbeScanI4D = int Function(Pointer<Void>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _SetOptionC = Int32 Function(Pointer<Void>, Int32, Int64);
 typedef _SetOptionD = int Function(Pointer<Void>, int, int);
 typedef _BlockBytesC = Int64 Function(Int32);
@@ -468,6 +472,8 @@ final class HipVectorBackend {
   static late final _SearchGroupedRowsD _searchGroupedRows;
   static late final _SearchGroupedRowsStatsD _searchGroupedRowsStats;
   static late final _ProbeScanI8D _probeScanI8;
+  static late final _ScanI4StatsD _scanI4Stats;
+  static late final _ProbeScanI4D _probeScanI4;
   static late final _BlockBytesD _blockBytes;
   static late final _BlockEntriesD _blockEntries;
   static late final _SearchShardD _searchShard;
@@ -566,6 +572,8 @@ final class HipVectorBackend {
       _searchGroupedRowsStats =
           lib.lookupFunction<_SearchGroupedRowsStatsC, _SearchGroupedRowsStatsD>('tsh_search_grouped_rows_stats');
       _probeScanI8 = lib.lookupFunction<_ProbeScanI8C, _ProbeScanI8D>('tsh_probe_scan_i8_keys');
+      _scanI4Stats = lib.lookupFunction<_ScanI4StatsC, _ScanI4StatsD>('tsh_scan_i4_stats');
+      _probeScanI4 = lib.lookupFunction<_ProbeScanI4C, _ProbeScanI4D>('tsh_probe_scan_i4_keys');
       _blockBytes = lib.lookupFunction<_BlockBytesC, _BlockBytesD>('tsh_candidate_block_bytes');
       _blockEntries = lib.lookupFunction<_BlockEntriesC, _BlockEntriesD>('tsh_default_block_entries');
       _searchShard = lib.lookupFunction<_SearchShardC, _SearchShardD>('tsh_search_shard');
@@ -1571,14 +1579,19 @@ final class HipVectorBackend {
 
   /// tsh_index_set_option: 1 = TSH_OPT_BATCH_MIN_NQ, 2 = TSH_OPT_BATCH_KERNEL, 4 = TSH_OPT_EXACT_SCAN_ROWS,
   /// 5 = TSH_OPT_EXACT_SELECT, 6 = TSH_OPT_BATCH_HUB, 7 = TSH_OPT_BATCH_GROUP, 8 = TSH_OPT_SCAN_F16,
-  /// 9 = TSH_OPT_SCAN_F16_MASKED, 10 = TSH_OPT_SCAN_I8, 12 = TSH_OPT_SCAN_STREAMS, 13 = TSH_OPT_SCAN_I8_MASKED (tuning
-  /// only: results never depend on them).
+  /// 9 = TSH_OPT_SCAN_F16_MASKED, 10 = TSH_OPT_SCAN_I8, 12 = TSH_OPT_SCAN_STREAMS, 13 = TSH_OPT_SCAN_I8_MASKED,
+  /// 14 = TSH_OPT_SCAN_I4 (tuning only: results never depend on them).
   bool setOption(int option, int value) => _setOption(_handle, option, value) == 0;
 
   /// TSH_OPT_SCAN_I8_MASKED: the int8 coarse pass behind row masks, tombstones, quarantined rows and gaps -- 0 never,
   /// 1 auto (shards above 256 MiB; gives way to a forced fp16 masked route), 2 every eligible masked scan.
   static const int optScanI8Masked = 13;
   bool setScanI8Masked(int mode) => setOption(optScanI8Masked, mode);
+
+  /// TSH_OPT_SCAN_I4: a 4-bit first pass in front of the dense L2 int8 scan -- 0 never, 1 auto (L2 shards above
+  /// 1400 MiB), 2 every eligible scan.
+  static const int optScanI4 = 14;
+  bool setScanI4(int mode) => setOption(optScanI4, mode);
 
   /// The fp16 scan's counters (TSH_OPT_SCAN_F16): scans over the fp16 copy of the rows, queries redone through the
   /// f32 scan, rows converted, bytes of the copy resident.
@@ -1613,6 +1626,23 @@ final class HipVectorBackend {
   /// hold one float per row.
   bool probeScanI8Keys(Pointer<Float> query, Pointer<Float> lower, Pointer<Float> upper) =>
       _probeScanI8(_handle, query, lower, upper) == 0;
+
+  /// The 4-bit first pass's counters (TSH_OPT_SCAN_I4): scans it ran in, rows it left to the int8 scan, rows converted,
+  /// bytes of the plane, times the route was denied, eligible scans a denial still covers.
+  Map<String, int>? scanI4Stats() {
+    final o = calloc<Int64>(6);
+    try {
+      if (_scanI4Stats(_handle, o) != 0) return null;
+      return {'scans': o[0], 'survivors': o[1], 'rowsConverted': o[2], 'copyBytes': o[3], 'denials': o[4], 'deniedLeft': o[5]};
+    } finally {
+      calloc.free(o);
+    }
+  }
+
+  /// Diagnostics: the two sides of the 4-bit pass's band around every row's key for one query; `lower` and `upper`
+  /// hold one float per row.
+  bool probeScanI4Keys(Pointer<Float> query, Pointer<Float> lower, Pointer<Float> upper) =>
+      _probeScanI4(_handle, query, lower, upper) == 0;
 
   int get nativeDimensions => _dim(_handle);
   int get nativeMetric => _metric(_handle);
