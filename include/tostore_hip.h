@@ -59,6 +59,8 @@ extern "C" {
 /*    Additive since, same version, continued: tsh_attr_create, tsh_attr_set, tsh_attr_destroy, tsh_mask_create_range,
  *    tsh_mask_read. */
 /*    Additive since, same version, continued: tsh_mask_create_where (tsh_where_term, TSH_TERM_*, TSH_WHERE_MAX_*). */
+/*    Additive since, same version, continued: tsh_tags_create, tsh_tags_set, tsh_tags_destroy, tsh_mask_create_tags
+ *    (TSH_TAGS_ALL, TSH_TAGS_ANY, TSH_TAGS_MAX_SET_VALUES). */
 
 /* status codes */
 #define TSH_OK 0
@@ -392,7 +394,8 @@ int32_t tsh_search_submit_masked(tsh_index *idx, const float *query, int32_t k, 
  *   launch of its own: folding it into the range kernel would save under a tenth of the call.
  * The attribute handle is a tsh_attr * (typedef below) and travels as `void *`, tsh_attr_create's `out` -- the address
  *   of the caller's tsh_attr * -- too, exactly as a tsh_groups * does (see tsh_groups_create below).
- * Not here: string or multi-valued attributes; a predicate evaluated inside the scan
+ * Not here: string attributes (the bindings map them to int64 through a dictionary; multi-valued attributes are tag
+ *   columns, tsh_tags_create below); a predicate evaluated inside the scan
  *   kernels without a handle; a column that follows appends on its own; collective (sharded) creation -- every rank
  *   makes its own handle from its own column, as with bitmaps. */
 #define TSH_ATTR_NULL INT64_MIN
@@ -461,6 +464,76 @@ typedef struct tsh_where_term {
 } tsh_where_term;
 int32_t tsh_mask_create_where(tsh_index *idx, const void *terms, int32_t n_terms, tsh_mask *with, int32_t combine,
                               tsh_mask **out);
+
+/* ---- tag columns: an array-valued WHERE term made into a mask handle on the device (additive since ABI 5) -------------
+ * The filter a vector table meets first is not scalar: `acl HAS ANY (the caller's 5 - 200 group ids)` differs for every
+ * user and so for every query; `tags HAS ALL ('gpu', 'rocm')`, `NOT (labels HAS ANY (...))`.  The reference has the field
+ * type (DataType.array, lib/src/model/table_schema.dart:1896) and would filter on the host
+ * (lib/src/core/vector_index_manager.dart:1223-1378).  No attribute column can hold a row's set, so without this the caller
+ * walks a ragged array per row per query, packs a bitmap and pays tsh_mask_create.  A TAG handle keeps the ragged column
+ * beside the rows on the device as CSR, and tsh_mask_create_tags makes a mask handle from one HAS ANY / HAS ALL term over
+ * it in one launch (T1 mask_tags_kernel, tostore_amd/csrc/tsh_tags.hip.h; the host side is tsh_tags_plan.h): a wave per
+ * 64 rows streams those rows' values as ONE contiguous span, counts each row's matches against the term's sorted set in
+ * LDS, and its ballot is the mask word.  The result is an ordinary tsh_mask.  It is not a new term kind of
+ * tsh_mask_create_where: it composes with scalar clauses through `with`, as chained range calls do.
+ *
+ * tsh_tags_create: the column is CSR by GLOBAL row id: row i < n holds values[offsets[i] .. offsets[i + 1]); offsets has
+ *   n + 1 entries, offsets[0] == 0, and never decreases (neither array is read when n == 0; values is not read when
+ *   offsets[n] == 0).  The library keeps its own copy with every row's list sorted and deduplicated: a row is a SET.  A
+ *   row whose list contains TSH_ATTR_NULL anywhere is a NULL row -- the field has no value -- and so is a row at or
+ *   beyond n.  An empty list is a value, the empty set; it is NOT NULL.  Strings go in through the bindings' dictionary.
+ * tsh_tags_set overwrites or extends rows [first_row_id, first_row_id + n); its offsets are relative to its own values,
+ *   again from 0, and the lists may differ in length from those they replace.  Rows between the old end and first_row_id
+ *   become NULL rows.  The append feed's companion: the column does not follow appends on its own.
+ * tsh_mask_create_tags: let S be set[0, n_set) with duplicates and TSH_ATTR_NULL dropped, c_i = |row_i n S|, and the
+ *   threshold t = |S| if need == TSH_TAGS_ALL, else need (TSH_TAGS_ANY is 1; any n >= 1 says "at least n distinct values
+ *   of the set").  Row i of the index's current rows is kept iff it is not NULL and  (c_i >= t) != (negate != 0);  the
+ *   result is then and-ed (TSH_MASK_AND) or or-ed (TSH_MASK_OR) with `with`'s bitmap, zero-extended to the current rows,
+ *   exactly as by tsh_mask_create_range.  So HAS ALL of an empty S keeps every non-NULL row (t = 0) and HAS ANY of an
+ *   empty S keeps none; need > |S| keeps none and, negated, every non-NULL row, empty-set rows included; a NULL row is
+ *   kept by no term, negated or not.  The answer is exact: NumPy on the host is the specification.  The library copies
+ *   the set: it need only live for the call.  One tag term per call; several are chained through `with`.
+ *   Snapshot (a later tsh_tags_set or tsh_tags_destroy does not change the handle, rows appended later are not kept),
+ *   tsh_mask_read, tsh_mask_kept, rebuilds after appends, tombstones, quarantined rows, several devices and shard handles
+ *   with global ids: as for a range-made handle.
+ * TSH_E_BAD_ARG (each clears *out, each answered before any device work): a NULL idx, tags or out; n < 0; NULL offsets
+ *   with n > 0; offsets[0] != 0, or a decreasing offset; NULL values with offsets[n] > 0; first_row_id < 0; need < 0;
+ *   n_set < 0, or a NULL set with n_set > 0; |S| > TSH_TAGS_MAX_SET_VALUES; combine neither TSH_MASK_AND nor TSH_MASK_OR,
+ *   even with with == NULL; a tags or `with` handle of another index, or an orphaned one.  And: the device offsets are
+ *   32-bit, so a shard's slice of the column may hold at most 2^31 - 1 values; the call that would build such a part
+ *   (tsh_tags_create, or the tsh_mask_create_tags after a tsh_tags_set or an append) refuses it.
+ * Lifetime: as an attribute handle's.  tsh_index_destroy orphans a live tag handle (later use answers TSH_E_BAD_ARG,
+ *   tsh_tags_destroy then frees only the handle itself); the two destroys may come in either order.
+ * Threads: any number of tsh_mask_create_tags calls may share one tag handle.  tsh_tags_set takes the index lock the way
+ *   an append does and waits for the calls that use the handle.
+ * Cost, measured on 1 M x 768, L2, k = 100 ("tag columns"; profiles/mask_tags_ab.json, written by
+ *   tools/ab_mask_tags.py), us by the host clock, medians over five processes with their lowest and highest, the device
+ *   route against the host route (NumPy isin over the flat values, bincount by owner, compare, packbits,
+ *   tsh_mask_create).  An ACL-shaped column, 1 - 8 group ids per row out of 10 000 (4.5 M stored values): HAS ANY of 5
+ *   values 90.7 (87.7 - 100.9) against 24 838 (24 502 - 28 053), of 64 values 94.3 against 22 549, of 1024 values 87.9
+ *   against 23 101, HAS ALL of 2 values 61.8 against 30 053; a lone query including make and destroy 137.6, 171.7, 212.5
+ *   and 115.4 against 24 967, 22 689, 23 328 and 30 182.  A tag-shaped column, 0 - 32 tags per row out of 1 000 (15.8 M
+ *   stored values): HAS ANY of 5 values 78.4 (76.5 - 82.0) against 77 734 (76 590 - 77 947), of 64 values 87.1 against
+ *   75 855, of all 1 000 values 132.8 against 89 369, HAS ALL of 2 values 104.1 against 46 683; a lone query 167.0,
+ *   237.1, 332.7 and 152.4 against 77 915, 76 110, 89 657 and 46 790.  In every shape the device route's slowest process
+ *   is faster than the host route's fastest.  The kernel itself, from a kernel trace in a run of its own: 9.4 - 32.0 us
+ *   on the ACL-shaped column and 22.6 - 78.7 us on the tag-shaped one (it reads 8 B per stored value, 4 B per row of
+ *   offsets and 8 B per 64 rows of valid bits, once; the longest is the term every stored value matches); the rest of
+ *   the call is the tail every device-made handle pays (tsh_mask_create_range above).
+ * The tag handle is a tsh_tags * (typedef below) and travels as `void *`, tsh_tags_create's `out` -- the address of the
+ *   caller's tsh_tags * -- too, exactly as a tsh_attr * does.
+ * Not here: tag terms inside tsh_mask_create_where's term table; more than one tag term per call; string values; a
+ *   column that follows appends on its own; collective (sharded) creation -- every rank makes its own handle from the
+ *   global CSR; a predicate evaluated inside the scan kernels without a handle. */
+#define TSH_TAGS_ALL 0   /* need: every distinct non-NULL value of the set */
+#define TSH_TAGS_ANY 1   /* need: at least one; any n >= 1 means "at least n distinct values of the set" */
+#define TSH_TAGS_MAX_SET_VALUES 4096 /* the term's set, after the library's sort + dedupe */
+typedef struct tsh_tags tsh_tags;
+int32_t tsh_tags_create(tsh_index *idx, const int64_t *offsets, int64_t n, const int64_t *values, void *out);
+int32_t tsh_tags_set(void *tags, int64_t first_row_id, int64_t n, const int64_t *offsets, const int64_t *values);
+int32_t tsh_tags_destroy(void *tags);
+int32_t tsh_mask_create_tags(tsh_index *idx, void *tags, const int64_t *set, int64_t n_set, int32_t need,
+                             int32_t negate, tsh_mask *with, int32_t combine, tsh_mask **out);
 
 /* Asynchronous form of a single-query tsh_search, for callers that keep several
  * independent queries in flight (the reference serves concurrent vectorSearch

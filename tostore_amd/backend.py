@@ -102,6 +102,32 @@ class HipMask:
         index._live_masks().add(self)
         return self
 
+    @classmethod
+    def _tags(cls, index: "HipVectorIndex", tags: "HipTags", values, need, negate: bool, with_mask, combine) -> "HipMask":
+        """A handle made on the device from one HAS ANY / HAS ALL term over a tag column (`tsh_mask_create_tags`)."""
+        ops = {"and": _ffi.TSH_MASK_AND, "or": _ffi.TSH_MASK_OR, _ffi.TSH_MASK_AND: _ffi.TSH_MASK_AND, _ffi.TSH_MASK_OR: _ffi.TSH_MASK_OR}
+        if combine not in ops:
+            raise ValueError("combine is 'and' or 'or'")
+        if need == "any":
+            n = _ffi.TSH_TAGS_ANY
+        elif need == "all":
+            n = _ffi.TSH_TAGS_ALL
+        elif isinstance(need, (int, np.integer)) and not isinstance(need, bool) and need >= 1:
+            n = int(need)
+        else:
+            raise ValueError("need is 'any', 'all' or a count of at least 1")
+        # (a closed tags or with_mask raises here: NULL would read as "no tags" / "no with")
+        t = tags.handle()
+        w = with_mask.handle() if with_mask is not None else None
+        v = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.index = index
+        _ffi.check(_ffi.lib().tsh_mask_create_tags(index._h, t, v.ctypes.data_as(_ffi.p_i64) if v.shape[0] else None, v.shape[0], n,
+                                                   1 if negate else 0, w, ops[combine], ctypes.byref(self._h)))
+        index._live_masks().add(self)
+        return self
+
     def handle(self):
         """The `tsh_mask*` to pass to the library; ValueError once the mask (or its index) was closed."""
         if not self._h:
@@ -272,6 +298,70 @@ class HipAttr:
             pass
 
 
+def _tags_csr(lists):
+    """(offsets, values), both int64 and contiguous, of a tag column given as a list of iterables (one per row) or as an
+    (offsets, values) pair of arrays already."""
+    if isinstance(lists, tuple) and len(lists) == 2:
+        off = np.ascontiguousarray(lists[0], dtype=np.int64).reshape(-1)
+        vals = np.ascontiguousarray(lists[1], dtype=np.int64).reshape(-1)
+        if off.shape[0] == 0:
+            off = np.zeros(1, dtype=np.int64)
+        return off, vals
+    rows = [np.asarray(list(r), dtype=np.int64).reshape(-1) for r in lists]
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    if rows:
+        np.cumsum([r.shape[0] for r in rows], out=off[1:])
+    vals = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    return off, np.ascontiguousarray(vals, dtype=np.int64)
+
+
+class HipTags:
+    """One array-valued attribute of every row, kept on the device as CSR (`tsh_tags*`, include/tostore_hip.h), for
+    `HipVectorIndex.make_mask_tags`: row i holds a SET of int64 values (group ids of an ACL, tags, labels; strings go in
+    through a dictionary of the caller's).  `lists` is a list of iterables, one per GLOBAL row id, or an
+    `(offsets, values)` pair.  A list that holds `ATTR_NULL` makes the row a NULL row, as a row beyond the column is; an
+    empty list is the empty set, not NULL.  `set()` overwrites or extends a range of rows, as the append feed does for the
+    rows.  An index that is closed first closes its tag columns, and a closed handle is refused (ValueError)."""
+
+    def __init__(self, index: "HipVectorIndex", lists):
+        off, vals = _tags_csr(lists)
+        self._h = ctypes.c_void_p()
+        self.index = index
+        _ffi.check(_ffi.lib().tsh_tags_create(index._h, off.ctypes.data_as(_ffi.p_i64), off.shape[0] - 1,
+                                              vals.ctypes.data_as(_ffi.p_i64) if vals.shape[0] else None, ctypes.byref(self._h)))
+        index._live_masks().add(self)
+
+    def handle(self):
+        """The `tsh_tags*` to pass to the library; ValueError once the handle (or its index) was closed."""
+        if not self._h:
+            raise ValueError("the tags handle is closed (or its index was)")
+        return self._h
+
+    def set(self, first_row_id: int, lists) -> None:
+        """Rows [first_row_id, first_row_id + len(lists)) of the column; rows between its old end and first_row_id become
+        NULL rows."""
+        off, vals = _tags_csr(lists)
+        _ffi.check(_ffi.lib().tsh_tags_set(self.handle(), int(first_row_id), off.shape[0] - 1, off.ctypes.data_as(_ffi.p_i64),
+                                           vals.ctypes.data_as(_ffi.p_i64) if vals.shape[0] else None))
+
+    def close(self) -> None:
+        if self._h:
+            _ffi.lib().tsh_tags_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipVectorIndex:
     """Owner of one `tsh_index*`.  Destroy exactly once (close / context manager)."""
 
@@ -339,6 +429,20 @@ class HipVectorIndex:
         terms over 8 attributes and 4096 set values in one call; more is chained through `with_mask`.  A snapshot, as
         `make_mask_where`'s."""
         return HipMask._where_clauses(self, clauses, with_mask, combine)
+
+    def make_tags(self, lists) -> "HipTags":
+        """An array-valued attribute column on the device: `lists` is a list of iterables of int64 (entry i: the set of
+        GLOBAL row id i; one that holds ATTR_NULL: no value) or an `(offsets, values)` CSR pair."""
+        return HipTags(self, lists)
+
+    def make_mask_tags(self, tags: "HipTags", values, need="any", negate: bool = False, with_mask: Optional["HipMask"] = None,
+                       combine="and") -> "HipMask":
+        """A mask handle made ON the device from one HAS ANY / HAS ALL term (`tsh_mask_create_tags`): keeps the rows whose
+        set is not NULL and for which (the row holds at least t distinct values of `values`) != negate -- t is 1 for
+        need="any", the number of distinct values for need="all", or the count given -- and-ed / or-ed (`combine`) with
+        `with_mask` when one is given.  At most 4096 distinct values; scalar clauses are chained through `with_mask`.  A
+        snapshot: later `tags.set()` calls and appends do not change it."""
+        return HipMask._tags(self, tags, values, need, negate, with_mask, combine)
 
     def _live_masks(self) -> "weakref.WeakSet":
         """The masks and groups handles made for this index and not yet closed: close() closes them before it destroys

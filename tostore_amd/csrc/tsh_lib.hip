@@ -52,6 +52,7 @@
 #include "tsh_scan_i8_band.h"
 #include "tsh_scan_i4.hip.h"
 #include "tsh_where.hip.h"
+#include "tsh_tags.hip.h"
 
 using namespace tsh;
 
@@ -1026,6 +1027,23 @@ struct AttrPart {
   std::atomic<int64_t> built_rows{-1};
   int64_t *d_vals = nullptr;
   int64_t cap = 0;
+};
+
+// ---- tag handles (tsh_tags_create, include/tostore_hip.h): one shard's part --------------------------------------------
+// The handle's normalised CSR sliced to this shard's rows on the device (tsh_tags_plan.h, tags_slice): rows + 1 32-bit
+// offsets rebased to the slice's first value, the values, and the valid words (bit r of word t: local row 64 t + r
+// exists in the column and is not NULL), for the rows the shard had when the part was built.  A mask made from the
+// handle (tsh_mask_create_tags) that finds the shard grown, or the column changed by tsh_tags_set (built_rows = -1),
+// rebuilds it first (tags_part).  4 B per row + 8 B per value + 8 B per 64 rows.
+struct TagsPart {
+  int device = 0;
+  std::atomic<int64_t> built_rows{-1};
+  uint32_t *d_off = nullptr;
+  int64_t off_cap = 0;
+  int64_t *d_vals = nullptr;
+  int64_t vals_cap = 0;
+  uint64_t *d_valid = nullptr;
+  int64_t valid_cap = 0;
 };
 
 // One query in flight on one context.  Its three kernels (scan, select,
@@ -2783,6 +2801,7 @@ struct tsh_index {
   std::vector<tsh_mask *> masks;  // live mask handles made for this index (guarded by g_mask_mu): orphaned by destroy
   std::vector<struct tsh_groups *> groups;  // ... and live groups handles, the same way
   std::vector<struct tsh_attr *> attrs;     // ... and live attribute handles
+  std::vector<struct tsh_tags *> tags;      // ... and live tag handles
   std::unique_ptr<ShardWorkers> workers;  // multi-device handles: one persistent host thread per further shard
   // result-block buffers of multi-query calls, kept between calls: a fresh 6 MB allocation per call spends
   // ~0.3 ms in page faults when it is first written
@@ -2946,6 +2965,15 @@ struct tsh_attr {
   std::shared_mutex use_mu;     // tsh_mask_create_range / _where: shared, for the whole call; tsh_attr_set: exclusive
   std::mutex mu;                // builds / rebuilds of the parts
   std::vector<std::unique_ptr<AttrPart>> parts;  // one per shard of the index
+};
+
+// ---- tag handles ------------------------------------------------------------------------------------------------------
+struct tsh_tags {
+  tsh_index *idx = nullptr;     // nullptr: orphaned -- its index was destroyed first (parts freed then)
+  TagsColumn col;               // the caller's column by GLOBAL row id, normalised (tsh_tags_plan.h): the parts are sliced from it
+  std::shared_mutex use_mu;     // tsh_mask_create_tags: shared, for the whole call; tsh_tags_set: exclusive
+  std::mutex mu;                // builds / rebuilds of the parts
+  std::vector<std::unique_ptr<TagsPart>> parts;  // one per shard of the index
 };
 
 namespace {
@@ -3263,6 +3291,116 @@ int mask_where_part(MaskPart *p, Shard *s, const WherePlan &plan, const AttrPart
   return mask_finish_part(p, s, rows, n_tiles);
 }
 
+void tags_part_free(TagsPart *p) {
+  if (hipSetDevice(p->device) != hipSuccess) return;
+  hipFree(p->d_off);
+  hipFree(p->d_vals);
+  hipFree(p->d_valid);
+  p->d_off = nullptr;
+  p->d_vals = nullptr;
+  p->d_valid = nullptr;
+  p->off_cap = p->vals_cap = p->valid_cap = 0;
+  p->built_rows.store(-1);
+}
+
+// (Re)builds one shard's part for the rows the shard has now: the slice of the handle's column (tags_slice: rebased
+// offsets, the value span as it lies in the handle's copy, the valid words; rows beyond the column are empty spans with
+// valid bit 0).  A slice of more than 2^31 - 1 values is refused before anything is allocated.  Caller holds s->mu
+// shared, t->use_mu (shared or exclusive) and t->mu
+int tags_build_part(tsh_tags *t, TagsPart *p, Shard *s) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  const int64_t rows = s->rows;
+  TagsSlice sl;
+  try {
+    if (const int e = tags_slice(t->col, s->row_base, rows, &sl)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for the offsets of %lld rows", (long long)rows);
+  }
+  const int64_t n_tiles = (int64_t)sl.valid.size();
+  if (rows + 1 > p->off_cap) {
+    hipFree(p->d_off);
+    p->d_off = nullptr;
+    p->off_cap = 0;
+    const int64_t want = round_up(rows + 1 + rows / 8, 1024);
+    HIPCHK(hipMalloc(&p->d_off, (size_t)want * sizeof(uint32_t)));
+    p->off_cap = want;
+  }
+  if (sl.n_vals > p->vals_cap) {
+    hipFree(p->d_vals);
+    p->d_vals = nullptr;
+    p->vals_cap = 0;
+    const int64_t want = round_up(sl.n_vals + sl.n_vals / 8, 1024);
+    HIPCHK(hipMalloc(&p->d_vals, (size_t)want * sizeof(int64_t)));
+    p->vals_cap = want;
+  }
+  if (n_tiles > p->valid_cap) {
+    hipFree(p->d_valid);
+    p->d_valid = nullptr;
+    p->valid_cap = 0;
+    const int64_t want = round_up(n_tiles + n_tiles / 8, 64);
+    HIPCHK(hipMalloc(&p->d_valid, (size_t)want * sizeof(uint64_t)));
+    p->valid_cap = want;
+  }
+  hipStream_t st = s->aux_stream;
+  HIPCHK(hipMemcpyAsync(p->d_off, sl.off.data(), (size_t)(rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (sl.n_vals > 0)
+    HIPCHK(hipMemcpyAsync(p->d_vals, sl.vals, (size_t)sl.n_vals * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (n_tiles > 0)
+    HIPCHK(hipMemcpyAsync(p->d_valid, sl.valid.data(), (size_t)n_tiles * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  p->built_rows.store(rows, std::memory_order_release);
+  return TSH_OK;
+}
+
+// shard g's part of a tag handle, current for the rows the shard has (caller holds s->mu shared and h->use_mu shared);
+// nullptr + *rc on failure.  As attr_part: appends take the shard exclusively, tsh_tags_set the handle, so no kernel
+// reads the buffers while they are rebuilt
+const TagsPart *tags_part(tsh_tags *h, size_t g, Shard *s, int *rc) {
+  *rc = TSH_OK;
+  TagsPart *p = h->parts[g].get();
+  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
+    *rc = tags_build_part(h, p, s);
+    if (*rc) return nullptr;
+  }
+  return p;
+}
+
+// ... and the words of a HAS ANY / HAS ALL term over a tag column (tsh_mask_create_tags): one launch of mask_tags_kernel
+// (tsh_tags.hip.h) over the shard's part of the column, one copy of the words back, one mask_finish_part.  The term's set
+// goes up in one copy ahead of the launch, into the tail of the part's own word allocation, as W2's sets do.  q.set
+// outlives the synchronise below.  Locks as for mask_range_part, the tag handle's use_mu shared
+int mask_tags_part(MaskPart *p, Shard *s, const TagsPart *tp, const TagsQuery &q, bool negate, const MaskPart *wp,
+                   int32_t combine) {
+  HIPCHK(hipSetDevice(s->device));
+  p->device = s->device;
+  const int64_t rows = s->rows;
+  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
+  const int32_t n_set = (int32_t)q.set.size();
+  try {
+    p->h_words.assign((size_t)n_tiles, 0);
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for %d mask words", n_tiles);
+  }
+  int rc = mask_reserve_words(p, n_tiles + (n_tiles > 0 ? n_set : 0));
+  if (rc) return rc;
+  if (n_tiles > 0) {
+    hipStream_t st = s->aux_stream;
+    int64_t *d_set = reinterpret_cast<int64_t *>(p->d_words + n_tiles);
+    if (n_set > 0) HIPCHK(hipMemcpyAsync(d_set, q.set.data(), (size_t)n_set * 8, hipMemcpyHostToDevice, st));
+    // (tp and wp were built for the same rows: rows + 1 offsets, n_tiles valid words, n_tiles words of wp)
+    mask_tags_kernel<<<where_grid(n_tiles), WHERE_BLOCK, (size_t)n_set * 8, st>>>(
+        tp->d_off, tp->d_vals, tp->d_valid, rows, n_tiles, d_set, n_set, (uint32_t)q.t, negate ? 1 : 0,
+        wp ? wp->d_words : nullptr, combine, p->d_words);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return mask_finish_part(p, s, rows, n_tiles);
+}
+
 // A part's words put back where slice_mask would take them from: bit r of the words = bit row_base + r of the GLOBAL
 // bitmap (bits holds at least (row_base + rows + 7) / 8 + 1 bytes; or-ed in: neighbouring shards may share a byte)
 void unslice_mask(int64_t row_base, int64_t rows, const uint64_t *words, uint8_t *bits) {
@@ -3484,6 +3622,11 @@ int32_t tsh_index_destroy(tsh_index *idx) {
       a->idx = nullptr;
     }
     idx->attrs.clear();
+    for (tsh_tags *t : idx->tags) {  // ... and tag handles
+      for (auto &p : t->parts) tags_part_free(p.get());
+      t->idx = nullptr;
+    }
+    idx->tags.clear();
   }
   idx->workers.reset();  // joins the shard threads
   for (auto &s : idx->shards) {
@@ -4411,6 +4554,150 @@ int32_t tsh_mask_create_where(tsh_index *idx, const void *terms_p, int32_t n_ter
       try {
         const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
         if (m->bits.size() < need) m->bits.resize(need, 0);
+      } catch (...) {
+        rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
+        break;
+      }
+      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
+    }
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    for (auto &p : m->parts) mask_part_free(p.get());
+    g_err = keep;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->masks.push_back(m.get());
+  }
+  *out = m.release();
+  return TSH_OK;
+}
+
+// ---- tag columns: an array-valued WHERE term made into a mask handle on the device (tsh_tags.hip.h) ----------------------
+// Modelled on the attribute entries above line for line; the column's normalisation, tsh_tags_set's splice, the slices and
+// the term's set are tsh_tags_plan.h's.  (The tag handle travels as void *, and create's out as the address of one)
+int32_t tsh_tags_create(tsh_index *idx, const int64_t *offsets, int64_t n, const int64_t *values, void *out_p) {
+  tsh_tags **out = static_cast<tsh_tags **>(out_p);
+  if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (const int e = tags_check_csr(offsets, n, values)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+  if (!idx && device_count_cached() <= 0) return set_err(TSH_E_NO_DEVICE, "no HIP device available");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  std::unique_ptr<tsh_tags> t(new tsh_tags());
+  t->idx = idx;
+  try {
+    if (const int e = tags_normalise(offsets, n, values, &t->col)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for the tag lists of %lld rows", (long long)n);
+  }
+  // (a slice too large for the parts' 32-bit offsets is refused before any device work)
+  for (size_t i = 0; i < idx->shards.size(); ++i) {
+    Shard *s = idx->shards[i].get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    if (!tags_slice_fits(tags_slice_values(t->col, s->row_base, s->rows)))
+      return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(TAGS_PLAN_SLICE_VALUES));
+  }
+  for (size_t i = 0; i < idx->shards.size(); ++i) t->parts.emplace_back(new TagsPart());
+  int rc = TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(t->mu);
+    for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
+      Shard *s = idx->shards[i].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      rc = tags_build_part(t.get(), t->parts[i].get(), s);
+    }
+  }
+  if (rc) {
+    const std::string keep = g_err;
+    for (auto &p : t->parts) tags_part_free(p.get());
+    g_err = keep;
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    idx->tags.push_back(t.get());
+  }
+  *out = t.release();
+  return TSH_OK;
+}
+
+int32_t tsh_tags_set(void *tags, int64_t first_row_id, int64_t n, const int64_t *offsets, const int64_t *values) {
+  tsh_tags *t = static_cast<tsh_tags *>(tags);
+  if (!t) return set_err(TSH_E_BAD_ARG, "tags is NULL");
+  if (first_row_id < 0) return set_err(TSH_E_BAD_ARG, "first_row_id < 0");
+  if (const int e = tags_check_csr(offsets, n, values)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+  std::lock_guard<std::mutex> hold(g_mask_mu);  // (the index cannot be destroyed under the call)
+  tsh_index *idx = t->idx;
+  if (!idx) return set_err(TSH_E_BAD_ARG, "the tag handle's index was destroyed");
+  if (n == 0) return TSH_OK;
+  std::lock_guard<std::mutex> lk(idx->mu);  // as an append does
+  std::unique_lock<std::shared_mutex> xl(t->use_mu);
+  try {
+    if (const int e = tags_splice(&t->col, first_row_id, n, offsets, values)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for the tag lists of %lld rows", (long long)(first_row_id + n));
+  }
+  for (auto &p : t->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next mask made of each shard
+  return TSH_OK;
+}
+
+int32_t tsh_tags_destroy(void *tags) {
+  tsh_tags *t = static_cast<tsh_tags *>(tags);
+  if (!t) return TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    if (tsh_index *idx = t->idx) {  // (an orphan's parts went with its index)
+      idx->tags.erase(std::remove(idx->tags.begin(), idx->tags.end(), t), idx->tags.end());
+      for (auto &p : t->parts) tags_part_free(p.get());
+    }
+  }
+  delete t;
+  return TSH_OK;
+}
+
+// Modelled on tsh_mask_create_range line for line; what differs is the term's set in front (tags_query) and the part it
+// reads.  Everything that can be refused on the arguments is refused before any device work
+int32_t tsh_mask_create_tags(tsh_index *idx, void *tags_p, const int64_t *set, int64_t n_set, int32_t need, int32_t negate,
+                             tsh_mask *with, int32_t combine, tsh_mask **out) {
+  tsh_tags *tags = static_cast<tsh_tags *>(tags_p);
+  if (!out) return set_err(TSH_E_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (combine != TSH_MASK_AND && combine != TSH_MASK_OR) return set_err(TSH_E_BAD_ARG, "combine %d is neither TSH_MASK_AND nor TSH_MASK_OR", combine);
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (!tags) return set_err(TSH_E_BAD_ARG, "tags is NULL");
+  TagsQuery q;
+  try {
+    if (const int e = tags_query(set, n_set, need, &q)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for the term's set");
+  }
+  if (tags->idx != idx) return set_err(TSH_E_BAD_ARG, "the tag handle was made for another index (or its index was destroyed)");
+  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
+  std::unique_ptr<tsh_mask> m(new tsh_mask());
+  m->idx = idx;
+  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
+  int rc = TSH_OK;
+  {
+    // the column stays as it is until every part is made (given up before g_mask_mu is taken below: tsh_tags_set holds
+    // that one while it waits for this one)
+    std::shared_lock<std::shared_mutex> use(tags->use_mu);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
+      Shard *s = idx->shards[g].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      const TagsPart *tp = tags_part(tags, g, s, &rc);
+      if (!tp) break;
+      const MaskPart *wp = with ? mask_part(with, g, s, &rc) : nullptr;
+      if (with && !wp) break;
+      MaskPart *p = m->parts[g].get();
+      rc = mask_tags_part(p, s, tp, q, negate != 0, wp, combine);
+      if (rc) break;
+      // the handle's GLOBAL bitmap, as for a range-made handle
+      try {
+        const size_t need_bytes = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
+        if (m->bits.size() < need_bytes) m->bits.resize(need_bytes, 0);
       } catch (...) {
         rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
         break;

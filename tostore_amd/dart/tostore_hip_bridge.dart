@@ -81,6 +81,16 @@ typedef _MaskReadC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Int64);
 typedef _MaskReadD = int Function(Pointer<Void>, Pointer<Uint8>, int);
 typedef _MaskCreateWhereC = Int32 Function(Pointer<Void>, Pointer<Void>, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
 typedef _MaskCreateWhereD = int Function(Pointer<Void>, Pointer<Void>, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
+typedef _TagsCreateC = Int32 Function(Pointer<Void>, Pointer<Int64>, Int64, Pointer<Int64>, Pointer<Void>);
+typedef _TagsCreateD = int Function(Pointer<Void>, Pointer<Int64>, int, Pointer<Int64>, Pointer<Void>);
+typedef _TagsSetC = Int32 Function(Pointer<Void>, Int64, Int64, Pointer<Int64>, Pointer<Int64>);
+typedef _TagsSetD = int Function(Pointer<Void>, int, int, Pointer<Int64>, Pointer<Int64>);
+typedef _TagsDestroyC = Int32 Function(Pointer<Void>);
+typedef _TagsDestroyD = int Function(Pointer<Void>);
+typedef _MaskCreateTagsC = Int32 Function(
+    Pointer<Void>, Pointer<Void>, Pointer<Int64>, Int64, Int32, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
+typedef _MaskCreateTagsD = int Function(
+    Pointer<Void>, Pointer<Void>, Pointer<Int64>, int, int, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
 typedef _SearchMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double,
     Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, double,
@@ -510,6 +520,10 @@ final class HipVectorBackend {
   static late final _MaskCreateRangeD _maskCreateRange;
   static late final _MaskReadD _maskRead;
   static late final _MaskCreateWhereD _maskCreateWhere;
+  static late final _TagsCreateD _tagsCreate;
+  static late final _TagsSetD _tagsSet;
+  static late final _TagsDestroyD _tagsDestroy;
+  static late final _MaskCreateTagsD _maskCreateTags;
   static late final _SearchMaskedD _searchMasked;
   static late final _SubmitMaskedD _submitMasked;
 
@@ -624,6 +638,10 @@ final class HipVectorBackend {
       _maskCreateRange = lib.lookupFunction<_MaskCreateRangeC, _MaskCreateRangeD>('tsh_mask_create_range');
       _maskRead = lib.lookupFunction<_MaskReadC, _MaskReadD>('tsh_mask_read');
       _maskCreateWhere = lib.lookupFunction<_MaskCreateWhereC, _MaskCreateWhereD>('tsh_mask_create_where');
+      _tagsCreate = lib.lookupFunction<_TagsCreateC, _TagsCreateD>('tsh_tags_create');
+      _tagsSet = lib.lookupFunction<_TagsSetC, _TagsSetD>('tsh_tags_set');
+      _tagsDestroy = lib.lookupFunction<_TagsDestroyC, _TagsDestroyD>('tsh_tags_destroy');
+      _maskCreateTags = lib.lookupFunction<_MaskCreateTagsC, _MaskCreateTagsD>('tsh_mask_create_tags');
       _searchMasked = lib.lookupFunction<_SearchMaskedC, _SearchMaskedD>('tsh_search_masked');
       _submitMasked =
           lib.lookupFunction<_SubmitMaskedC, _SubmitMaskedD>('tsh_search_submit_masked');
@@ -872,6 +890,66 @@ final class HipVectorBackend {
       calloc.free(out);
     }
   }
+
+  /// One array-valued attribute of every node id, kept on the device as CSR (tsh_tags_create): entry i of `lists` is the
+  /// set of node id i -- the group ids of an ACL, tags, labels; strings go in through a dictionary of the caller's.  A
+  /// list that holds [HipRowAttr.nullValue] makes the row a NULL row, as a row beyond `lists` is; an empty list is the
+  /// empty set, not NULL.  The column crosses the FFI boundary once; [HipTagColumn.set] extends it as rows are appended.
+  /// Dispose it before this backend.
+  HipTagColumn? createTags(List<List<int>> lists) {
+    final csr = HipTagColumn._csr(lists);
+    final out = calloc<Pointer<Void>>();
+    try {
+      final rc = _tagsCreate(_handle, csr.offsets, lists.length, csr.values, out.cast<Void>());
+      if (rc != 0) {
+        Logger.warn('tsh_tags_create failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return HipTagColumn._(out.value);
+    } finally {
+      csr.free();
+      calloc.free(out);
+    }
+  }
+
+  /// A mask made ON the device from one HAS ANY / HAS ALL term over a tag column (tsh_mask_create_tags): keeps the node
+  /// ids whose set is not NULL and for which (the row holds at least t distinct values of `values`) != negate, t being
+  /// the number of distinct values for `need` == [tagsAll], else `need` ([tagsAny] is 1); and-ed (or, with `or: true`,
+  /// or-ed) with `withMask` when one is given.  At most [tagsMaxSetValues] distinct values.  `tenant = 7 AND acl HAS ANY
+  /// (...)` is [createMaskWhereClauses] and then this call with its mask as `withMask`.  A snapshot, as
+  /// [createMaskWhere]'s.  Null on any native failure; a disposed [HipTagColumn] or `withMask` is refused (null, with a
+  /// warning), never sent as NULL.
+  HipRowMask? createMaskTags(HipTagColumn tags, Int64List values,
+      {int need = tagsAny, bool negate = false, HipRowMask? withMask, bool or = false}) {
+    if (tags._tags == nullptr) {
+      Logger.warn('createMaskTags with a disposed HipTagColumn', label: 'HipVectorBackend');
+      return null;
+    }
+    if (withMask != null && withMask._mask == nullptr) {
+      Logger.warn('createMaskTags with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    final buf = calloc<Int64>(values.isEmpty ? 1 : values.length);
+    final out = calloc<Pointer<Void>>();
+    try {
+      buf.asTypedList(values.length).setAll(0, values);
+      final rc = _maskCreateTags(
+          _handle, tags._tags, buf, values.length, need, negate ? 1 : 0, withMask?._mask ?? nullptr, or ? 1 : 0, out);
+      if (rc != 0) {
+        Logger.warn('tsh_mask_create_tags failed ($rc): ${_errorText()}', label: 'HipVectorBackend');
+        return null;
+      }
+      return HipRowMask._(out.value);
+    } finally {
+      calloc.free(buf);
+      calloc.free(out);
+    }
+  }
+
+  /// TSH_TAGS_ALL / TSH_TAGS_ANY and the limit of one tsh_mask_create_tags call (include/tostore_hip.h).
+  static const int tagsAll = 0;
+  static const int tagsAny = 1;
+  static const int tagsMaxSetValues = 4096;
 
   /// TSH_TERM_RANGE / TSH_TERM_IN and the limits of one tsh_mask_create_where call (include/tostore_hip.h).
   static const int termRange = 0;
@@ -2135,6 +2213,11 @@ final class HipRowMask {
           {HipRowMask? withMask, bool or = false}) =>
       backend.createMaskWhereClauses(clauses, withMask: withMask, or: or);
 
+  /// [HipVectorBackend.createMaskTags] by its other name: the mask of one HAS ANY / HAS ALL term over a tag column.
+  static HipRowMask? hasTags(HipVectorBackend backend, HipTagColumn tags, Int64List values,
+          {int need = HipVectorBackend.tagsAny, bool negate = false, HipRowMask? withMask, bool or = false}) =>
+      backend.createMaskTags(tags, values, need: need, negate: negate, withMask: withMask, or: or);
+
   /// The first `nBytes` bytes of the mask's bitmap as it stands (tsh_mask_read): bit i (LSB first) = node id i, bytes
   /// past what the mask knows read 0.  Null on failure, or on a disposed mask.
   Uint8List? readBits(int nBytes) {
@@ -2193,6 +2276,65 @@ final class HipRowAttr {
     if (_attr != nullptr) {
       HipVectorBackend._attrDestroy(_attr);
       _attr = nullptr;
+    }
+  }
+}
+
+/// A caller's lists as the native CSR: `offsets` (lists.length + 1 entries from 0) and `values`, both on the C heap.
+final class _TagCsr {
+  final Pointer<Int64> offsets;
+  final Pointer<Int64> values;
+  _TagCsr(this.offsets, this.values);
+
+  void free() {
+    calloc.free(offsets);
+    calloc.free(values);
+  }
+}
+
+/// One array-valued attribute of every node id ([HipVectorBackend.createTags], tsh_tags_create), kept on the device as
+/// CSR for as many [HipVectorBackend.createMaskTags] calls as it serves.  [set] overwrites or extends a range of rows,
+/// the companion of the append feed.  Dispose it before its backend; a disposed column is refused by
+/// [HipVectorBackend.createMaskTags] (null, with a warning), and one whose backend was disposed first is orphaned by
+/// the library and still safe to dispose.  Masks made from it outlive it.
+final class HipTagColumn {
+  Pointer<Void> _tags;
+
+  HipTagColumn._(this._tags);
+
+  static _TagCsr _csr(List<List<int>> lists) {
+    var total = 0;
+    for (final l in lists) {
+      total += l.length;
+    }
+    final offsets = calloc<Int64>(lists.length + 1);
+    final values = calloc<Int64>(total == 0 ? 1 : total);
+    var at = 0;
+    for (var i = 0; i < lists.length; i++) {
+      for (final v in lists[i]) {
+        values[at++] = v;
+      }
+      offsets[i + 1] = at;
+    }
+    return _TagCsr(offsets, values);
+  }
+
+  /// Rows [firstNodeId, firstNodeId + lists.length) of the column; rows between its old end and firstNodeId become NULL
+  /// rows.  False on failure (or on a disposed column).
+  bool set(int firstNodeId, List<List<int>> lists) {
+    if (_tags == nullptr) return false;
+    final csr = _csr(lists);
+    try {
+      return HipVectorBackend._tagsSet(_tags, firstNodeId, lists.length, csr.offsets, csr.values) == 0;
+    } finally {
+      csr.free();
+    }
+  }
+
+  void dispose() {
+    if (_tags != nullptr) {
+      HipVectorBackend._tagsDestroy(_tags);
+      _tags = nullptr;
     }
   }
 }
