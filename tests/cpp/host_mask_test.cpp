@@ -1,5 +1,5 @@
 // A caller's row mask sliced to one shard (tostore_amd/csrc/tsh_host_sync.h slice_mask, mask_kept_rows, popcount_words,
-// list_mask_bits) on every row base 0..71 and a few large ones, every shard length 1..200 and a few around 4096 and
+// list_mask_bits) and put back (unslice_mask) on every row base 0..71 and a few large ones, every shard length 1..200 and a few around 4096 and
 // 65536, with the shard's range zero, all ones or random and the bits around it set (or, for the last kind, clear).
 // argv[1]: the random range content (bit i of the file = bit i of the range), argv[2]: where the results go -- one
 // record per case, int64 {row_base, rows, kind, popcount, kept, listed, sum of ids, sum of (position + 1) * id} then
@@ -9,6 +9,46 @@
 #include <vector>
 
 #include "../../tostore_amd/csrc/tsh_host_sync.h"
+
+// unslice_mask, slice_mask's other half: the sliced words of [base, base + rows) put back into a zeroed bitmap of
+// (base + rows + 7) / 8 + 1 bytes between canaries must give the source's bits inside the range and nothing outside it;
+// then an adjacent range of 37 ones into the same bitmap, grown as a handle's is, must leave every bit of the first
+// (the shared byte is or-ed).  Returns what is wrong, or nullptr.
+static const char *unslice_check(int64_t base, int64_t rows, const uint8_t *src, const uint64_t *words) {
+  const size_t PAD = 16;
+  const uint8_t CAN = 0xC5;
+  const int64_t rows2 = 37, end = base + rows, end2 = end + rows2;
+  const size_t n1 = (size_t)((end + 7) / 8) + 1, n2 = (size_t)((end2 + 7) / 8) + 1;
+  static std::vector<uint8_t> buf;
+  buf.assign(PAD + n2 + PAD, CAN);
+  uint8_t *bits = buf.data() + PAD;
+  auto bit = [](const uint8_t *b, int64_t i) { return (b[i >> 3] >> (i & 7)) & 1; };
+  // the bits of [0, n_bits) against: zero below `base`, the source in the first range, `second` in the second, zero after
+  auto holds = [&](size_t n_bytes, int second) {
+    for (int64_t i = 0; i < (int64_t)n_bytes * 8; ++i) {
+      const int want = i < base ? 0 : i < end ? bit(src, i) : i < end2 ? second : 0;
+      if (bit(bits, i) != want) return false;
+    }
+    return true;
+  };
+  auto canaries = [&](size_t n_bytes) {
+    for (size_t i = 0; i < PAD; ++i)
+      if (buf[i] != CAN) return false;
+    for (size_t i = PAD + n_bytes; i < buf.size(); ++i)
+      if (buf[i] != CAN) return false;
+    return true;
+  };
+  memset(bits, 0, n1);
+  tsh::unslice_mask(base, rows, words, bits);
+  if (!canaries(n1)) return "wrote outside the bitmap";
+  if (!holds(n1, 0)) return "the bitmap is not the source's range and zero around it";
+  memset(bits + n1, 0, n2 - n1);
+  const uint64_t ones = (1ull << rows2) - 1;
+  tsh::unslice_mask(end, rows2, &ones, bits);
+  if (!canaries(n2)) return "the adjacent range wrote outside the bitmap";
+  if (!holds(n2, 1)) return "the adjacent range did not leave the first as it was";
+  return nullptr;
+}
 
 int main(int argc, char **argv) {
   if (argc != 3) return 2;
@@ -62,6 +102,10 @@ int main(int argc, char **argv) {
                     (long long)rows, kind);
             return 1;
           }
+        if (const char *what = unslice_check(base, rows, g.data(), words.data())) {
+          fprintf(stderr, "unslice_mask: %s: base %lld rows %lld kind %d\n", what, (long long)base, (long long)rows, kind);
+          return 1;
+        }
         const int64_t rec[8] = {base, rows, kind, pop, kept, (int64_t)listed, (int64_t)sum, (int64_t)wsum};
         fwrite(rec, sizeof(rec), 1, out);
         fwrite(words.data(), 8, (size_t)n_words, out);

@@ -33,7 +33,35 @@ def _f32c(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class HipMask:
+class _HipHandle:
+    """What the device-resident handles share (`HipMask`, `HipGroups`, `HipAttr`, `HipTags`): `_h`, the library's pointer,
+    NULL once closed; `_destroy`, the name of the library's destroy function; `_closed`, what `handle()` says then."""
+    _destroy = _closed = ""
+
+    def handle(self):
+        """The pointer to pass to the library; ValueError once the handle (or its index) was closed."""
+        if not self._h:
+            raise ValueError(self._closed)
+        return self._h
+
+    def close(self) -> None:
+        if self._h:
+            getattr(_ffi.lib(), self._destroy)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+class HipMask(_HipHandle):
     """A WHERE row set that lives on the device (`tsh_mask*`, include/tostore_hip.h): the keep bitmap is uploaded once
     and -- when it is selective -- compacted into the list of kept row ids on the device; searches that pass the
     handle (`HipVectorIndex.search(..., row_mask=handle)`) do no host work on the mask.  The natural row sets are the
@@ -42,6 +70,7 @@ class HipMask:
     (/root/reference/lib/src/core/ngh_page.dart:105-108).  Rows appended after the mask was made are not kept; rows
     deleted later are dropped as always.  Destroy before the index (close / context manager); an index that is closed
     first closes its masks, and a closed mask is refused by every search (ValueError), never taken for "no filter"."""
+    _destroy, _closed = "tsh_mask_destroy", "the mask is closed (or its index was)"
 
     def __init__(self, index: "HipVectorIndex", bits):
         bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
@@ -128,12 +157,6 @@ class HipMask:
         index._live_masks().add(self)
         return self
 
-    def handle(self):
-        """The `tsh_mask*` to pass to the library; ValueError once the mask (or its index) was closed."""
-        if not self._h:
-            raise ValueError("the mask is closed (or its index was)")
-        return self._h
-
     def bits(self, n_bytes: Optional[int] = None) -> np.ndarray:
         """The handle's GLOBAL bitmap as it stands (`tsh_mask_read`): bit i, LSB first, = row id i; uint8, by default
         one bit per row id the index holds now.  Bytes past what the handle knows read 0."""
@@ -150,30 +173,14 @@ class HipMask:
             _ffi.check(int(n))
         return int(n)
 
-    def close(self) -> None:
-        if self._h:
-            _ffi.lib().tsh_mask_destroy(self._h)
-            self._h = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipGroups:
+class HipGroups(_HipHandle):
     """The group of every row (`tsh_groups*`, include/tostore_hip.h), for `HipVectorIndex.search_grouped`: entry i of
     `group_of` (int32) is the group of GLOBAL row id i -- a document, a video, a product --, at least 0 and below
     `n_groups`, or negative for a row that stands for itself.  Rows beyond the array are ungrouped; `set()` extends or
     overwrites a range, as the append feed does for the rows.  An index that is closed first closes its groups, and a
     closed handle is refused by every search (ValueError)."""
+    _destroy, _closed = "tsh_groups_destroy", "the groups handle is closed (or its index was)"
 
     def __init__(self, index: "HipVectorIndex", group_of, n_groups: int):
         g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
@@ -187,12 +194,6 @@ class HipGroups:
         self.group_of = g.copy()
         index._live_masks().add(self)
 
-    def handle(self):
-        """The `tsh_groups*` to pass to the library; ValueError once the handle (or its index) was closed."""
-        if not self._h:
-            raise ValueError("the groups handle is closed (or its index was)")
-        return self._h
-
     def set(self, first_row_id: int, group_of) -> None:
         """Entries [first_row_id, first_row_id + len(group_of)) of the array, extended where it was shorter."""
         g = np.ascontiguousarray(group_of, dtype=np.int32).reshape(-1)
@@ -201,23 +202,6 @@ class HipGroups:
         if g.shape[0] and end > self.group_of.shape[0]:
             self.group_of = np.concatenate([self.group_of, np.full(end - self.group_of.shape[0], -1, dtype=np.int32)])
         self.group_of[int(first_row_id):end] = g
-
-    def close(self) -> None:
-        if self._h:
-            _ffi.lib().tsh_groups_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 ATTR_NULL = _ffi.TSH_ATTR_NULL
@@ -255,12 +239,13 @@ def f64_order_key(a) -> np.ndarray:
     return np.where(b >= 0, b, b ^ np.int64(0x7FFFFFFFFFFFFFFF))
 
 
-class HipAttr:
+class HipAttr(_HipHandle):
     """One scalar attribute of every row, kept on the device (`tsh_attr*`, include/tostore_hip.h), for
     `HipVectorIndex.make_mask_where`: entry i of `values` (int64) belongs to GLOBAL row id i; `ATTR_NULL` says the row
     has no value, and rows beyond the array read as NULL.  `set()` extends or overwrites a range, as the append feed does
     for the rows.  Doubles go in by `f64_order_key`.  An index that is closed first closes its attributes, and a closed
     handle is refused (ValueError)."""
+    _destroy, _closed = "tsh_attr_destroy", "the attribute handle is closed (or its index was)"
 
     def __init__(self, index: "HipVectorIndex", values):
         v = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
@@ -269,33 +254,10 @@ class HipAttr:
         _ffi.check(_ffi.lib().tsh_attr_create(index._h, v.ctypes.data_as(_ffi.p_i64), v.shape[0], ctypes.byref(self._h)))
         index._live_masks().add(self)
 
-    def handle(self):
-        """The `tsh_attr*` to pass to the library; ValueError once the handle (or its index) was closed."""
-        if not self._h:
-            raise ValueError("the attribute handle is closed (or its index was)")
-        return self._h
-
     def set(self, first_row_id: int, values) -> None:
         """Entries [first_row_id, first_row_id + len(values)) of the column, extended with NULLs where it was shorter."""
         v = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
         _ffi.check(_ffi.lib().tsh_attr_set(self.handle(), int(first_row_id), v.shape[0], v.ctypes.data_as(_ffi.p_i64)))
-
-    def close(self) -> None:
-        if self._h:
-            _ffi.lib().tsh_attr_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _tags_csr(lists):
@@ -315,13 +277,14 @@ def _tags_csr(lists):
     return off, np.ascontiguousarray(vals, dtype=np.int64)
 
 
-class HipTags:
+class HipTags(_HipHandle):
     """One array-valued attribute of every row, kept on the device as CSR (`tsh_tags*`, include/tostore_hip.h), for
     `HipVectorIndex.make_mask_tags`: row i holds a SET of int64 values (group ids of an ACL, tags, labels; strings go in
     through a dictionary of the caller's).  `lists` is a list of iterables, one per GLOBAL row id, or an
     `(offsets, values)` pair.  A list that holds `ATTR_NULL` makes the row a NULL row, as a row beyond the column is; an
     empty list is the empty set, not NULL.  `set()` overwrites or extends a range of rows, as the append feed does for the
     rows.  An index that is closed first closes its tag columns, and a closed handle is refused (ValueError)."""
+    _destroy, _closed = "tsh_tags_destroy", "the tags handle is closed (or its index was)"
 
     def __init__(self, index: "HipVectorIndex", lists):
         off, vals = _tags_csr(lists)
@@ -331,35 +294,12 @@ class HipTags:
                                               vals.ctypes.data_as(_ffi.p_i64) if vals.shape[0] else None, ctypes.byref(self._h)))
         index._live_masks().add(self)
 
-    def handle(self):
-        """The `tsh_tags*` to pass to the library; ValueError once the handle (or its index) was closed."""
-        if not self._h:
-            raise ValueError("the tags handle is closed (or its index was)")
-        return self._h
-
     def set(self, first_row_id: int, lists) -> None:
         """Rows [first_row_id, first_row_id + len(lists)) of the column; rows between its old end and first_row_id become
         NULL rows."""
         off, vals = _tags_csr(lists)
         _ffi.check(_ffi.lib().tsh_tags_set(self.handle(), int(first_row_id), off.shape[0] - 1, off.ctypes.data_as(_ffi.p_i64),
                                            vals.ctypes.data_as(_ffi.p_i64) if vals.shape[0] else None))
-
-    def close(self) -> None:
-        if self._h:
-            _ffi.lib().tsh_tags_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class HipVectorIndex:

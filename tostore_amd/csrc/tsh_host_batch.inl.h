@@ -283,7 +283,7 @@ struct BatchCall {
   bool quar_host() const { return !quar_sel.empty() && !out->d_blocks; }  // host mode: the quarantined rows' sums come back
   QAux haux() const { return QAux{b->qaux.h, (size_t)p.nq_pad}; }
   QAux daux() const { return QAux{b->qaux.d, (size_t)p.nq_pad}; }
-  const uint32_t *list_ids() const { return mask.part ? mask.part->d_list : b->list.d; }  // listed: the kept rows
+  const uint32_t *list_ids() const { return mask.part ? mask.part->list.d : b->list.d; }  // listed: the kept rows
 };
 
 // the shard's first scratch set stands for "either": a call that finds it taken by a concurrent call uses the second
@@ -310,7 +310,7 @@ int batch_resolve_mask(BatchCall &c) {
   if (c.mask.part) {
     c.kept = c.mask.part->kept;
     c.h_mw = c.mask.part->h_words.data();
-    c.d_mw = c.mask.part->d_words;
+    c.d_mw = c.mask.part->words.d;
   } else if (c.mask.bytes) {
     slice_mask(c.s, c.mask.bytes, b->mask.h, c.n_tiles_all);  // (bits past the last row keep nothing: slice_mask clears them)
     c.kept = popcount_words(b->mask.h, (size_t)c.n_tiles_all);
@@ -332,7 +332,7 @@ BatchCallFacts batch_call_facts(const BatchCall &c, int force_kernel) {
   f.force_kernel = force_kernel;
   f.mask = c.mask.part ? BatchMask::HANDLE : (c.mask.bytes ? BatchMask::POINTER : BatchMask::NONE);
   f.kept = c.kept;
-  f.handle_list = c.mask.part && c.mask.part->d_list && c.mask.part->list_padded > 0;
+  f.handle_list = c.mask.part && c.mask.part->list.d && c.mask.part->list_padded > 0;
   f.f16_denied = (force_kernel >= 0 ? force_kernel : c.sh.batch_kernel) == 3 && c.s->f16_denied_calls.load() > 0;
   f.sample_force = c.b->last_sample_force != 0;
   f.est_backoff = c.b->est_backoff;

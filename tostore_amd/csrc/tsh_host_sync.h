@@ -411,6 +411,24 @@ inline void slice_mask(int64_t row_base, int64_t rows, const uint8_t *mask, uint
   if (rows & 63) out_words[(rows - 1) / 64] &= (1ull << (rows & 63)) - 1ull;
 }
 
+// ... and a shard's words put back where slice_mask would take them from (the device-made mask handles' GLOBAL bitmap):
+// bit r of the words = bit row_base + r of `bits`, for r < rows; the words' bits at or past `rows` are 0.  `bits` holds
+// at least (row_base + rows + 7) / 8 + 1 bytes.  Or-ed in: neighbouring shards may share a byte
+inline void unslice_mask(int64_t row_base, int64_t rows, const uint64_t *words, uint8_t *bits) {
+  const uint8_t *wb = reinterpret_cast<const uint8_t *>(words);
+  const int64_t nbytes = (rows + 7) / 8, b0 = row_base / 8;
+  const int sh = (int)(row_base & 7);
+  if (sh == 0) {
+    for (int64_t i = 0; i < nbytes; ++i) bits[b0 + i] |= wb[i];
+    return;
+  }
+  for (int64_t i = 0; i < nbytes; ++i) {
+    const unsigned v = wb[i];
+    bits[b0 + i] |= (uint8_t)(v << sh);
+    if (v >> (8 - sh)) bits[b0 + i + 1] |= (uint8_t)(v >> (8 - sh));
+  }
+}
+
 // rows a caller's mask keeps on the shard [row_base, row_base + rows) -- the pointer form, counted for the cost model
 // without a slice (tsh_host_batch.inl.h shard_search_any: 125 KB at 1 M rows, ~5 us)
 inline int64_t mask_kept_rows(int64_t row_base, int64_t rows, const uint8_t *bytes) {

@@ -964,12 +964,38 @@ struct RowList {
   int32_t padded = 0;  // entries incl. padding (multiple of 64)
 };
 
+// A device buffer of the handles' parts that grows and never shrinks (BatchBuf's idiom, tsh_host_batch.inl.h).  The
+// current device is the buffer's.  A failed allocation leaves d NULL and cap 0
+template <typename T>
+struct DevBuf {
+  T *d = nullptr;
+  int64_t cap = 0;  // entries
+  // room for `want` entries: a buffer too small is replaced (never copied) by one of want + slack entries rounded up to
+  // round_to, slack = want / 8 unless given.  *bytes follows what is held
+  int reserve(int64_t want, int64_t round_to, int64_t *bytes = nullptr, int64_t slack = -1) {
+    if (want <= cap) return TSH_OK;
+    const int64_t held = cap;
+    free();
+    if (bytes) *bytes -= held * (int64_t)sizeof(T);
+    const int64_t grown = round_up(want + (slack < 0 ? want / 8 : slack), round_to);
+    HIPCHK(hipMalloc(&d, (size_t)grown * sizeof(T)));
+    cap = grown;
+    if (bytes) *bytes += grown * (int64_t)sizeof(T);
+    return TSH_OK;
+  }
+  void free() {
+    hipFree(d);
+    d = nullptr;
+    cap = 0;
+  }
+};
+
 // ---- mask handles (tsh_mask_create, include/tostore_hip.h): one shard's part ------------------------------------
 // The caller's bitmap sliced to this shard's rows, as the kernels read it (word t bit r = local row 64 t + r), on
 // the host (the quarantined rows are matched against it there; the batched path places its sample window by it) and
 // on the device (dense masked scans, the batched epilogue); and, when the mask is selective, the ascending list of
 // its kept rows -- compacted on the device (tsh_mask.hip.h), never on the host.  Built for the rows the shard had at
-// the time; a search that finds the shard grown rebuilds it first (mask_part).
+// the time; a search that finds the shard grown rebuilds it first (current_part).
 struct MaskPart {
   int device = 0;
   std::atomic<int64_t> built_rows{-1};  // rows of the shard the part was built for (-1: not built)
@@ -977,14 +1003,17 @@ struct MaskPart {
   int64_t kept = 0;                // set bits (tombstones not subtracted)
   std::vector<uint64_t> h_words;   // n_tiles words
   std::vector<int32_t> pre;        // pre[t] = kept rows in words [0, t): n_tiles + 1 entries
-  uint64_t *d_words = nullptr;
-  int64_t words_cap = 0;
-  uint32_t *d_list = nullptr;      // kept rows' local ids, ascending, padded with 0xFFFFFFFF to a multiple of 64
-  int64_t list_cap = 0;
+  DevBuf<uint64_t> words;
+  DevBuf<uint32_t> list;           // kept rows' local ids, ascending, padded with 0xFFFFFFFF to a multiple of 64
   int32_t list_padded = 0;         // 0: no list (the mask keeps too many rows for one to pay, or none)
-  uint32_t *d_bsum = nullptr;      // M1's per-workgroup counts + one word for M2's total
-  int64_t bsum_cap = 0;
+  DevBuf<uint32_t> bsum;           // M1's per-workgroup counts + one word for M2's total
   int64_t bytes = 0;               // device bytes held
+  void free_bufs() {
+    words.free();
+    list.free();
+    bsum.free();
+    bytes = 0;
+  }
 };
 // the mask of a search, as the shard-level functions take it
 struct MaskSrc {
@@ -1008,25 +1037,25 @@ struct ShardMask {
 // ---- groups handles (tsh_groups_create, include/tostore_hip.h): one shard's part ---------------------------------------
 // The caller's group array sliced to this shard's rows on the device: entry r = the group of local row r, for the rows
 // the shard had when the part was built (rows beyond the caller's array: -1).  A search that finds the shard grown, or
-// the array changed by tsh_groups_set (built_rows = -1), rebuilds it first (groups_part).
+// the array changed by tsh_groups_set (built_rows = -1), rebuilds it first (current_part).
 struct GroupPart {
   int device = 0;
   std::atomic<int64_t> built_rows{-1};
-  int32_t *d_group = nullptr;
-  int64_t cap = 0;
+  DevBuf<int32_t> group;
   int32_t n_groups = 0;
+  void free_bufs() { group.free(); }
 };
 
 // ---- attribute handles (tsh_attr_create, include/tostore_hip.h): one shard's part --------------------------------------
 // The caller's column sliced to this shard's rows on the device: entry r = the value of local row r, for the rows the
 // shard had when the part was built (rows beyond the caller's array: TSH_ATTR_NULL).  A mask made from the handle
 // (tsh_mask_create_range) that finds the shard grown, or the array changed by tsh_attr_set (built_rows = -1), rebuilds
-// it first (attr_part).  8 B per row.
+// it first (current_part).  8 B per row.
 struct AttrPart {
   int device = 0;
   std::atomic<int64_t> built_rows{-1};
-  int64_t *d_vals = nullptr;
-  int64_t cap = 0;
+  DevBuf<int64_t> vals;
+  void free_bufs() { vals.free(); }
 };
 
 // ---- tag handles (tsh_tags_create, include/tostore_hip.h): one shard's part --------------------------------------------
@@ -1034,16 +1063,18 @@ struct AttrPart {
 // offsets rebased to the slice's first value, the values, and the valid words (bit r of word t: local row 64 t + r
 // exists in the column and is not NULL), for the rows the shard had when the part was built.  A mask made from the
 // handle (tsh_mask_create_tags) that finds the shard grown, or the column changed by tsh_tags_set (built_rows = -1),
-// rebuilds it first (tags_part).  4 B per row + 8 B per value + 8 B per 64 rows.
+// rebuilds it first (current_part).  4 B per row + 8 B per value + 8 B per 64 rows.
 struct TagsPart {
   int device = 0;
   std::atomic<int64_t> built_rows{-1};
-  uint32_t *d_off = nullptr;
-  int64_t off_cap = 0;
-  int64_t *d_vals = nullptr;
-  int64_t vals_cap = 0;
-  uint64_t *d_valid = nullptr;
-  int64_t valid_cap = 0;
+  DevBuf<uint32_t> off;
+  DevBuf<int64_t> vals;
+  DevBuf<uint64_t> valid;
+  void free_bufs() {
+    off.free();
+    vals.free();
+    valid.free();
+  }
 };
 
 // One query in flight on one context.  Its three kernels (scan, select,
@@ -1298,7 +1329,7 @@ ShardMask resolve_mask(Shard *s, const MaskSrc &mask, int32_t k, int32_t entries
     m.words = mp->h_words.data();
     m.rows_est = std::max<int64_t>(mp->kept, 1);
     if (mp->list_padded > 0 && row_list_pays(s, mp->kept, k, entries)) {
-      m.list.d_ids = mp->d_list;
+      m.list.d_ids = mp->list.d;
       m.list.padded = mp->list_padded;
     }
   } else if (mask.bytes) {
@@ -1683,7 +1714,7 @@ int job_stage(Shard *s, Job *j, const JobReq &rq, JobArgs *ka, float **qp) {
   const bool own_list = r.use_list && !m.list.d_ids;  // the context's copy of a host-made list
   if (own_list && (rc = ctx_reserve_list(c, m.list.padded))) return rc;
   if (r.exact && (rc = ctx_reserve_exact(c, r.n_exam))) return rc;
-  j->d_mask = m.part ? m.part->d_words : c->d_mask;
+  j->d_mask = m.part ? m.part->words.d : c->d_mask;
   j->d_list = r.use_list ? (own_list ? c->d_list : m.list.d_ids) : nullptr;
   j->k = rq.k;
   j->entries = rq.entries;
@@ -1928,7 +1959,7 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     const uint32_t side_cap = (uint32_t)c->side_cap;
     uint32_t *const side_count = c->d_side_cnt + j->side_word;
     const CountWindow &w = j->window;
-    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, nullptr, nullptr, gp->built_rows.load(), gp->n_groups, n_tiles};
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->group.d, c->d_gm, nullptr, nullptr, gp->built_rows.load(), gp->n_groups, n_tiles};
     if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
     group_min_kernel<<<(unsigned)((n_tiles + 3) / 4), 256, 0, ts>>>(ga);
     const GroupCountArgs gc{ga, c->d_side_rows, side_count, c->d_side_cnt + 2, side_cap, w.in_lo, w.in_hi, w.out_lo, w.out_hi, ka.se.eps_rel, ka.se.delta_abs};
@@ -1945,7 +1976,7 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     const unsigned tgrid = (unsigned)((n_tiles + 3) / 4);
     const uint32_t side_cap = (uint32_t)c->side_cap;
     uint32_t *const side_count = c->d_side_cnt + j->side_word;
-    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->group.d, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
     if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
     group_min_kernel<<<tgrid, 256, 0, ts>>>(ga);
     const GroupHeadsAfterArgs gh{ga, c->d_side_rows, side_count, side_cap, j->floor.lo, j->floor.hi};
@@ -1980,7 +2011,7 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     const uint32_t side_cap = (uint32_t)c->side_cap;
     uint32_t *const side_count = c->d_side_cnt + j->side_word;
     const uint32_t slot_cap = (uint32_t)std::min<int64_t>(group_rows_slots(j->k), c->gr_slots);
-    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->group.d, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
     if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
     // (the control words, cnt[] and cur[]; off[] is written before it is read)
     HIPCHK(hipMemsetAsync(c->d_gr_ctl, 0, (size_t)(GROUP_ROWS_CTL + 2 * c->gr_slots) * sizeof(uint32_t), ts));
@@ -2009,7 +2040,7 @@ int launch_job_tail(Shard *s, Job *j, const JobArgs &ka, hipStream_t ts) {
     const unsigned tgrid = (unsigned)((n_tiles + 3) / 4);
     const uint32_t side_cap = (uint32_t)c->side_cap;
     uint32_t *const side_count = c->d_side_cnt + j->side_word;
-    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->d_group, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
+    const GroupArgs ga{c->d_keys, c->d_gmin, j->d_list, gp->group.d, c->d_gm, c->d_heads, c->d_hmin, gp->built_rows.load(), gp->n_groups, n_tiles};
     if (gp->n_groups > 0) HIPCHK(hipMemsetAsync(c->d_gm, 0xFF, (size_t)gp->n_groups * 8, ts));
     group_min_kernel<<<tgrid, 256, 0, ts>>>(ga);
     group_heads_kernel<<<tgrid, 256, 0, ts>>>(ga);
@@ -2983,34 +3014,136 @@ namespace {
 // be destroyed under a count.
 std::mutex g_mask_mu;
 
-void mask_part_free(MaskPart *p) {
+// ---- what the four handle kinds share: tsh_mask, tsh_groups, tsh_attr, tsh_tags ------------------------------------------
+// Each has idx, mu and parts; a kind adds its part struct (with free_bufs), a build_part overload and a live_list overload.
+template <class H>
+using PartOf = typename decltype(H::parts)::value_type::element_type;
+
+std::vector<tsh_mask *> &live_list(tsh_index *idx, const tsh_mask *) { return idx->masks; }
+std::vector<tsh_groups *> &live_list(tsh_index *idx, const tsh_groups *) { return idx->groups; }
+std::vector<tsh_attr *> &live_list(tsh_index *idx, const tsh_attr *) { return idx->attrs; }
+std::vector<tsh_tags *> &live_list(tsh_index *idx, const tsh_tags *) { return idx->tags; }
+
+int build_part(tsh_mask *m, MaskPart *p, Shard *s);
+int build_part(tsh_groups *g, GroupPart *p, Shard *s);
+int build_part(tsh_attr *a, AttrPart *p, Shard *s);
+int build_part(tsh_tags *t, TagsPart *p, Shard *s);
+
+// A part's device buffers go (built_rows with them: nothing reads it afterwards -- an orphan is refused by its idx ==
+// nullptr before any part is read, and a failed create deletes the handle)
+template <class P>
+void part_free(P *p) {
   if (hipSetDevice(p->device) != hipSuccess) return;
-  hipFree(p->d_words);
-  hipFree(p->d_list);
-  hipFree(p->d_bsum);
-  p->d_words = nullptr;
-  p->d_list = p->d_bsum = nullptr;
-  p->words_cap = p->list_cap = p->bsum_cap = 0;
-  p->bytes = 0;
+  p->free_bufs();
+  p->built_rows.store(-1);
+}
+// ... every part's, and the error text stays as it was
+template <class H>
+void free_parts(H *h) {
+  const std::string keep = g_err;
+  for (auto &p : h->parts) part_free(p.get());
+  g_err = keep;
 }
 
-// Room for n_tiles words in a part's d_words (the current device is the part's)
-int mask_reserve_words(MaskPart *p, int32_t n_tiles) {
-  if (n_tiles > p->words_cap) {
-    hipFree(p->d_words);
-    p->d_words = nullptr;
-    p->bytes -= p->words_cap * 8;
-    p->words_cap = 0;
-    const int64_t want = round_up(n_tiles + n_tiles / 8, 64);
-    HIPCHK(hipMalloc(&p->d_words, (size_t)want * 8));
-    p->words_cap = want;
-    p->bytes += want * 8;
+// Shard g's part of a handle, current for the rows the shard has; nullptr + *rc on failure.  Caller holds s->mu shared
+// and, where the kind has one, h->use_mu shared.  A part built for other rows (the shard grew), or marked -1 by the
+// kind's _set, is rebuilt under h->mu first.  Appends take the shard exclusively and _set takes the handle exclusively, so
+// no search or kernel that reads the old buffers is running: whoever starts after either passes through here first
+template <class H>
+const PartOf<H> *current_part(H *h, size_t g, Shard *s, int *rc) {
+  *rc = TSH_OK;
+  PartOf<H> *p = h->parts[g].get();
+  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
+    *rc = build_part(h, p, s);
+    if (*rc) return nullptr;
   }
+  return p;
+}
+
+// A new handle's parts: one for every shard of h->idx, each made by build(g, s, part) under h->mu and the shard's shared
+// lock (a handle exists to take this work out of the searches).  On failure the parts are freed and g_err is build's
+template <class H, class F>
+int make_parts(H *h, F &&build) {
+  tsh_index *idx = h->idx;
+  for (size_t g = 0; g < idx->shards.size(); ++g) h->parts.emplace_back(new PartOf<H>());
+  int rc = TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
+      Shard *s = idx->shards[g].get();
+      std::shared_lock<RwLock> sl = share(idx, s);
+      rc = build(g, s, h->parts[g].get());
+    }
+  }
+  if (rc) free_parts(h);
+  return rc;
+}
+template <class H>
+int make_parts(H *h) {
+  return make_parts(h, [h](size_t, Shard *s, PartOf<H> *p) { return build_part(h, p, s); });
+}
+
+// The end of every create: the index learns of the handle, the caller gets it
+template <class H>
+int32_t register_handle(std::unique_ptr<H> &h, H **out) {
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    live_list(h->idx, h.get()).push_back(h.get());
+  }
+  *out = h.release();
   return TSH_OK;
 }
 
+template <class H>
+int32_t destroy_handle(H *h) {
+  if (!h) return TSH_OK;
+  {
+    std::lock_guard<std::mutex> lk(g_mask_mu);
+    if (tsh_index *idx = h->idx) {  // (an orphan's parts went with its index)
+      auto &live = live_list(idx, h);
+      live.erase(std::remove(live.begin(), live.end(), h), live.end());
+      free_parts(h);
+    }
+  }
+  delete h;
+  return TSH_OK;
+}
+
+// tsh_index_destroy, g_mask_mu held: handles still alive are orphaned -- their device parts go now, the structs stay for
+// their own destroy
+template <class H>
+void orphan_handles(std::vector<H *> &live) {
+  for (H *h : live) {
+    free_parts(h);
+    h->idx = nullptr;
+  }
+  live.clear();
+}
+
+// tsh_groups_set, tsh_attr_set, tsh_tags_set behind their argument checks.  Locks: g_mask_mu (the index cannot be destroyed
+// under the call), then idx->mu as an append does, then h->use_mu exclusive.  check() runs before the last two; change()
+// alters the host copy under all three, and every part is marked for its rebuild by the next reader of each shard
+template <class H, class C, class F>
+int32_t set_column(H *h, const char *orphaned, int64_t n, C &&check, F &&change) {
+  std::lock_guard<std::mutex> hold(g_mask_mu);
+  tsh_index *idx = h->idx;
+  if (!idx) return set_err(TSH_E_BAD_ARG, "%s", orphaned);
+  int rc = check();
+  if (rc) return rc;
+  if (n == 0) return TSH_OK;
+  std::lock_guard<std::mutex> lk(idx->mu);
+  std::unique_lock<std::shared_mutex> xl(h->use_mu);
+  rc = change();
+  if (rc) return rc;
+  for (auto &p : h->parts) p->built_rows.store(-1, std::memory_order_release);
+  return TSH_OK;
+}
+inline int no_check() { return TSH_OK; }
+
 // The second half of a part's build, whichever way its words were obtained (sliced from the handle's bitmap and uploaded:
-// mask_build_part; or written by mask_range_kernel and copied back: mask_range_part): p->h_words and p->d_words hold the
+// build_part; or written by a W kernel and copied back: mask_device_part): p->h_words and p->words.d hold the
 // same n_tiles words (an upload may still be in flight on s->aux_stream; a copy back is done).  Counts them on the host once -- the
 // batched path and the quarantined rows read words and prefix there -- and compacts a selective mask's list on the device
 // (tsh_mask.hip.h).  Returns with the stream drained and the part current for `rows`.
@@ -3029,31 +3162,15 @@ int mask_finish_part(MaskPart *p, Shard *s, int64_t rows, int32_t n_tiles) {
                          (padded <= EX_MAX_ROWS || p->kept * list_div <= rows);
   if (want_list) {
     const int32_t n_blocks = (n_tiles + MASK_BLOCK_WORDS - 1) / MASK_BLOCK_WORDS;
-    if (n_blocks + 1 > p->bsum_cap) {
-      hipFree(p->d_bsum);
-      p->d_bsum = nullptr;
-      p->bytes -= p->bsum_cap * 4;
-      p->bsum_cap = 0;
-      const int64_t want = round_up(n_blocks + 1 + n_blocks / 8, 64);
-      HIPCHK(hipMalloc(&p->d_bsum, (size_t)want * 4));
-      p->bsum_cap = want;
-      p->bytes += want * 4;
-    }
-    if (padded > p->list_cap) {
-      hipFree(p->d_list);
-      p->d_list = nullptr;
-      p->bytes -= p->list_cap * 4;
-      p->list_cap = 0;
-      const int64_t want = round_up(padded + padded / 8, 1024);
-      HIPCHK(hipMalloc(&p->d_list, (size_t)want * 4));
-      p->list_cap = want;
-      p->bytes += want * 4;
-    }
-    uint32_t *d_total = p->d_bsum + n_blocks;
-    mask_block_count_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, st>>>(p->d_words, n_tiles, p->d_bsum);
-    mask_compact_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, st>>>(p->d_words, n_tiles, p->d_bsum, p->d_list, d_total);
+    int rc = p->bsum.reserve(n_blocks + 1, 64, &p->bytes, n_blocks / 8);
+    if (rc) return rc;
+    rc = p->list.reserve(padded, 1024, &p->bytes);
+    if (rc) return rc;
+    uint32_t *d_total = p->bsum.d + n_blocks;
+    mask_block_count_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, st>>>(p->words.d, n_tiles, p->bsum.d);
+    mask_compact_kernel<<<n_blocks, MASK_BLOCK_WORDS, 0, st>>>(p->words.d, n_tiles, p->bsum.d, p->list.d, d_total);
     if (padded > p->kept)
-      HIPCHK(hipMemsetAsync(p->d_list + p->kept, 0xFF, (size_t)(padded - p->kept) * 4, st));
+      HIPCHK(hipMemsetAsync(p->list.d + p->kept, 0xFF, (size_t)(padded - p->kept) * 4, st));
     uint32_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -3070,7 +3187,7 @@ int mask_finish_part(MaskPart *p, Shard *s, int64_t rows, int32_t n_tiles) {
 
 // (Re)builds one shard's part for the rows the shard has now.  Caller holds s->mu shared (the rows cannot change) and
 // m->mu.  The words are sliced from the handle's bitmap on the host and uploaded once; mask_finish_part does the rest.
-int mask_build_part(tsh_mask *m, MaskPart *p, Shard *s) {
+int build_part(tsh_mask *m, MaskPart *p, Shard *s) {
   HIPCHK(hipSetDevice(s->device));
   p->device = s->device;
   const int64_t rows = s->rows;
@@ -3080,26 +3197,11 @@ int mask_build_part(tsh_mask *m, MaskPart *p, Shard *s) {
   if (m->bits.size() < need) m->bits.resize(need, 0);
   p->h_words.assign((size_t)n_tiles, 0);
   if (n_tiles > 0) slice_mask(s, m->bits.data(), p->h_words.data(), n_tiles);
-  int rc = mask_reserve_words(p, n_tiles);
+  int rc = p->words.reserve(n_tiles, 64, &p->bytes);
   if (rc) return rc;
   if (n_tiles > 0)
-    HIPCHK(hipMemcpyAsync(p->d_words, p->h_words.data(), (size_t)n_tiles * 8, hipMemcpyHostToDevice, s->aux_stream));
+    HIPCHK(hipMemcpyAsync(p->words.d, p->h_words.data(), (size_t)n_tiles * 8, hipMemcpyHostToDevice, s->aux_stream));
   return mask_finish_part(p, s, rows, n_tiles);
-}
-
-// shard g's part of a handle, current for the rows the shard has (caller holds s->mu shared); nullptr + *rc on failure
-const MaskPart *mask_part(tsh_mask *m, size_t g, Shard *s, int *rc) {
-  *rc = TSH_OK;
-  MaskPart *p = m->parts[g].get();
-  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
-  // the shard grew since the part was built (appends take the shard exclusively, so no search that reads the old
-  // buffers is running: every search that started after the append passes through here first)
-  std::lock_guard<std::mutex> lk(m->mu);
-  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
-    *rc = mask_build_part(m, p, s);
-    if (*rc) return nullptr;
-  }
-  return p;
 }
 
 // The mask of a call, as the entries get it: the caller's global bitmap, or a mask handle, or neither
@@ -3113,201 +3215,61 @@ inline int call_mask_for_shard(const CallMask &m, size_t g, Shard *s, MaskSrc *o
   *out = MaskSrc(m.bytes);
   if (!m.handle) return TSH_OK;
   int rc = TSH_OK;
-  const MaskPart *mp = mask_part(m.handle, g, s, &rc);
+  const MaskPart *mp = current_part(m.handle, g, s, &rc);
   if (!mp) return rc;
   *out = MaskSrc(mp);
   return TSH_OK;
 }
 
-void groups_part_free(GroupPart *p) {
-  if (hipSetDevice(p->device) != hipSuccess) return;
-  hipFree(p->d_group);
-  p->d_group = nullptr;
-  p->cap = 0;
-  p->built_rows.store(-1);
-}
-
 // (Re)builds one shard's part for the rows the shard has now: the slice of the handle's array, -1 beyond it.  Caller holds
 // s->mu shared, g->use_mu (shared or exclusive) and g->mu
-int groups_build_part(tsh_groups *g, GroupPart *p, Shard *s) {
+int build_part(tsh_groups *g, GroupPart *p, Shard *s) {
   HIPCHK(hipSetDevice(s->device));
   p->device = s->device;
   p->n_groups = g->n_groups;
   const int64_t rows = s->rows;
-  if (rows > p->cap) {
-    hipFree(p->d_group);
-    p->d_group = nullptr;
-    p->cap = 0;
-    const int64_t want = round_up(rows + rows / 8, 1024);
-    HIPCHK(hipMalloc(&p->d_group, (size_t)want * sizeof(int32_t)));
-    p->cap = want;
-  }
+  int rc = p->group.reserve(rows, 1024);
+  if (rc) return rc;
   if (rows > 0) {
     std::vector<int32_t> slice((size_t)rows, -1);
     const int64_t have = std::min<int64_t>(rows, std::max<int64_t>((int64_t)g->group_of.size() - s->row_base, 0));
     if (have > 0) memcpy(slice.data(), g->group_of.data() + s->row_base, (size_t)have * sizeof(int32_t));
-    HIPCHK(hipMemcpyAsync(p->d_group, slice.data(), (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s->aux_stream));
+    HIPCHK(hipMemcpyAsync(p->group.d, slice.data(), (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s->aux_stream));
     HIPCHK(hipStreamSynchronize(s->aux_stream));
   }
   p->built_rows.store(rows, std::memory_order_release);
   return TSH_OK;
-}
-
-// shard g's part of a groups handle, current for the rows the shard has (caller holds s->mu shared and h->use_mu shared);
-// nullptr + *rc on failure.  As mask_part: appends take the shard exclusively, tsh_groups_set the handle, so no search
-// reads the buffer while it is rebuilt
-const GroupPart *groups_part(tsh_groups *h, size_t g, Shard *s, int *rc) {
-  *rc = TSH_OK;
-  GroupPart *p = h->parts[g].get();
-  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
-    *rc = groups_build_part(h, p, s);
-    if (*rc) return nullptr;
-  }
-  return p;
-}
-
-void attr_part_free(AttrPart *p) {
-  if (hipSetDevice(p->device) != hipSuccess) return;
-  hipFree(p->d_vals);
-  p->d_vals = nullptr;
-  p->cap = 0;
-  p->built_rows.store(-1);
 }
 
 // (Re)builds one shard's part for the rows the shard has now: the slice of the handle's column, TSH_ATTR_NULL beyond it.
 // Caller holds s->mu shared, a->use_mu (shared or exclusive) and a->mu
-int attr_build_part(tsh_attr *a, AttrPart *p, Shard *s) {
+int build_part(tsh_attr *a, AttrPart *p, Shard *s) {
   HIPCHK(hipSetDevice(s->device));
   p->device = s->device;
   const int64_t rows = s->rows;
-  if (rows > p->cap) {
-    hipFree(p->d_vals);
-    p->d_vals = nullptr;
-    p->cap = 0;
-    const int64_t want = round_up(rows + rows / 8, 1024);
-    HIPCHK(hipMalloc(&p->d_vals, (size_t)want * sizeof(int64_t)));
-    p->cap = want;
-  }
+  int rc = p->vals.reserve(rows, 1024);
+  if (rc) return rc;
   if (rows > 0) {
     const int64_t have = std::min<int64_t>(rows, std::max<int64_t>((int64_t)a->values.size() - s->row_base, 0));
     // (the rows the column names go up from the handle's copy as they lie; only the rows beyond it need a staged NULL)
     if (have > 0)
-      HIPCHK(hipMemcpyAsync(p->d_vals, a->values.data() + s->row_base, (size_t)have * sizeof(int64_t), hipMemcpyHostToDevice,
+      HIPCHK(hipMemcpyAsync(p->vals.d, a->values.data() + s->row_base, (size_t)have * sizeof(int64_t), hipMemcpyHostToDevice,
                             s->aux_stream));
     std::vector<int64_t> nulls((size_t)(rows - have), ATTR_NULL);
     if (rows > have)
-      HIPCHK(hipMemcpyAsync(p->d_vals + have, nulls.data(), (size_t)(rows - have) * sizeof(int64_t), hipMemcpyHostToDevice,
+      HIPCHK(hipMemcpyAsync(p->vals.d + have, nulls.data(), (size_t)(rows - have) * sizeof(int64_t), hipMemcpyHostToDevice,
                             s->aux_stream));
     HIPCHK(hipStreamSynchronize(s->aux_stream));
   }
   p->built_rows.store(rows, std::memory_order_release);
   return TSH_OK;
-}
-
-// shard g's part of an attribute handle, current for the rows the shard has (caller holds s->mu shared and h->use_mu
-// shared); nullptr + *rc on failure.  As groups_part: appends take the shard exclusively, tsh_attr_set the handle, so no
-// kernel reads the buffer while it is rebuilt
-const AttrPart *attr_part(tsh_attr *h, size_t g, Shard *s, int *rc) {
-  *rc = TSH_OK;
-  AttrPart *p = h->parts[g].get();
-  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
-    *rc = attr_build_part(h, p, s);
-    if (*rc) return nullptr;
-  }
-  return p;
-}
-
-// The words of a mask part obtained ON the device (tsh_where.hip.h): the range term over the shard's slice of the column,
-// combined with another handle's words if one is given, written straight into p->d_words by mask_range_kernel and copied
-// back once into p->h_words; mask_finish_part does the rest, as for an uploaded bitmap.  Caller holds s->mu shared, the
-// new handle's mu, and the attribute handle's use_mu shared; ap and wp are current for the shard's rows
-int mask_range_part(MaskPart *p, Shard *s, const AttrPart *ap, int64_t lo, int64_t hi, bool negate, const MaskPart *wp,
-                    int32_t combine) {
-  HIPCHK(hipSetDevice(s->device));
-  p->device = s->device;
-  const int64_t rows = s->rows;
-  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
-  try {
-    p->h_words.assign((size_t)n_tiles, 0);
-  } catch (...) {
-    return set_err(TSH_E_OOM, "no memory for %d mask words", n_tiles);
-  }
-  int rc = mask_reserve_words(p, n_tiles);
-  if (rc) return rc;
-  if (n_tiles > 0) {
-    hipStream_t st = s->aux_stream;
-    // (wp was built for the same rows: n_tiles words, the bits at or past the last row 0)
-    mask_range_kernel<<<where_grid(n_tiles), WHERE_BLOCK, 0, st>>>(ap->d_vals, rows, n_tiles, lo, hi, negate ? 1 : 0,
-                                                                   wp ? wp->d_words : nullptr, combine, p->d_words);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return mask_finish_part(p, s, rows, n_tiles);
-}
-
-// ... and the same for a whole clause (tsh_mask_create_where): one launch of mask_where_kernel over the shard's slices of
-// the plan's columns (aps[c] for plan.columns[c]), one copy of the words back, one mask_finish_part.  The plan's sets go
-// up in one copy ahead of the launch, into the tail of the part's own word allocation (both are 8-byte entries; the
-// part is new, so the allocation is made here anyway): a call without IN terms stages nothing and allocates no more
-// than the range entry does.  plan.set outlives the synchronise below.  Locks as for mask_range_part, every column's
-// use_mu shared
-int mask_where_part(MaskPart *p, Shard *s, const WherePlan &plan, const AttrPart *const *aps, const MaskPart *wp,
-                    int32_t combine) {
-  HIPCHK(hipSetDevice(s->device));
-  p->device = s->device;
-  const int64_t rows = s->rows;
-  const int32_t n_tiles = (int32_t)((rows + 63) / 64);
-  const int32_t n_set = (int32_t)plan.set.size();
-  try {
-    p->h_words.assign((size_t)n_tiles, 0);
-  } catch (...) {
-    return set_err(TSH_E_OOM, "no memory for %d mask words", n_tiles);
-  }
-  int rc = mask_reserve_words(p, n_tiles + (n_tiles > 0 ? n_set : 0));
-  if (rc) return rc;
-  if (n_tiles > 0) {
-    hipStream_t st = s->aux_stream;
-    WhereArgs a{};
-    for (int c = 0; c < WHERE_MAX_COLUMNS; ++c) a.cols[c] = c < plan.n_cols ? aps[c]->d_vals : nullptr;
-    memcpy(a.terms, plan.terms, sizeof(a.terms[0]) * (size_t)plan.n_terms);
-    a.n_terms = plan.n_terms;
-    a.n_cols = plan.n_cols;
-    a.n_set = n_set;
-    a.combine = combine;
-    int64_t *d_set = reinterpret_cast<int64_t *>(p->d_words + n_tiles);
-    if (n_set > 0) HIPCHK(hipMemcpyAsync(d_set, plan.set.data(), (size_t)n_set * 8, hipMemcpyHostToDevice, st));
-    // (wp was built for the same rows: n_tiles words, the bits at or past the last row 0)
-    mask_where_kernel<<<where_grid(n_tiles), WHERE_BLOCK, (size_t)n_set * 8, st>>>(a, rows, n_tiles, d_set,
-                                                                                   wp ? wp->d_words : nullptr, p->d_words);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return mask_finish_part(p, s, rows, n_tiles);
-}
-
-void tags_part_free(TagsPart *p) {
-  if (hipSetDevice(p->device) != hipSuccess) return;
-  hipFree(p->d_off);
-  hipFree(p->d_vals);
-  hipFree(p->d_valid);
-  p->d_off = nullptr;
-  p->d_vals = nullptr;
-  p->d_valid = nullptr;
-  p->off_cap = p->vals_cap = p->valid_cap = 0;
-  p->built_rows.store(-1);
 }
 
 // (Re)builds one shard's part for the rows the shard has now: the slice of the handle's column (tags_slice: rebased
 // offsets, the value span as it lies in the handle's copy, the valid words; rows beyond the column are empty spans with
 // valid bit 0).  A slice of more than 2^31 - 1 values is refused before anything is allocated.  Caller holds s->mu
 // shared, t->use_mu (shared or exclusive) and t->mu
-int tags_build_part(tsh_tags *t, TagsPart *p, Shard *s) {
+int build_part(tsh_tags *t, TagsPart *p, Shard *s) {
   HIPCHK(hipSetDevice(s->device));
   p->device = s->device;
   const int64_t rows = s->rows;
@@ -3318,104 +3280,93 @@ int tags_build_part(tsh_tags *t, TagsPart *p, Shard *s) {
     return set_err(TSH_E_OOM, "no memory for the offsets of %lld rows", (long long)rows);
   }
   const int64_t n_tiles = (int64_t)sl.valid.size();
-  if (rows + 1 > p->off_cap) {
-    hipFree(p->d_off);
-    p->d_off = nullptr;
-    p->off_cap = 0;
-    const int64_t want = round_up(rows + 1 + rows / 8, 1024);
-    HIPCHK(hipMalloc(&p->d_off, (size_t)want * sizeof(uint32_t)));
-    p->off_cap = want;
-  }
-  if (sl.n_vals > p->vals_cap) {
-    hipFree(p->d_vals);
-    p->d_vals = nullptr;
-    p->vals_cap = 0;
-    const int64_t want = round_up(sl.n_vals + sl.n_vals / 8, 1024);
-    HIPCHK(hipMalloc(&p->d_vals, (size_t)want * sizeof(int64_t)));
-    p->vals_cap = want;
-  }
-  if (n_tiles > p->valid_cap) {
-    hipFree(p->d_valid);
-    p->d_valid = nullptr;
-    p->valid_cap = 0;
-    const int64_t want = round_up(n_tiles + n_tiles / 8, 64);
-    HIPCHK(hipMalloc(&p->d_valid, (size_t)want * sizeof(uint64_t)));
-    p->valid_cap = want;
-  }
+  int rc = p->off.reserve(rows + 1, 1024, nullptr, rows / 8);
+  if (rc == TSH_OK) rc = p->vals.reserve(sl.n_vals, 1024);
+  if (rc == TSH_OK) rc = p->valid.reserve(n_tiles, 64);
+  if (rc) return rc;
   hipStream_t st = s->aux_stream;
-  HIPCHK(hipMemcpyAsync(p->d_off, sl.off.data(), (size_t)(rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(p->off.d, sl.off.data(), (size_t)(rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   if (sl.n_vals > 0)
-    HIPCHK(hipMemcpyAsync(p->d_vals, sl.vals, (size_t)sl.n_vals * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p->vals.d, sl.vals, (size_t)sl.n_vals * sizeof(int64_t), hipMemcpyHostToDevice, st));
   if (n_tiles > 0)
-    HIPCHK(hipMemcpyAsync(p->d_valid, sl.valid.data(), (size_t)n_tiles * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p->valid.d, sl.valid.data(), (size_t)n_tiles * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   p->built_rows.store(rows, std::memory_order_release);
   return TSH_OK;
 }
 
-// shard g's part of a tag handle, current for the rows the shard has (caller holds s->mu shared and h->use_mu shared);
-// nullptr + *rc on failure.  As attr_part: appends take the shard exclusively, tsh_tags_set the handle, so no kernel
-// reads the buffers while they are rebuilt
-const TagsPart *tags_part(tsh_tags *h, size_t g, Shard *s, int *rc) {
-  *rc = TSH_OK;
-  TagsPart *p = h->parts[g].get();
-  if (p->built_rows.load(std::memory_order_acquire) == s->rows) return p;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (p->built_rows.load(std::memory_order_acquire) != s->rows) {
-    *rc = tags_build_part(h, p, s);
-    if (*rc) return nullptr;
-  }
-  return p;
-}
-
-// ... and the words of a HAS ANY / HAS ALL term over a tag column (tsh_mask_create_tags): one launch of mask_tags_kernel
-// (tsh_tags.hip.h) over the shard's part of the column, one copy of the words back, one mask_finish_part.  The term's set
-// goes up in one copy ahead of the launch, into the tail of the part's own word allocation, as W2's sets do.  q.set
-// outlives the synchronise below.  Locks as for mask_range_part, the tag handle's use_mu shared
-int mask_tags_part(MaskPart *p, Shard *s, const TagsPart *tp, const TagsQuery &q, bool negate, const MaskPart *wp,
-                   int32_t combine) {
+// The words of a mask part obtained ON the device (tsh_where.hip.h, tsh_tags.hip.h): one launch over the shard's slice of
+// the column(s), combined there with with's words if a handle is given, written straight into p->words.d and copied back
+// once into p->h_words; mask_finish_part does the rest, as for an uploaded bitmap.  A term's set (n_set 8-byte entries;
+// it outlives the synchronise below) goes up in one copy ahead of the launch, into the tail of the part's own word
+// allocation -- the part is new, so the allocation is made here anyway: a call without a set stages nothing and allocates
+// no more.  launch(st, rows, n_tiles, d_set, with's words or nullptr) enqueues the one kernel on st.  Caller holds s->mu
+// shared, the new handle's mu and the columns' use_mu shared; the columns' parts are current for the shard's rows, and
+// with's is made so here (n_tiles words, the bits at or past the last row 0)
+template <class F>
+int mask_device_part(MaskPart *p, Shard *s, tsh_mask *with, size_t g, const int64_t *set, int32_t n_set, F &&launch) {
+  int rc = TSH_OK;
+  const MaskPart *wp = with ? current_part(with, g, s, &rc) : nullptr;
+  if (with && !wp) return rc;
   HIPCHK(hipSetDevice(s->device));
   p->device = s->device;
   const int64_t rows = s->rows;
   const int32_t n_tiles = (int32_t)((rows + 63) / 64);
-  const int32_t n_set = (int32_t)q.set.size();
   try {
     p->h_words.assign((size_t)n_tiles, 0);
   } catch (...) {
     return set_err(TSH_E_OOM, "no memory for %d mask words", n_tiles);
   }
-  int rc = mask_reserve_words(p, n_tiles + (n_tiles > 0 ? n_set : 0));
+  rc = p->words.reserve(n_tiles + (n_tiles > 0 ? n_set : 0), 64, &p->bytes);
   if (rc) return rc;
   if (n_tiles > 0) {
     hipStream_t st = s->aux_stream;
-    int64_t *d_set = reinterpret_cast<int64_t *>(p->d_words + n_tiles);
-    if (n_set > 0) HIPCHK(hipMemcpyAsync(d_set, q.set.data(), (size_t)n_set * 8, hipMemcpyHostToDevice, st));
-    // (tp and wp were built for the same rows: rows + 1 offsets, n_tiles valid words, n_tiles words of wp)
-    mask_tags_kernel<<<where_grid(n_tiles), WHERE_BLOCK, (size_t)n_set * 8, st>>>(
-        tp->d_off, tp->d_vals, tp->d_valid, rows, n_tiles, d_set, n_set, (uint32_t)q.t, negate ? 1 : 0,
-        wp ? wp->d_words : nullptr, combine, p->d_words);
+    int64_t *d_set = reinterpret_cast<int64_t *>(p->words.d + n_tiles);
+    if (n_set > 0) HIPCHK(hipMemcpyAsync(d_set, set, (size_t)n_set * 8, hipMemcpyHostToDevice, st));
+    launch(st, rows, n_tiles, d_set, wp ? wp->words.d : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->d_words, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(p->h_words.data(), p->words.d, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
   return mask_finish_part(p, s, rows, n_tiles);
 }
 
-// A part's words put back where slice_mask would take them from: bit r of the words = bit row_base + r of the GLOBAL
-// bitmap (bits holds at least (row_base + rows + 7) / 8 + 1 bytes; or-ed in: neighbouring shards may share a byte)
-void unslice_mask(int64_t row_base, int64_t rows, const uint64_t *words, uint8_t *bits) {
-  const uint8_t *wb = reinterpret_cast<const uint8_t *>(words);
-  const int64_t nbytes = (rows + 7) / 8, b0 = row_base / 8;
-  const int sh = (int)(row_base & 7);
-  if (sh == 0) {
-    for (int64_t i = 0; i < nbytes; ++i) bits[b0 + i] |= wb[i];
-    return;
+// tsh_mask_create_range, _where and _tags behind their argument checks and their plan: the with check, the new handle,
+// every shard's part by words(g, s, part) -- which fetches the columns' parts and ends in mask_device_part -- the handle's
+// GLOBAL bitmap, registration.  cols: the column handles the words are made from.  They stay as they are until every part
+// is made: their use_mu are held shared, taken in one order, by address -- two calls that name the same handles in
+// opposite orders cannot hold one each while a _set waits between them -- and all given up before g_mask_mu is taken to
+// register: a _set holds that one while it waits for these
+template <class C, class F>
+int32_t make_device_mask(tsh_index *idx, tsh_mask *with, tsh_mask **out, C *const *cols, int n_cols, F &&words) {
+  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
+  std::unique_ptr<tsh_mask> m(new tsh_mask());
+  m->idx = idx;
+  int rc = TSH_OK;
+  {
+    C *order[WHERE_MAX_COLUMNS];
+    std::copy(cols, cols + n_cols, order);
+    std::sort(order, order + n_cols, std::less<C *>());
+    std::vector<std::shared_lock<std::shared_mutex>> use;
+    use.reserve((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c) use.emplace_back(order[c]->use_mu);
+    rc = make_parts(m.get(), [&](size_t g, Shard *s, MaskPart *p) {
+      int prc = words(g, s, p);
+      if (prc) return prc;
+      // the handle's GLOBAL bitmap, as a bitmap-made handle holds it: what a rebuild after an append slices (the rows it
+      // keeps then are the rows it keeps now) and what tsh_mask_read copies
+      try {
+        const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
+        if (m->bits.size() < need) m->bits.resize(need, 0);
+      } catch (...) {
+        return set_err(TSH_E_OOM, "no memory for the mask's bitmap");
+      }
+      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
+      return (int)TSH_OK;
+    });
   }
-  for (int64_t i = 0; i < nbytes; ++i) {
-    const unsigned v = wb[i];
-    bits[b0 + i] |= (uint8_t)(v << sh);
-    if (v >> (8 - sh)) bits[b0 + i + 1] |= (uint8_t)(v >> (8 - sh));
-  }
+  if (rc) return rc;
+  return register_handle(m, out);
 }
 
 // tsh_groups::spans: one pass over the array against the shards' row ranges.  A multi-device index cuts its rows at
@@ -3605,28 +3556,11 @@ int32_t tsh_index_create_shard(int32_t dim, int32_t metric, int64_t capacity_row
 int32_t tsh_index_destroy(tsh_index *idx) {
   if (!idx) return TSH_OK;
   {
-    // mask handles still alive are orphaned: their device parts go now, the structs stay for tsh_mask_destroy
     std::lock_guard<std::mutex> lk(g_mask_mu);
-    for (tsh_mask *m : idx->masks) {
-      for (auto &p : m->parts) mask_part_free(p.get());
-      m->idx = nullptr;
-    }
-    idx->masks.clear();
-    for (tsh_groups *g : idx->groups) {  // groups handles the same way
-      for (auto &p : g->parts) groups_part_free(p.get());
-      g->idx = nullptr;
-    }
-    idx->groups.clear();
-    for (tsh_attr *a : idx->attrs) {  // ... and attribute handles
-      for (auto &p : a->parts) attr_part_free(p.get());
-      a->idx = nullptr;
-    }
-    idx->attrs.clear();
-    for (tsh_tags *t : idx->tags) {  // ... and tag handles
-      for (auto &p : t->parts) tags_part_free(p.get());
-      t->idx = nullptr;
-    }
-    idx->tags.clear();
+    orphan_handles(idx->masks);
+    orphan_handles(idx->groups);
+    orphan_handles(idx->attrs);
+    orphan_handles(idx->tags);
   }
   idx->workers.reset();  // joins the shard threads
   for (auto &s : idx->shards) {
@@ -3925,74 +3859,39 @@ int32_t tsh_groups_create(tsh_index *idx, const int32_t *group_of, int64_t n, in
   } catch (...) {
     return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)n);
   }
-  for (size_t i = 0; i < idx->shards.size(); ++i) g->parts.emplace_back(new GroupPart());
   try {
     groups_update_spans(g.get());
   } catch (...) {
     return set_err(TSH_E_OOM, "no memory for %d groups' shards", n_groups);
   }
-  {
-    std::lock_guard<std::mutex> lk(g->mu);
-    for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
-      Shard *s = idx->shards[i].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      rc = groups_build_part(g.get(), g->parts[i].get(), s);
-    }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : g->parts) groups_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->groups.push_back(g.get());
-  }
-  *out = g.release();
-  return TSH_OK;
+  rc = make_parts(g.get());
+  if (rc) return rc;
+  return register_handle(g, out);
 }
 
 int32_t tsh_groups_set(void *groups, int64_t first_row_id, int64_t n, const int32_t *group_of) {
   tsh_groups *g = static_cast<tsh_groups *>(groups);
   if (!g) return set_err(TSH_E_BAD_ARG, "groups is NULL");
   if (first_row_id < 0 || n < 0 || (n > 0 && !group_of)) return set_err(TSH_E_BAD_ARG, "group_of is NULL / negative row range");
-  std::lock_guard<std::mutex> hold(g_mask_mu);  // (the index cannot be destroyed under the call)
-  tsh_index *idx = g->idx;
-  if (!idx) return set_err(TSH_E_BAD_ARG, "the groups handle's index was destroyed");
-  int rc = check_group_ids(group_of, n, g->n_groups);
-  if (rc) return rc;
-  if (n == 0) return TSH_OK;
-  std::lock_guard<std::mutex> lk(idx->mu);  // as an append does
-  std::unique_lock<std::shared_mutex> xl(g->use_mu);
-  try {
-    if ((int64_t)g->group_of.size() < first_row_id + n) g->group_of.resize((size_t)(first_row_id + n), -1);
-  } catch (...) {
-    return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)(first_row_id + n));
-  }
-  memcpy(g->group_of.data() + first_row_id, group_of, (size_t)n * sizeof(int32_t));
-  try {
-    groups_update_spans(g);
-  } catch (...) {
-    g->spans = true;  // (no memory for the pass: the exact-all route is always right)
-  }
-  for (auto &p : g->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next search of each shard
-  return TSH_OK;
+  return set_column(
+      g, "the groups handle's index was destroyed", n, [&] { return check_group_ids(group_of, n, g->n_groups); },
+      [&] {
+        try {
+          if ((int64_t)g->group_of.size() < first_row_id + n) g->group_of.resize((size_t)(first_row_id + n), -1);
+        } catch (...) {
+          return set_err(TSH_E_OOM, "no memory for %lld group ids", (long long)(first_row_id + n));
+        }
+        memcpy(g->group_of.data() + first_row_id, group_of, (size_t)n * sizeof(int32_t));
+        try {
+          groups_update_spans(g);
+        } catch (...) {
+          g->spans = true;  // (no memory for the pass: the exact-all route is always right)
+        }
+        return (int)TSH_OK;
+      });
 }
 
-int32_t tsh_groups_destroy(void *groups_p) {
-  tsh_groups *g = static_cast<tsh_groups *>(groups_p);
-  if (!g) return TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    if (tsh_index *idx = g->idx) {  // (an orphan's parts went with its index)
-      idx->groups.erase(std::remove(idx->groups.begin(), idx->groups.end(), g), idx->groups.end());
-      for (auto &p : g->parts) groups_part_free(p.get());
-    }
-  }
-  delete g;
-  return TSH_OK;
-}
+int32_t tsh_groups_destroy(void *groups_p) { return destroy_handle(static_cast<tsh_groups *>(groups_p)); }
 
 int32_t tsh_search_grouped(tsh_index *idx, const float *queries, int32_t nq, int32_t k, double thr, const uint8_t *row_mask,
                            tsh_mask *mask_h, void *groups_p, int64_t *out_ids, double *out_dist, int32_t *out_group,
@@ -4028,7 +3927,7 @@ int32_t tsh_search_grouped(tsh_index *idx, const float *queries, int32_t nq, int
     so.spill = &spills[g];
     so.extra = &extras[g];
     int prc = TSH_OK;
-    so.groups = groups_part(groups, g, s, &prc);
+    so.groups = current_part(groups, g, s, &prc);
     if (!so.groups) return prc;
     MaskSrc ms;
     int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
@@ -4114,7 +4013,7 @@ int grouped_after_impl(tsh_index *idx, const float *queries, int32_t nq, int32_t
       so.count_thr = thr;
     }
     int prc = TSH_OK;
-    so.groups = groups_part(groups, g, s, &prc);
+    so.groups = current_part(groups, g, s, &prc);
     if (!so.groups) return prc;
     MaskSrc ms;
     int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
@@ -4249,7 +4148,7 @@ int32_t tsh_search_grouped_rows(tsh_index *idx, const float *queries, int32_t nq
     so.group_rows = m;
     so.exact_all = exact_all || !s->quar_ids.empty();
     int prc = TSH_OK;
-    so.groups = groups_part(groups, g, s, &prc);
+    so.groups = current_part(groups, g, s, &prc);
     if (!so.groups) return prc;
     MaskSrc ms;
     int mrc = call_mask_for_shard(CallMask{row_mask, mask_h}, g, s, &ms);
@@ -4301,43 +4200,11 @@ int32_t tsh_mask_create(tsh_index *idx, const uint8_t *bits, int64_t n_bytes, ts
   } catch (...) {
     return set_err(TSH_E_OOM, "no memory for a %lld-byte mask", (long long)n_bytes);
   }
-  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
-  // every shard's part now: a handle exists to take this work out of the searches
-  int rc = TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(m->mu);
-    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
-      Shard *s = idx->shards[g].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      rc = mask_build_part(m.get(), m->parts[g].get(), s);
-    }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : m->parts) mask_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->masks.push_back(m.get());
-  }
-  *out = m.release();
-  return TSH_OK;
+  if (const int rc = make_parts(m.get())) return rc;
+  return register_handle(m, out);
 }
 
-int32_t tsh_mask_destroy(tsh_mask *mask) {
-  if (!mask) return TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    if (tsh_index *idx = mask->idx) {  // (an orphan's parts went with its index)
-      idx->masks.erase(std::remove(idx->masks.begin(), idx->masks.end(), mask), idx->masks.end());
-      for (auto &p : mask->parts) mask_part_free(p.get());
-    }
-  }
-  delete mask;
-  return TSH_OK;
-}
+int32_t tsh_mask_destroy(tsh_mask *mask) { return destroy_handle(mask); }
 
 int64_t tsh_mask_kept(tsh_mask *mask) {
   if (!mask) return set_err(TSH_E_BAD_ARG, "mask is NULL");
@@ -4349,7 +4216,7 @@ int64_t tsh_mask_kept(tsh_mask *mask) {
     Shard *s = idx->shards[g].get();
     std::shared_lock<RwLock> sl = share(idx, s);
     int rc = TSH_OK;
-    const MaskPart *p = mask_part(mask, g, s, &rc);
+    const MaskPart *p = current_part(mask, g, s, &rc);
     if (!p) return rc;
     kept += p->kept;
   }
@@ -4372,63 +4239,26 @@ int32_t tsh_attr_create(tsh_index *idx, const int64_t *values, int64_t n, void *
   } catch (...) {
     return set_err(TSH_E_OOM, "no memory for %lld attribute values", (long long)n);
   }
-  for (size_t i = 0; i < idx->shards.size(); ++i) a->parts.emplace_back(new AttrPart());
-  int rc = TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
-      Shard *s = idx->shards[i].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      rc = attr_build_part(a.get(), a->parts[i].get(), s);
-    }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : a->parts) attr_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->attrs.push_back(a.get());
-  }
-  *out = a.release();
-  return TSH_OK;
+  if (const int rc = make_parts(a.get())) return rc;
+  return register_handle(a, out);
 }
 
 int32_t tsh_attr_set(void *attr, int64_t first_row_id, int64_t n, const int64_t *values) {
   tsh_attr *a = static_cast<tsh_attr *>(attr);
   if (!a) return set_err(TSH_E_BAD_ARG, "attr is NULL");
   if (first_row_id < 0 || n < 0 || (n > 0 && !values)) return set_err(TSH_E_BAD_ARG, "values is NULL / negative row range");
-  std::lock_guard<std::mutex> hold(g_mask_mu);  // (the index cannot be destroyed under the call)
-  tsh_index *idx = a->idx;
-  if (!idx) return set_err(TSH_E_BAD_ARG, "the attribute handle's index was destroyed");
-  if (n == 0) return TSH_OK;
-  std::lock_guard<std::mutex> lk(idx->mu);  // as an append does
-  std::unique_lock<std::shared_mutex> xl(a->use_mu);
-  try {
-    if ((int64_t)a->values.size() < first_row_id + n) a->values.resize((size_t)(first_row_id + n), ATTR_NULL);
-  } catch (...) {
-    return set_err(TSH_E_OOM, "no memory for %lld attribute values", (long long)(first_row_id + n));
-  }
-  memcpy(a->values.data() + first_row_id, values, (size_t)n * sizeof(int64_t));
-  for (auto &p : a->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next mask made of each shard
-  return TSH_OK;
+  return set_column(a, "the attribute handle's index was destroyed", n, no_check, [&] {
+    try {
+      if ((int64_t)a->values.size() < first_row_id + n) a->values.resize((size_t)(first_row_id + n), ATTR_NULL);
+    } catch (...) {
+      return set_err(TSH_E_OOM, "no memory for %lld attribute values", (long long)(first_row_id + n));
+    }
+    memcpy(a->values.data() + first_row_id, values, (size_t)n * sizeof(int64_t));
+    return (int)TSH_OK;
+  });
 }
 
-int32_t tsh_attr_destroy(void *attr) {
-  tsh_attr *a = static_cast<tsh_attr *>(attr);
-  if (!a) return TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    if (tsh_index *idx = a->idx) {  // (an orphan's parts went with its index)
-      idx->attrs.erase(std::remove(idx->attrs.begin(), idx->attrs.end(), a), idx->attrs.end());
-      for (auto &p : a->parts) attr_part_free(p.get());
-    }
-  }
-  delete a;
-  return TSH_OK;
-}
+int32_t tsh_attr_destroy(void *attr) { return destroy_handle(static_cast<tsh_attr *>(attr)); }
 
 int32_t tsh_mask_create_range(tsh_index *idx, void *attr_p, int64_t lo, int64_t hi, int32_t negate, tsh_mask *with,
                               int32_t combine, tsh_mask **out) {
@@ -4439,55 +4269,20 @@ int32_t tsh_mask_create_range(tsh_index *idx, void *attr_p, int64_t lo, int64_t 
   if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
   if (!attr) return set_err(TSH_E_BAD_ARG, "attr is NULL");
   if (attr->idx != idx) return set_err(TSH_E_BAD_ARG, "the attribute handle was made for another index (or its index was destroyed)");
-  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
-  std::unique_ptr<tsh_mask> m(new tsh_mask());
-  m->idx = idx;
-  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
-  int rc = TSH_OK;
-  {
-    // the column stays as it is until every part is made (given up before g_mask_mu is taken below: tsh_attr_set holds
-    // that one while it waits for this one)
-    std::shared_lock<std::shared_mutex> use(attr->use_mu);
-    std::lock_guard<std::mutex> lk(m->mu);
-    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
-      Shard *s = idx->shards[g].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      const AttrPart *ap = attr_part(attr, g, s, &rc);
-      if (!ap) break;
-      const MaskPart *wp = with ? mask_part(with, g, s, &rc) : nullptr;
-      if (with && !wp) break;
-      MaskPart *p = m->parts[g].get();
-      rc = mask_range_part(p, s, ap, lo, hi, negate != 0, wp, combine);
-      if (rc) break;
-      // the handle's GLOBAL bitmap, as a bitmap-made handle holds it: what a rebuild after an append slices (the rows it
-      // keeps then are the rows it keeps now) and what tsh_mask_read copies
-      try {
-        const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
-        if (m->bits.size() < need) m->bits.resize(need, 0);
-      } catch (...) {
-        rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
-        break;
-      }
-      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
-    }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : m->parts) mask_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->masks.push_back(m.get());
-  }
-  *out = m.release();
-  return TSH_OK;
+  return make_device_mask(idx, with, out, &attr, 1, [&](size_t g, Shard *s, MaskPart *p) {
+    int rc = TSH_OK;
+    const AttrPart *ap = current_part(attr, g, s, &rc);
+    if (!ap) return rc;
+    return mask_device_part(p, s, with, g, nullptr, 0, [&](hipStream_t st, int64_t rows, int32_t n_tiles, int64_t *, const uint64_t *d_with) {
+      mask_range_kernel<<<where_grid(n_tiles), WHERE_BLOCK, 0, st>>>(ap->vals.d, rows, n_tiles, lo, hi, negate != 0 ? 1 : 0, d_with,
+                                                                     combine, p->words.d);
+    });
+  });
 }
 
 // A whole WHERE clause in one launch and one finish per shard (tsh_where_plan.h plans it, W2 of tsh_where.hip.h runs it).
-// Modelled on tsh_mask_create_range line for line; what differs is the plan in front and one attr_part per distinct
-// column.  Everything that can be refused is refused before any device work.  (terms travels as void *: see the header)
+// make_device_mask as tsh_mask_create_range; what differs is the plan in front and one part per distinct column.
+// Everything that can be refused is refused before any device work.  (terms travels as void *: see the header)
 int32_t tsh_mask_create_where(tsh_index *idx, const void *terms_p, int32_t n_terms, tsh_mask *with, int32_t combine,
                               tsh_mask **out) {
   const tsh_where_term *terms = static_cast<const tsh_where_term *>(terms_p);
@@ -4520,63 +4315,29 @@ int32_t tsh_mask_create_where(tsh_index *idx, const void *terms_p, int32_t n_ter
     attrs[c] = static_cast<tsh_attr *>(const_cast<void *>(plan.columns[c]));
     if (attrs[c]->idx != idx) return set_err(TSH_E_BAD_ARG, "the attribute handle was made for another index (or its index was destroyed)");
   }
-  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
-  std::unique_ptr<tsh_mask> m(new tsh_mask());
-  m->idx = idx;
-  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
-  int rc = TSH_OK;
-  {
-    // every column stays as it is until every part is made.  The handles are taken in one order, by address: two calls
-    // that name the same handles in opposite orders cannot hold one each while a tsh_attr_set waits between them.  (All
-    // given up before g_mask_mu is taken below: tsh_attr_set holds that one while it waits for these)
-    tsh_attr *order[WHERE_MAX_COLUMNS];
-    std::copy(attrs, attrs + plan.n_cols, order);
-    std::sort(order, order + plan.n_cols, std::less<tsh_attr *>());
-    std::vector<std::shared_lock<std::shared_mutex>> use;
-    use.reserve((size_t)plan.n_cols);
-    for (int c = 0; c < plan.n_cols; ++c) use.emplace_back(order[c]->use_mu);
-    std::lock_guard<std::mutex> lk(m->mu);
-    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
-      Shard *s = idx->shards[g].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      const AttrPart *aps[WHERE_MAX_COLUMNS] = {};
-      for (int c = 0; c < plan.n_cols; ++c) {
-        aps[c] = attr_part(attrs[c], g, s, &rc);
-        if (!aps[c]) break;
-      }
-      if (rc) break;
-      const MaskPart *wp = with ? mask_part(with, g, s, &rc) : nullptr;
-      if (with && !wp) break;
-      MaskPart *p = m->parts[g].get();
-      rc = mask_where_part(p, s, plan, aps, wp, combine);
-      if (rc) break;
-      // the handle's GLOBAL bitmap, as for a range-made handle
-      try {
-        const size_t need = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
-        if (m->bits.size() < need) m->bits.resize(need, 0);
-      } catch (...) {
-        rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
-        break;
-      }
-      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
+  // (with is checked after the columns: a refusal make_device_mask makes ahead of any device work)
+  const int32_t n_set = (int32_t)plan.set.size();
+  return make_device_mask(idx, with, out, attrs, plan.n_cols, [&](size_t g, Shard *s, MaskPart *p) {
+    int rc = TSH_OK;
+    WhereArgs a{};
+    for (int c = 0; c < plan.n_cols; ++c) {
+      const AttrPart *ap = current_part(attrs[c], g, s, &rc);
+      if (!ap) return rc;
+      a.cols[c] = ap->vals.d;
     }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : m->parts) mask_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->masks.push_back(m.get());
-  }
-  *out = m.release();
-  return TSH_OK;
+    memcpy(a.terms, plan.terms, sizeof(a.terms[0]) * (size_t)plan.n_terms);
+    a.n_terms = plan.n_terms;
+    a.n_cols = plan.n_cols;
+    a.n_set = n_set;
+    a.combine = combine;
+    return mask_device_part(p, s, with, g, plan.set.data(), n_set, [&](hipStream_t st, int64_t rows, int32_t n_tiles, int64_t *d_set, const uint64_t *d_with) {
+      mask_where_kernel<<<where_grid(n_tiles), WHERE_BLOCK, (size_t)n_set * 8, st>>>(a, rows, n_tiles, d_set, d_with, p->words.d);
+    });
+  });
 }
 
 // ---- tag columns: an array-valued WHERE term made into a mask handle on the device (tsh_tags.hip.h) ----------------------
-// Modelled on the attribute entries above line for line; the column's normalisation, tsh_tags_set's splice, the slices and
+// The attribute entries' shape; the column's normalisation, tsh_tags_set's splice, the slices and
 // the term's set are tsh_tags_plan.h's.  (The tag handle travels as void *, and create's out as the address of one)
 int32_t tsh_tags_create(tsh_index *idx, const int64_t *offsets, int64_t n, const int64_t *values, void *out_p) {
   tsh_tags **out = static_cast<tsh_tags **>(out_p);
@@ -4599,28 +4360,8 @@ int32_t tsh_tags_create(tsh_index *idx, const int64_t *offsets, int64_t n, const
     if (!tags_slice_fits(tags_slice_values(t->col, s->row_base, s->rows)))
       return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(TAGS_PLAN_SLICE_VALUES));
   }
-  for (size_t i = 0; i < idx->shards.size(); ++i) t->parts.emplace_back(new TagsPart());
-  int rc = TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(t->mu);
-    for (size_t i = 0; i < idx->shards.size() && rc == TSH_OK; ++i) {
-      Shard *s = idx->shards[i].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      rc = tags_build_part(t.get(), t->parts[i].get(), s);
-    }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : t->parts) tags_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->tags.push_back(t.get());
-  }
-  *out = t.release();
-  return TSH_OK;
+  if (const int rc = make_parts(t.get())) return rc;
+  return register_handle(t, out);
 }
 
 int32_t tsh_tags_set(void *tags, int64_t first_row_id, int64_t n, const int64_t *offsets, const int64_t *values) {
@@ -4628,36 +4369,19 @@ int32_t tsh_tags_set(void *tags, int64_t first_row_id, int64_t n, const int64_t 
   if (!t) return set_err(TSH_E_BAD_ARG, "tags is NULL");
   if (first_row_id < 0) return set_err(TSH_E_BAD_ARG, "first_row_id < 0");
   if (const int e = tags_check_csr(offsets, n, values)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
-  std::lock_guard<std::mutex> hold(g_mask_mu);  // (the index cannot be destroyed under the call)
-  tsh_index *idx = t->idx;
-  if (!idx) return set_err(TSH_E_BAD_ARG, "the tag handle's index was destroyed");
-  if (n == 0) return TSH_OK;
-  std::lock_guard<std::mutex> lk(idx->mu);  // as an append does
-  std::unique_lock<std::shared_mutex> xl(t->use_mu);
-  try {
-    if (const int e = tags_splice(&t->col, first_row_id, n, offsets, values)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
-  } catch (...) {
-    return set_err(TSH_E_OOM, "no memory for the tag lists of %lld rows", (long long)(first_row_id + n));
-  }
-  for (auto &p : t->parts) p->built_rows.store(-1, std::memory_order_release);  // rebuilt by the next mask made of each shard
-  return TSH_OK;
-}
-
-int32_t tsh_tags_destroy(void *tags) {
-  tsh_tags *t = static_cast<tsh_tags *>(tags);
-  if (!t) return TSH_OK;
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    if (tsh_index *idx = t->idx) {  // (an orphan's parts went with its index)
-      idx->tags.erase(std::remove(idx->tags.begin(), idx->tags.end(), t), idx->tags.end());
-      for (auto &p : t->parts) tags_part_free(p.get());
+  return set_column(t, "the tag handle's index was destroyed", n, no_check, [&] {
+    try {
+      if (const int e = tags_splice(&t->col, first_row_id, n, offsets, values)) return set_err(TSH_E_BAD_ARG, "%s", tags_plan_error(e));
+    } catch (...) {
+      return set_err(TSH_E_OOM, "no memory for the tag lists of %lld rows", (long long)(first_row_id + n));
     }
-  }
-  delete t;
-  return TSH_OK;
+    return (int)TSH_OK;
+  });
 }
 
-// Modelled on tsh_mask_create_range line for line; what differs is the term's set in front (tags_query) and the part it
+int32_t tsh_tags_destroy(void *tags) { return destroy_handle(static_cast<tsh_tags *>(tags)); }
+
+// make_device_mask as tsh_mask_create_range; what differs is the term's set in front (tags_query) and the part it
 // reads.  Everything that can be refused on the arguments is refused before any device work
 int32_t tsh_mask_create_tags(tsh_index *idx, void *tags_p, const int64_t *set, int64_t n_set, int32_t need, int32_t negate,
                              tsh_mask *with, int32_t combine, tsh_mask **out) {
@@ -4674,49 +4398,17 @@ int32_t tsh_mask_create_tags(tsh_index *idx, void *tags_p, const int64_t *set, i
     return set_err(TSH_E_OOM, "no memory for the term's set");
   }
   if (tags->idx != idx) return set_err(TSH_E_BAD_ARG, "the tag handle was made for another index (or its index was destroyed)");
-  if (with && with->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
-  std::unique_ptr<tsh_mask> m(new tsh_mask());
-  m->idx = idx;
-  for (size_t g = 0; g < idx->shards.size(); ++g) m->parts.emplace_back(new MaskPart());
-  int rc = TSH_OK;
-  {
-    // the column stays as it is until every part is made (given up before g_mask_mu is taken below: tsh_tags_set holds
-    // that one while it waits for this one)
-    std::shared_lock<std::shared_mutex> use(tags->use_mu);
-    std::lock_guard<std::mutex> lk(m->mu);
-    for (size_t g = 0; g < idx->shards.size() && rc == TSH_OK; ++g) {
-      Shard *s = idx->shards[g].get();
-      std::shared_lock<RwLock> sl = share(idx, s);
-      const TagsPart *tp = tags_part(tags, g, s, &rc);
-      if (!tp) break;
-      const MaskPart *wp = with ? mask_part(with, g, s, &rc) : nullptr;
-      if (with && !wp) break;
-      MaskPart *p = m->parts[g].get();
-      rc = mask_tags_part(p, s, tp, q, negate != 0, wp, combine);
-      if (rc) break;
-      // the handle's GLOBAL bitmap, as for a range-made handle
-      try {
-        const size_t need_bytes = (size_t)((s->row_base + s->rows + 7) / 8) + 1;
-        if (m->bits.size() < need_bytes) m->bits.resize(need_bytes, 0);
-      } catch (...) {
-        rc = set_err(TSH_E_OOM, "no memory for the mask's bitmap");
-        break;
-      }
-      if (s->rows > 0) unslice_mask(s->row_base, s->rows, p->h_words.data(), m->bits.data());
-    }
-  }
-  if (rc) {
-    const std::string keep = g_err;
-    for (auto &p : m->parts) mask_part_free(p.get());
-    g_err = keep;
-    return rc;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_mask_mu);
-    idx->masks.push_back(m.get());
-  }
-  *out = m.release();
-  return TSH_OK;
+  const int32_t n_q = (int32_t)q.set.size();
+  return make_device_mask(idx, with, out, &tags, 1, [&](size_t g, Shard *s, MaskPart *p) {
+    int rc = TSH_OK;
+    const TagsPart *tp = current_part(tags, g, s, &rc);
+    if (!tp) return rc;
+    // (tp was built for the same rows: rows + 1 offsets, n_tiles valid words)
+    return mask_device_part(p, s, with, g, q.set.data(), n_q, [&](hipStream_t st, int64_t rows, int32_t n_tiles, int64_t *d_set, const uint64_t *d_with) {
+      mask_tags_kernel<<<where_grid(n_tiles), WHERE_BLOCK, (size_t)n_q * 8, st>>>(tp->off.d, tp->vals.d, tp->valid.d, rows, n_tiles, d_set, n_q,
+                                                                                  (uint32_t)q.t, negate != 0 ? 1 : 0, d_with, combine, p->words.d);
+    });
+  });
 }
 
 int32_t tsh_mask_read(tsh_mask *mask, uint8_t *out_bits, int64_t n_bytes) {
@@ -4899,7 +4591,7 @@ int32_t search_shard_impl(tsh_index *idx, const ShardSearchReq &r, void *stream)
   so.d_blocks = r.d_blocks;
   so.user_stream = static_cast<hipStream_t>(stream);
   so.after = r.after;
-  if (r.groups && !(so.groups = groups_part(r.groups, 0, s, &rc))) return rc;
+  if (r.groups && !(so.groups = current_part(r.groups, 0, s, &rc))) return rc;
   if (r.after || r.groups)  // a cursor call or a grouped call is never batched: every query is its own scan
     return shard_search_blocks(s, r.queries, r.nq, r.k, ms, r.entries, &so, PIPE_DEPTH);
   return shard_search_any(s, s->batch, idx->batch_min_nq.load(), r.queries, r.nq, r.k, ms, r.entries, &so);
@@ -5035,7 +4727,7 @@ struct tsh_shard_stream {
     const int32_t min_nq = idx->batch_min_nq.load();
     const int32_t st = opt.step > 0 ? std::min(opt.step, nq) : nq;
     const GroupPart *gpart = nullptr;
-    if (req.groups && !(gpart = groups_part(req.groups, 0, s, &mrc))) return mrc;
+    if (req.groups && !(gpart = current_part(req.groups, 0, s, &mrc))) return mrc;
     // (a cursor call or a grouped call is never batched, whatever step or the handle's batch threshold say)
     if (req.after || gpart || !shard_takes_batch(s, min_nq, st, k)) {  // one pipeline over all queries
       done_q.assign((size_t)nq, 0);
