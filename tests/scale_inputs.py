@@ -28,6 +28,10 @@ scan_f16_band_lib.cpp, scan_i8_band_lib.cpp, batch_plan_lib.cpp), never from the
                2 (|q| ((4 nch + 6) 2^-23 + 2^-21) + d 7.5e-37) 1.0001); "demanded" -- no wide-band fallback -- when the
                rows whose exact key less its own error is inside the band of the k-th smallest exact tile minimum (what
                the select takes for tau) plus its error stay below 96; else "free"
+  4-bit        i4_facts() (L2, dense; tests/test_gpu_scales_i4.py): "demanded" where the int8 band and tsh_scan_i4_band.h
+               (tests/cpp/scan_i4_band_lib.cpp) are ok for every query and the survivors of the NumPy model
+               (scan_i4_model.py) stay at or below SCAN_I4_MAX_SHARE of the rows; "refused" where the 4-bit band's ok is
+               false for every query; else "free"
   batched      batch_facts(): the kernel a forced option runs as and the queries the call drops (tsh_batch_plan.h), the
                tombstones of the second pass (every query's nearest row dead), and the most rows a query can have on
                its candidate list (batch_candidates) -- below half of cand_cap nothing but the dropped queries may be
@@ -336,6 +340,35 @@ def facts(d, case, metric):
             routes["int8"] = "refused" if f.safe else ("demanded" if all(f.i8_ok) else "free")
         f.routes[masked] = routes
     return f
+
+
+@functools.lru_cache(maxsize=None)
+def i4_facts(d, case):
+    """The 4-bit first pass in front of the int8 scan (L2, dense: the only shape it takes) for one case and width, on the
+    rows, queries and reduced keys of facts(d, case, L2).  ok per query from tsh_scan_i4_band.h itself (tests/cpp/
+    scan_i4_band_lib.cpp), the survivors from the NumPy model (scan_i4_model.Shard.survivors: at most).  The route:
+      "demanded"  the int8 band and the 4-bit band are ok for every query and the model's survivors stay at or below
+                  SCAN_I4_MAX_SHARE of the rows for every query -- no scan can be denied: each query runs one 4-bit and
+                  one int8 scan;
+      "refused"   the 4-bit band's ok is false for every query: the pass never runs and its probe refuses;
+      "free"      otherwise (a band as wide as the keys keeps every row, and the deny rule may act)."""
+    import scan_i4_inputs as si4
+    import scan_i4_model as M
+
+    f = facts(d, case, L2)
+    g = Facts()
+    g.d, g.case, g.rows, g.qs, g.reduced, g.i8_ok, g.safe = d, case, f.rows, f.qs, f.reduced, f.i8_ok, f.safe
+    g.i4_ok = [si4.header_band(q, f.stats[0], f.stats[2])[0] for q in f.qs]
+    sh = M.Shard(f.rows)
+    with np.errstate(all="ignore"):
+        g.survivors = [sh.survivors(q, K)[1] if ok else None for q, ok in zip(f.qs, g.i4_ok)]
+    if f.safe or not any(g.i4_ok):
+        g.route = "refused"
+    elif all(g.i4_ok) and all(g.i8_ok) and max(g.survivors) <= int(M.MAX_SHARE * N):
+        g.route = "demanded"
+    else:
+        g.route = "free"
+    return g
 
 
 @functools.lru_cache(maxsize=None)

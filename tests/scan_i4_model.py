@@ -29,6 +29,8 @@ def nibbles(biased):
 
 
 def rho_of(rows, s, h):
+    """|v_i - recon4_i|_2 over the row's dim elements, rounded up, as rows4_convert_kernel sums it: the pad elements up to
+    ld (code 8: 8 s_i each) meet no query element and are left out."""
     recon = (16 * h + 8 - 128).astype(np.float64) * s.astype(np.float64)[:, None]
     r = np.sqrt(((rows.astype(np.float64) - recon) ** 2).sum(axis=1)) * (1.0 + 1e-6)
     f = r.astype(np.float32)
@@ -41,11 +43,12 @@ def _up(x):
 
 
 def band(q, dim, ld, max_norm, max_abs):
-    """scan_i4_band: (a_s, a_r, a_c, a_v, beta, qbias), f32."""
+    """scan_i4_band: (a_s, a_r, a_c, a_v, beta, qbias), f32 -- the header's values bit for bit (test_host_scan_i4_widths.py):
+    the three sums over q run element by element, as the header's loop does."""
     q64 = np.asarray(q, dtype=np.float64)[:dim]
     groups = (ld + GROUP - 1) // GROUP
-    q1, qs = np.abs(q64).sum(), q64.sum()
-    qn = np.sqrt((q64 * q64).sum()) * (1.0 + 1e-6)
+    q1, qs, qn2 = (np.add.accumulate(x)[-1] for x in (np.abs(q64), q64, q64 * q64))
+    qn = np.sqrt(qn2) * (1.0 + 1e-6)
     smax = float(max_abs) / 127.0 * (1.0 + 1e-6)
     gam = (8.0 * groups + 8.0) * U2
     kar = 256.0 * gam + 512.0 * U
@@ -76,6 +79,11 @@ class Shard:
 
     def sides(self, q):
         """(lower, upper, margin) per row, f64: margin covers the device's f32 chain and epilogue against this model's."""
+        x, w, margin = self.key_and_band(q)
+        return x - w, x + w, margin
+
+    def key_and_band(self, q):
+        """(key, band, margin) per row, f64: the middle of [lower, upper] and half its width."""
         a_s, a_r, a_c, a_v, beta, qb = (float(x) for x in band(q, self.dim, self.ld, self.max_norm, self.max_abs))
         q64 = np.asarray(q, dtype=np.float64)
         acc = self.h.astype(np.float64) @ q64
@@ -85,7 +93,7 @@ class Shard:
         w = np.minimum(a_s * s, a_r * rho + a_c * s) + a_v * np.sqrt(sq) + beta
         # the device's own roundings: the chain, the bias, the scale (a_c s covers twice their sum), four epilogue roundings
         margin = a_c * s + 4.0 * U2 * (np.abs(x) + w) + 1e-6 * w
-        return x - w, x + w, margin
+        return x, w, margin
 
     def survivors(self, q, k):
         """(at least, at most) rows whose lower side is at or below tau = the k-th smallest tile minimum of upper sides;

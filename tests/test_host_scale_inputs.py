@@ -143,6 +143,30 @@ def test_routes_that_may_be_demanded(d):
     assert demanded >= (180 if d == 768 else 120)  # what the sweep demands is not nothing
 
 
+@pytest.mark.parametrize("d", si.WIDTHS)
+def test_the_4bit_routes_that_may_be_demanded(d):
+    """scale_inputs.i4_facts (L2, dense), for tests/test_gpu_scales_i4.py: tsh_scan_i4_band.h says ok for every query of
+    every case -- its refusal lines (a largest scale below 2^-126 or above 1e30, a widest band of 1e37) lie outside these
+    corpora: 2^-118 times the largest element over 127 is still 1.2e-37 -- so no case is refused.  Demanded: wherever the
+    model's survivors stay a tenth of the rows below the share.  Free, with (nearly) every row a survivor: keys of 2^-200
+    and less, far below the band's underflow terms (2^-118, 2^-100); L2 with queries 2^40 above the rows, where the
+    oracle's own (d + 4) 2^-52 |q|^2 is in the band ((-40, 40), and (0, 40) at d = 768: at d = 32 that term is 2^38 beside
+    keys 2^42 apart); norms 2^30 apart at d = 768, where a_v max|v| of the longest rows swallows the short rows' keys."""
+    import scan_i4_model as M
+
+    share = int(M.MAX_SHARE * N)
+    free = {"-118,-118", "-100,-100", "-40,40"} | ({"0,40", "mixed"} if d == 768 else set())
+    for case in si.CASES:
+        g = si.i4_facts(d, case)
+        print("d=%d %s: %s, the model's survivors at most %s" % (d, case, g.route, g.survivors))
+        assert all(g.i4_ok) and all(g.i8_ok) and not g.safe, case
+        if case in free:
+            assert g.route == "free" and min(g.survivors) >= 0.9 * N, case
+        else:
+            assert g.route == "demanded" and K <= min(g.survivors) and max(g.survivors) <= share - 0.10 * N, case
+    assert share == 339
+
+
 def test_the_f32_band_is_the_designs():
     """spot values of the formulas at d = 768: nch = 3"""
     q = np.zeros(768, np.float32)

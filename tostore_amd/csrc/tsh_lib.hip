@@ -1498,7 +1498,7 @@ bool rows4_ensure(Shard *s, hipStream_t st) {
   return row_copy_ensure(s, s->rows4, s->cap * groups * 16 + s->cap * 4, false, st, [&](int64_t r0, int64_t r1) {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((r1 - r0 + 3) / 4, 16384));
     rows4_convert_kernel<<<grid, 256, 0, st>>>(s->d_rows, static_cast<const uint8_t *>(s->rows8.d), rows8_scales(s->rows8, s->ld),
-                                               static_cast<uint32_t *>(s->rows4.d), rows4_rho(s->rows4, groups), s->ld, groups, r0, r1);
+                                               static_cast<uint32_t *>(s->rows4.d), rows4_rho(s->rows4, groups), s->ld, s->dim, groups, r0, r1);
   });
 }
 

@@ -178,11 +178,11 @@ static __global__ void __launch_bounds__(1024) i4_total_kernel(const uint64_t *m
 }
 
 // rows [r0, r1) of the int8 copy -> the 4-bit plane and rho: a wave per row, a lane per dword of eight codes.  rho is
-// summed in f64 against the f32 rows (s_i times an integer is exact there) and rounded up.  Elements past ld: the code of
-// zero (biased byte 128).
+// summed in f64 against the f32 rows (s_i times an integer is exact there), over the row's dim elements -- the pad elements
+// up to ld meet no query element -- and rounded up.  Elements past dim: the code of zero (biased byte 128).
 static __global__ void __launch_bounds__(256) rows4_convert_kernel(const float *rows, const uint8_t *rows8, const float *scale8,
-                                                                   uint32_t *plane, float *rho, int64_t ld, int groups, int64_t r0,
-                                                                   int64_t r1) {
+                                                                   uint32_t *plane, float *rho, int64_t ld, int dim, int groups,
+                                                                   int64_t r0, int64_t r1) {
   const int lane = threadIdx.x & 63;
   const int64_t w0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
   for (int64_t r = r0 + w0; r < r1; r += nw) {
@@ -199,8 +199,10 @@ static __global__ void __launch_bounds__(256) rows4_convert_kernel(const float *
         uint32_t h = 8u;
         if (j < ld) {
           h = (uint32_t)src8[j] >> 4;
-          const double diff = (double)src[j] - s * (double)(16 * (int)h + 8 - 128);
-          ss += diff * diff;
+          if (j < dim) {
+            const double diff = (double)src[j] - s * (double)(16 * (int)h + 8 - 128);
+            ss += diff * diff;
+          }
         }
         word |= h << (8 * (e & 3) + 4 * (e >> 2));
       }

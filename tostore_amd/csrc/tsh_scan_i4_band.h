@@ -6,7 +6,8 @@
 // recon4_ij = (16 h_ij + 8 - 128) s_i.  With u = 2^-24:
 //   |b_ij - (16 h_ij + 8)| <= 8          and          |v_ij - s_i c_ij| <= s_i (1/2 + 127 u)   (the int8 copy's)
 //   => |v_ij - recon4_ij| <= s_i (8 + 1/2 + 127 u)
-// Beside the nibbles a row has rho_i >= |v_i - recon4_i|_2, formed in f64 at conversion and rounded up.
+// Beside the nibbles a row has rho_i >= |v_i - recon4_i|_2, formed in f64 at conversion and rounded up: over the row's dim
+// elements -- the pad elements up to ld hold the code of zero, meet no query element and are no part of rho.
 // L2 only.  The kernel forms  acc = sum_j q_j * float(h_ij)  in f32 FMAs, in SCAN_I4_ACC chains of 8 FMAs per group of 32
 // elements, added up at the end (m = 8 groups + 8 roundings at the most on an element's way, gam = m 2^-23),
 // t = fma(16, acc, -qb) with qb = fl((128 - 8) sum_j q_j) from the host (f64 sum, one rounding), dot = fl(s_i t), and
