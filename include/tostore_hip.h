@@ -61,6 +61,8 @@ extern "C" {
 /*    Additive since, same version, continued: tsh_mask_create_where (tsh_where_term, TSH_TERM_*, TSH_WHERE_MAX_*). */
 /*    Additive since, same version, continued: tsh_tags_create, tsh_tags_set, tsh_tags_destroy, tsh_mask_create_tags
  *    (TSH_TAGS_ALL, TSH_TAGS_ANY, TSH_TAGS_MAX_SET_VALUES). */
+/*    Additive since, same version, continued: tsh_attr_facets, tsh_tags_facets
+ *    (TSH_FACET_VALUES, TSH_FACET_EDGES, TSH_FACET_MAX_KEYS). */
 
 /* status codes */
 #define TSH_OK 0
@@ -534,6 +536,53 @@ int32_t tsh_tags_set(void *tags, int64_t first_row_id, int64_t n, const int64_t 
 int32_t tsh_tags_destroy(void *tags);
 int32_t tsh_mask_create_tags(tsh_index *idx, void *tags, const int64_t *set, int64_t n_set, int32_t need,
                              int32_t negate, tsh_mask *with, int32_t combine, tsh_mask **out);
+
+/* ---- facet counts: rows per value of an attribute or tag column, on the device (additive since ABI 5) -----------------
+ * A search screen that filters by the columns above also shows their facets: "Brand: A (312), B (207)", "Price: under 10
+ * (1 204), 10 - 50 (3 310)", "tags: gpu (88), rocm (41)".  Without these entries a caller reads the mask back and walks the
+ * column on the host, or makes one mask handle per value and pays a tsh_search_count each.  The column, the mask's words
+ * and the live bitmap are on the device already; one launch per shard counts there (F1 attr_facets_kernel, F2
+ * tags_facets_kernel, tostore_amd/csrc/tsh_facet.hip.h; the host side is tsh_facet_plan.h): a wave per 64 rows, each
+ * lane's bucket found by a branch-free search of the keys in LDS, 32-bit counters in LDS, one 64-bit add per nonzero
+ * counter and workgroup at the end.
+ *
+ * The population P -- the rows a search under `mask` could return: row ids 0 <= i < tsh_index_size that are present (not a
+ *   gap, not an absent page), not tombstoned and, if `mask` is given, kept by it (rows beyond its bitmap are not kept;
+ *   mask == NULL is no filter).  Quarantined rows (non-finite or huge elements) are in P: searches return them.  On a
+ *   shard handle P is the shard's own rows under the GLOBAL mask and the GLOBAL column, and the caller adds the ranks'
+ *   answers; a handle over several devices sums its shards itself.
+ *   out_rest[2] == tsh_search_count(any finite query, threshold NaN, no cursor, the same mask).
+ * tsh_attr_facets: v_i is the column's value of row i; rows beyond the column read as TSH_ATTR_NULL.
+ *   TSH_FACET_VALUES: keys in any order, duplicates allowed; out_counts[j] = #{i in P : v_i == keys[j]} in the caller's
+ *   order (a repeated key repeats its count; a TSH_ATTR_NULL among the keys matches nothing).
+ *   TSH_FACET_EDGES: keys ascend strictly and keys[0] != TSH_ATTR_NULL; bucket j counts keys[j] <= v_i < keys[j + 1] and
+ *   the last bucket v_i >= keys[n_keys - 1]: a value equal to an edge falls in the bucket that edge opens.
+ *   out_rest[0] = "other", the rows of P with a non-NULL value in no bucket; out_rest[1] = the rows of P whose value is
+ *   NULL; out_rest[2] = |P|.  The counts of the distinct keys + out_rest[0] + out_rest[1] == out_rest[2].  n_keys == 0 is
+ *   legal: out_counts is not written, every non-NULL row is "other", keys and out_counts may be NULL.
+ * tsh_tags_facets: a row is a set, NULL if its list holds TSH_ATTR_NULL or it lies beyond the column; an empty list is a
+ *   value.  out_counts[j] = #{i in P : row i not NULL, keys[j] in row_i}; out_rest[0] = the non-NULL rows of P that hold
+ *   none of the keys (empty sets included); out_rest[1] = the NULL rows of P; out_rest[2] = |P|.
+ * The answer is exact: NumPy on the host is the specification; the adds are integer adds, so two runs agree bit for bit.
+ *   The column is read as it stands when the call runs -- no handle is made, so there is no snapshot.  An empty index
+ *   gives zeros.
+ * TSH_E_BAD_ARG (each answered before any device work, nothing is written): a NULL idx, column or out_rest; n_keys < 0;
+ *   NULL keys or out_counts with n_keys > 0; more than TSH_FACET_MAX_KEYS distinct non-NULL keys; a kind that is neither
+ *   constant; edges that do not ascend strictly or start with TSH_ATTR_NULL; a column or mask made for another index, or
+ *   an orphaned one.
+ * Threads: any number of calls may share the handles; tsh_attr_set and tsh_tags_set wait for them, as they do for the
+ *   mask makers.
+ * Cost: DESIGN.md, "facet counts".
+ * Not here: facets under a distance threshold; discovering the distinct values without keys (the bindings' dictionaries
+ *   know them); more than TSH_FACET_MAX_KEYS keys in one call -- chain calls; a ticket form; collective (sharded) summing
+ *   -- every rank answers for its rows. */
+#define TSH_FACET_VALUES 0      /* bucket j: rows whose value == keys[j] */
+#define TSH_FACET_EDGES  1      /* bucket j: keys[j] <= value < keys[j+1]; the last bucket: value >= keys[n_keys-1] */
+#define TSH_FACET_MAX_KEYS 4096 /* distinct non-NULL keys of one call */
+int32_t tsh_attr_facets(tsh_index *idx, void *attr, tsh_mask *mask, int32_t kind, const int64_t *keys, int64_t n_keys,
+                        int64_t *out_counts, int64_t *out_rest);
+int32_t tsh_tags_facets(tsh_index *idx, void *tags, tsh_mask *mask, const int64_t *keys, int64_t n_keys,
+                        int64_t *out_counts, int64_t *out_rest);
 
 /* Asynchronous form of a single-query tsh_search, for callers that keep several
  * independent queries in flight (the reference serves concurrent vectorSearch

@@ -36,6 +36,8 @@ TSH_TERM_RANGE, TSH_TERM_IN = 0, 1  # tsh_where_term.kind (tsh_mask_create_where
 TSH_WHERE_MAX_TERMS, TSH_WHERE_MAX_COLUMNS, TSH_WHERE_MAX_SET_VALUES = 32, 8, 4096
 TSH_TAGS_ALL, TSH_TAGS_ANY = 0, 1  # tsh_mask_create_tags' need (any n >= 1: at least n distinct values of the set)
 TSH_TAGS_MAX_SET_VALUES = 4096
+TSH_FACET_VALUES, TSH_FACET_EDGES = 0, 1  # tsh_attr_facets' kind: a bucket per key, or per interval between ascending edges
+TSH_FACET_MAX_KEYS = 4096
 
 c_i32, c_i64, c_f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 p_f32 = ctypes.POINTER(ctypes.c_float)
@@ -121,6 +123,8 @@ SIGNATURES = {
     "tsh_tags_set": (c_i32, [p_void, c_i64, c_i64, p_i64, p_i64]),
     "tsh_tags_destroy": (c_i32, [p_void]),
     "tsh_mask_create_tags": (c_i32, [p_void, p_void, p_i64, c_i64, c_i32, c_i32, p_void, c_i32, ctypes.POINTER(p_void)]),
+    "tsh_attr_facets": (c_i32, [p_void, p_void, p_void, c_i32, p_i64, c_i64, p_i64, p_i64]),
+    "tsh_tags_facets": (c_i32, [p_void, p_void, p_void, p_i64, c_i64, p_i64, p_i64]),
     "tsh_search_masked": (c_i32, [p_void, p_f32, c_i32, c_i32, c_f64, p_void, p_i64, p_f64, p_i32]),
     "tsh_search_submit_masked": (c_i32, [p_void, p_f32, c_i32, p_void, p_i32]),
     "tsh_max_inflight": (c_i32, []),

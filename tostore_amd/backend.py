@@ -384,6 +384,37 @@ class HipVectorIndex:
         snapshot: later `tags.set()` calls and appends do not change it."""
         return HipMask._tags(self, tags, values, need, negate, with_mask, combine)
 
+    def facets(self, column, keys, row_mask: Optional["HipMask"] = None, kind="values"):
+        """Facet counts ON the device (`tsh_attr_facets` / `tsh_tags_facets`): over the rows a search under `row_mask` (None
+        or a HipMask) could return, `(counts, other, null, total)` -- counts[j] (int64) for every key as given, the rows
+        with a value in no bucket, the rows without a value, and all of them.  `column` is a `HipAttr` -- kind="values":
+        the rows whose value == keys[j], keys in any order; kind="edges": keys[j] <= value < keys[j + 1], the last bucket
+        open, keys strictly ascending -- or a `HipTags`: the rows whose set holds keys[j].  At most 4096 distinct keys.  The
+        column is read as it stands: no snapshot."""
+        if not isinstance(column, (HipAttr, HipTags)):
+            raise TypeError("column must be a HipAttr or a HipTags")
+        ch = column.handle()  # (a closed handle raises here, before the library is called)
+        mh = None
+        if row_mask is not None:
+            if not isinstance(row_mask, HipMask):
+                raise TypeError("row_mask must be a HipMask (or None)")
+            mh = row_mask.handle()
+        if kind not in ("values", "edges"):
+            raise ValueError("kind must be 'values' or 'edges'")
+        if isinstance(column, HipTags) and kind != "values":
+            raise ValueError("a tag column counts by value: kind must be 'values'")
+        k = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        counts, rest = np.zeros(k.shape[0], dtype=np.int64), np.zeros(3, dtype=np.int64)
+        pk = k.ctypes.data_as(_ffi.p_i64) if k.shape[0] else None
+        pc = counts.ctypes.data_as(_ffi.p_i64) if k.shape[0] else None
+        pr = rest.ctypes.data_as(_ffi.p_i64)
+        if isinstance(column, HipAttr):
+            code = _ffi.TSH_FACET_EDGES if kind == "edges" else _ffi.TSH_FACET_VALUES
+            _ffi.check(_ffi.lib().tsh_attr_facets(self._h, ch, mh, code, pk, k.shape[0], pc, pr))
+        else:
+            _ffi.check(_ffi.lib().tsh_tags_facets(self._h, ch, mh, pk, k.shape[0], pc, pr))
+        return counts, int(rest[0]), int(rest[1]), int(rest[2])
+
     def _live_masks(self) -> "weakref.WeakSet":
         """The masks and groups handles made for this index and not yet closed: close() closes them before it destroys
         the index."""

@@ -27,7 +27,7 @@ _KERN = ["tsh_kernels.hip.h", "tsh_block.h", "tsh_scan_tile.inc.h", "tsh_batch.h
 UNITS = {
     "tsh_scan_tu.hip": _KERN,
     "tsh_batch_tu.hip": _KERN + ["tsh_batch_f16.hip.h", "tsh_batch_f16pp.hip.h"],
-    "tsh_lib.hip": _KERN + ["tsh_batch_f16.hip.h", "tsh_batch_f16pp.hip.h", "tsh_exact.hip.h", "tsh_mask.hip.h", "tsh_where.hip.h", "tsh_where_plan.h", "tsh_tags.hip.h", "tsh_tags_plan.h", "tsh_host_sync.h", "tsh_pq.hip.h", "tsh_scan_f16_band.h", "tsh_scan_i8_band.h", "tsh_scan_i8.hip.h", "tsh_scan_i4_band.h", "tsh_scan_i4.hip.h",
+    "tsh_lib.hip": _KERN + ["tsh_batch_f16.hip.h", "tsh_batch_f16pp.hip.h", "tsh_exact.hip.h", "tsh_mask.hip.h", "tsh_where.hip.h", "tsh_where_plan.h", "tsh_tags.hip.h", "tsh_tags_plan.h", "tsh_facet.hip.h", "tsh_facet_plan.h", "tsh_host_sync.h", "tsh_pq.hip.h", "tsh_scan_f16_band.h", "tsh_scan_i8_band.h", "tsh_scan_i8.hip.h", "tsh_scan_i4_band.h", "tsh_scan_i4.hip.h",
                             "tsh_after.hip.h", "tsh_after_band.h", "tsh_count.hip.h", "tsh_count_band.h", "tsh_group.hip.h", "tsh_group_rule.h", "tsh_group_after_rule.h", "tsh_group_rows.hip.h", "tsh_group_rows_rule.h", "tsh_finalize.h", "tsh_batch_plan.h",
                             "tsh_host_batch.inl.h", "tsh_host_coldstart.inl.h", "tsh_host_pq.inl.h",
                             "tsh_host_comm.inl.h"],

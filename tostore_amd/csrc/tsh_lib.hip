@@ -53,6 +53,7 @@
 #include "tsh_scan_i4.hip.h"
 #include "tsh_where.hip.h"
 #include "tsh_tags.hip.h"
+#include "tsh_facet.hip.h"
 
 using namespace tsh;
 
@@ -319,6 +320,11 @@ struct Shard {
   std::vector<uint32_t> quar_ids;
   uint32_t *d_quar = nullptr;
   uint32_t *d_irr = nullptr;  // 1 + QUARANTINE_MAX: count and ids of the irregular rows of one append
+  // a facet call's keys and 64-bit counters (tsh_attr_facets, tsh_tags_facets): 2 |S| + 3 words, grown on demand and kept
+  // between calls; facet_mu covers a call's upload, launch and copy back on this shard
+  int64_t *d_facet = nullptr;
+  int64_t facet_cap = 0;
+  std::mutex facet_mu;
   hipStream_t ingest_stream = nullptr;  // all streams below belong to the device's DeviceStreams
   hipStream_t aux_stream = nullptr;
   // every query's scan -> select -> rerank runs on this one in-order stream,
@@ -2914,6 +2920,7 @@ void shard_destroy(Shard *s) {
   hipFree(s->d_del_ids);
   hipFree(s->d_quar);
   hipFree(s->d_irr);
+  hipFree(s->d_facet);
   if (s->holds_streams) {
     s->holds_streams = false;
     device_streams_release(s->device);
@@ -3473,6 +3480,84 @@ int write_empty_blocks(Shard *s, int32_t nq, int32_t k, int32_t entries, uint32_
     h->pad[1] = tag;
   }
   HIPCHK(hipMemcpy(d_blocks, z.data(), z.size(), hipMemcpyHostToDevice));
+  return TSH_OK;
+}
+
+// ---- facet counts (tsh_attr_facets, tsh_tags_facets; tsh_facet.hip.h, tsh_facet_plan.h) -------------------------------------
+// What the two entries refuse on their arguments alone, in the header's order; no handle is dereferenced
+int facet_check_args(tsh_index *idx, const void *col, const char *col_name, int32_t kind, const int64_t *keys, int64_t n_keys,
+                     const int64_t *out_counts, const int64_t *out_rest, FacetKeys *k) {
+  if (!out_rest) return set_err(TSH_E_BAD_ARG, "out_rest is NULL");
+  if (!idx) return set_err(TSH_E_BAD_ARG, "index is NULL");
+  if (!col) return set_err(TSH_E_BAD_ARG, "%s is NULL", col_name);
+  try {
+    if (const int e = facet_keys(kind, keys, n_keys, k)) return set_err(TSH_E_BAD_ARG, "%s", facet_plan_error(e));
+  } catch (...) {
+    return set_err(TSH_E_OOM, "no memory for the keys");
+  }
+  if (n_keys > 0 && !out_counts) return set_err(TSH_E_BAD_ARG, "out_counts is NULL with n_keys > 0");
+  return TSH_OK;
+}
+
+// The call behind the argument checks, for either column kind H.  col->use_mu is held shared for the whole call (a _set
+// waits for it, as for a mask maker); per shard, side by side: the shard's shared lock, the column's and the mask's part
+// made current for the shard's rows, then -- under the shard's facet_mu -- the keys go up behind zeroed counters in the
+// shard's scratch, launch(st, s, column part, mask words or nullptr, n_words, d_set, d_cnt) enqueues the one kernel on
+// aux_stream and the |S| + 3 counters come back in one copy.  The device live bitmap has the quarantined rows' bits
+// clear -- in safe mode too: the rows past QUARANTINE_MAX keep their bits and are counted on the device -- so the host adds
+// the listed ones: quar(s, the mask's words on the host or nullptr, counters).  Then the sum over shards and the scatter
+template <class H, class L, class Q>
+int32_t facet_call(tsh_index *idx, H *col, tsh_mask *mask, const FacetKeys &k, int64_t *out_counts, int64_t *out_rest, L &&launch,
+                   Q &&quar) {
+  const size_t ns = idx->shards.size(), n_cnt = k.counters();
+  const int32_t n_set = k.n();
+  std::vector<std::vector<uint64_t>> cnt(ns);
+  std::shared_lock<std::shared_mutex> use(col->use_mu);
+  int rc = for_each_shard(idx, [&](size_t g) -> int {
+    Shard *s = idx->shards[g].get();
+    std::shared_lock<RwLock> sl = share(idx, s);
+    if (s->rows == 0) return TSH_OK;
+    try {
+      cnt[g].assign(n_cnt, 0);
+    } catch (...) {
+      return set_err(TSH_E_OOM, "no memory for %zu counters", n_cnt);
+    }
+    int prc = TSH_OK;
+    const PartOf<H> *cp = current_part(col, g, s, &prc);
+    if (!cp) return prc;
+    const MaskPart *mp = mask ? current_part(mask, g, s, &prc) : nullptr;
+    if (mask && !mp) return prc;
+    HIPCHK(hipSetDevice(s->device));
+    const int32_t n_words = (int32_t)((s->rows + 63) / 64);
+    {
+      std::lock_guard<std::mutex> lk(s->facet_mu);
+      const int64_t need = (int64_t)n_cnt + n_set;
+      if (s->facet_cap < need) {
+        hipFree(s->d_facet);
+        s->d_facet = nullptr;
+        s->facet_cap = 0;
+        const int64_t grown = round_up(need + need / 8, 1024);
+        HIPCHK(hipMalloc(&s->d_facet, (size_t)grown * 8));
+        s->facet_cap = grown;
+      }
+      hipStream_t st = s->aux_stream;
+      unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(s->d_facet);
+      int64_t *d_set = s->d_facet + n_cnt;
+      HIPCHK(hipMemsetAsync(d_cnt, 0, n_cnt * 8, st));
+      if (n_set > 0) HIPCHK(hipMemcpyAsync(d_set, k.set.data(), (size_t)n_set * 8, hipMemcpyHostToDevice, st));
+      launch(st, s, cp, mp ? mp->words.d : nullptr, n_words, d_set, d_cnt);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cnt[g].data(), d_cnt, n_cnt * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    if (!s->quar_ids.empty()) quar(s, mp ? mp->h_words.data() : nullptr, cnt[g].data());
+    return TSH_OK;
+  });
+  if (rc) return rc;
+  std::vector<uint64_t> all(n_cnt, 0);
+  for (size_t g = 0; g < ns; ++g)
+    if (!cnt[g].empty()) facet_add(all.data(), cnt[g].data(), n_cnt);
+  facet_scatter(k, all.data(), out_counts, out_rest);
   return TSH_OK;
 }
 
@@ -4409,6 +4494,48 @@ int32_t tsh_mask_create_tags(tsh_index *idx, void *tags_p, const int64_t *set, i
                                                                                   (uint32_t)q.t, negate != 0 ? 1 : 0, d_with, combine, p->words.d);
     });
   });
+}
+
+// ---- facet counts: rows per value of an attribute or tag column, over the rows a search could return ----------------------
+// facet_call does the work; what differs is the part a kernel reads and the column copy the quarantined rows are read from
+int32_t tsh_attr_facets(tsh_index *idx, void *attr_p, tsh_mask *mask, int32_t kind, const int64_t *keys, int64_t n_keys,
+                        int64_t *out_counts, int64_t *out_rest) {
+  tsh_attr *attr = static_cast<tsh_attr *>(attr_p);
+  FacetKeys k;
+  if (const int rc = facet_check_args(idx, attr, "attr", kind, keys, n_keys, out_counts, out_rest, &k)) return rc;
+  if (attr->idx != idx) return set_err(TSH_E_BAD_ARG, "the attribute handle was made for another index (or its index was destroyed)");
+  if (mask && mask->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
+  return facet_call(
+      idx, attr, mask, k, out_counts, out_rest,
+      [&](hipStream_t st, Shard *s, const AttrPart *ap, const uint64_t *d_mask, int32_t n_words, const int64_t *d_set,
+          unsigned long long *d_cnt) {
+        attr_facets_kernel<<<facet_grid(n_words), FACET_BLOCK, facet_lds_bytes(k.n()), st>>>(ap->vals.d, s->d_live, d_mask, s->rows, n_words,
+                                                                                             d_set, k.n(), k.kind, d_cnt);
+      },
+      [&](const Shard *s, const uint64_t *mask_words, uint64_t *cnt) {
+        facet_quar_attr(k, s->quar_ids.data(), s->quar_ids.size(), mask_words, attr->values.data(), (int64_t)attr->values.size(),
+                        s->row_base, cnt);
+      });
+}
+
+int32_t tsh_tags_facets(tsh_index *idx, void *tags_p, tsh_mask *mask, const int64_t *keys, int64_t n_keys, int64_t *out_counts,
+                        int64_t *out_rest) {
+  tsh_tags *tags = static_cast<tsh_tags *>(tags_p);
+  FacetKeys k;
+  if (const int rc = facet_check_args(idx, tags, "tags", FACET_VALUES, keys, n_keys, out_counts, out_rest, &k)) return rc;
+  if (tags->idx != idx) return set_err(TSH_E_BAD_ARG, "the tag handle was made for another index (or its index was destroyed)");
+  if (mask && mask->idx != idx) return set_err(TSH_E_BAD_ARG, "the mask handle was made for another index (or its index was destroyed)");
+  return facet_call(
+      idx, tags, mask, k, out_counts, out_rest,
+      [&](hipStream_t st, Shard *s, const TagsPart *tp, const uint64_t *d_mask, int32_t n_words, const int64_t *d_set,
+          unsigned long long *d_cnt) {
+        // (tp was built for the same rows: rows + 1 offsets, n_words valid words)
+        tags_facets_kernel<<<facet_grid(n_words), FACET_BLOCK, facet_lds_bytes(k.n()), st>>>(tp->off.d, tp->vals.d, tp->valid.d, s->d_live, d_mask,
+                                                                                             s->rows, n_words, d_set, k.n(), d_cnt);
+      },
+      [&](const Shard *s, const uint64_t *mask_words, uint64_t *cnt) {
+        facet_quar_tags(k, s->quar_ids.data(), s->quar_ids.size(), mask_words, tags->col, s->row_base, cnt);
+      });
 }
 
 int32_t tsh_mask_read(tsh_mask *mask, uint8_t *out_bits, int64_t n_bytes) {

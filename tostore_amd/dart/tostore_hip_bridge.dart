@@ -91,6 +91,14 @@ typedef _MaskCreateTagsC = Int32 Function(
     Pointer<Void>, Pointer<Void>, Pointer<Int64>, Int64, Int32, Int32, Pointer<Void>, Int32, Pointer<Pointer<Void>>);
 typedef _MaskCreateTagsD = int Function(
     Pointer<Void>, Pointer<Void>, Pointer<Int64>, int, int, int, Pointer<Void>, int, Pointer<Pointer<Void>>);
+typedef _AttrFacetsC = Int32 Function(
+    Pointer<Void>, Pointer<Void>, Pointer<Void>, Int32, Pointer<Int64>, Int64, Pointer<Int64>, Pointer<Int64>);
+typedef _AttrFacetsD = int Function(
+    Pointer<Void>, Pointer<Void>, Pointer<Void>, int, Pointer<Int64>, int, Pointer<Int64>, Pointer<Int64>);
+typedef _TagsFacetsC = Int32 Function(
+    Pointer<Void>, Pointer<Void>, Pointer<Void>, Pointer<Int64>, Int64, Pointer<Int64>, Pointer<Int64>);
+typedef _TagsFacetsD = int Function(
+    Pointer<Void>, Pointer<Void>, Pointer<Void>, Pointer<Int64>, int, Pointer<Int64>, Pointer<Int64>);
 typedef _SearchMaskedC = Int32 Function(Pointer<Void>, Pointer<Float>, Int32, Int32, Double,
     Pointer<Void>, Pointer<Int64>, Pointer<Double>, Pointer<Int32>);
 typedef _SearchMaskedD = int Function(Pointer<Void>, Pointer<Float>, int, int, double,
@@ -524,6 +532,8 @@ final class HipVectorBackend {
   static late final _TagsSetD _tagsSet;
   static late final _TagsDestroyD _tagsDestroy;
   static late final _MaskCreateTagsD _maskCreateTags;
+  static late final _AttrFacetsD _attrFacets;
+  static late final _TagsFacetsD _tagsFacets;
   static late final _SearchMaskedD _searchMasked;
   static late final _SubmitMaskedD _submitMasked;
 
@@ -642,6 +652,8 @@ final class HipVectorBackend {
       _tagsSet = lib.lookupFunction<_TagsSetC, _TagsSetD>('tsh_tags_set');
       _tagsDestroy = lib.lookupFunction<_TagsDestroyC, _TagsDestroyD>('tsh_tags_destroy');
       _maskCreateTags = lib.lookupFunction<_MaskCreateTagsC, _MaskCreateTagsD>('tsh_mask_create_tags');
+      _attrFacets = lib.lookupFunction<_AttrFacetsC, _AttrFacetsD>('tsh_attr_facets');
+      _tagsFacets = lib.lookupFunction<_TagsFacetsC, _TagsFacetsD>('tsh_tags_facets');
       _searchMasked = lib.lookupFunction<_SearchMaskedC, _SearchMaskedD>('tsh_search_masked');
       _submitMasked =
           lib.lookupFunction<_SubmitMaskedC, _SubmitMaskedD>('tsh_search_submit_masked');
@@ -945,6 +957,37 @@ final class HipVectorBackend {
       calloc.free(out);
     }
   }
+
+  /// Facet counts ON the device (tsh_attr_facets / tsh_tags_facets) behind [HipRowAttr.facets] and [HipTagColumn.facets]:
+  /// `column` is the handle of either kind, `kind` is [facetValues] or [facetEdges] for an attribute column and null for
+  /// a tag column.  Null on any native failure.
+  HipFacetCounts? _facets(Pointer<Void> column, int? kind, Int64List keys, HipRowMask? mask) {
+    final buf = calloc<Int64>(keys.isEmpty ? 1 : keys.length);
+    final counts = calloc<Int64>(keys.isEmpty ? 1 : keys.length);
+    final rest = calloc<Int64>(3);
+    try {
+      buf.asTypedList(keys.length).setAll(0, keys);
+      final m = mask?._mask ?? nullptr;
+      final rc = kind != null
+          ? _attrFacets(_handle, column, m, kind, buf, keys.length, counts, rest)
+          : _tagsFacets(_handle, column, m, buf, keys.length, counts, rest);
+      if (rc != 0) {
+        Logger.warn('${kind != null ? 'tsh_attr_facets' : 'tsh_tags_facets'} failed ($rc): ${_errorText()}',
+            label: 'HipVectorBackend');
+        return null;
+      }
+      return HipFacetCounts(Int64List.fromList(counts.asTypedList(keys.length)), rest[0], rest[1], rest[2]);
+    } finally {
+      calloc.free(buf);
+      calloc.free(counts);
+      calloc.free(rest);
+    }
+  }
+
+  /// TSH_FACET_VALUES / TSH_FACET_EDGES and the limit of one facet call (include/tostore_hip.h).
+  static const int facetValues = 0;
+  static const int facetEdges = 1;
+  static const int facetMaxKeys = 4096;
 
   /// TSH_TAGS_ALL / TSH_TAGS_ANY and the limit of one tsh_mask_create_tags call (include/tostore_hip.h).
   static const int tagsAll = 0;
@@ -2272,6 +2315,23 @@ final class HipRowAttr {
     }
   }
 
+  /// Facet counts over the node ids a search under `mask` could return (tsh_attr_facets): counts[j] = the rows whose
+  /// value == keys[j] (keys in any order), or with `edges: true` the rows with keys[j] <= value < keys[j + 1], the last
+  /// bucket open and the keys strictly ascending; beside them the rows in no bucket, the rows without a value and all of
+  /// them.  At most [HipVectorBackend.facetMaxKeys] distinct keys.  The column is read as it stands: no snapshot.  Null
+  /// on any native failure; a disposed column or `mask` is refused (null, with a warning), never sent as NULL.
+  HipFacetCounts? facets(HipVectorBackend backend, Int64List keys, {HipRowMask? mask, bool edges = false}) {
+    if (_attr == nullptr) {
+      Logger.warn('facets with a disposed HipRowAttr', label: 'HipVectorBackend');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('facets with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    return backend._facets(_attr, edges ? HipVectorBackend.facetEdges : HipVectorBackend.facetValues, keys, mask);
+  }
+
   void dispose() {
     if (_attr != nullptr) {
       HipVectorBackend._attrDestroy(_attr);
@@ -2331,12 +2391,38 @@ final class HipTagColumn {
     }
   }
 
+  /// Facet counts over the node ids a search under `mask` could return (tsh_tags_facets): counts[j] = the rows whose set
+  /// is not NULL and holds keys[j]; beside them the non-NULL rows that hold none of the keys (empty sets included), the
+  /// NULL rows and all of them.  At most [HipVectorBackend.facetMaxKeys] distinct keys.  Null on any native failure; a
+  /// disposed column or `mask` is refused (null, with a warning), never sent as NULL.
+  HipFacetCounts? facets(HipVectorBackend backend, Int64List keys, {HipRowMask? mask}) {
+    if (_tags == nullptr) {
+      Logger.warn('facets with a disposed HipTagColumn', label: 'HipVectorBackend');
+      return null;
+    }
+    if (mask != null && mask._mask == nullptr) {
+      Logger.warn('facets with a disposed HipRowMask', label: 'HipVectorBackend');
+      return null;
+    }
+    return backend._facets(_tags, null, keys, mask);
+  }
+
   void dispose() {
     if (_tags != nullptr) {
       HipVectorBackend._tagsDestroy(_tags);
       _tags = nullptr;
     }
   }
+}
+
+/// What [HipRowAttr.facets] and [HipTagColumn.facets] answer: `counts[j]` for every key as given, then the rows in no
+/// bucket, the rows without a value, and all the rows a search under the same mask could return.
+final class HipFacetCounts {
+  final Int64List counts;
+  final int other;
+  final int nulls;
+  final int total;
+  const HipFacetCounts(this.counts, this.other, this.nulls, this.total);
 }
 
 /// One entry of [HipVectorBackend.searchGrouped]: a group's nearest row; `group` is -1 for a row that stands for itself.
